@@ -17,6 +17,10 @@ exposed after the kernel: the persistent kNN kernel owns every CU's registers an
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, before this process touches a GPU); under
 torchrun (RANK / WORLD_SIZE set, the driver's form) it is one of the ranks.  WORLD_SIZE != --gpus is an error.
 
+A plain run (`--gpus 1 --steps N --warmup W`) builds the bank, warms up, times the N steps, writes --dump-outputs if asked and
+prints the line; `--full` adds the legs beside the timed steps (A/B legs, use_fp16, end to end, counter passes, CPU baseline,
+mIoU parity; with N > 1 the oracle selftest and the per-rank A/B legs).
+
 Prints ONE JSON line on rank 0 (see README / the driver contract).
 """
 from __future__ import annotations
@@ -78,7 +82,16 @@ def parse():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # one untimed step under rocprofv3 --pmc
     ap.add_argument("--cluster-shape", type=int, nargs=2, default=[0, 0], metavar=("Q", "B"), help="L2-sharing cluster shape of the fp32 searches "
                     "(0 0 = automatic: kept where they measure faster; 1 1 = none; the counter passes repeat the timed steps' form)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run everything beside the timed steps: N = 1: the A/B legs, use_fp16, end to end, "
+                    "counter passes, CPU baseline, mIoU parity; N > 1: the oracle selftest and the per-rank A/B legs (the --no-* options "
+                    "drop single legs).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "(label_hat [nq, C] fp32, all queries of all ranks) as DIR/label_hat.npy; above 64 MB a fixed seeded sample of rows, "
+                    "whose ids go to DIR/label_hat_rows.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def images_note(nq):
@@ -202,10 +215,30 @@ def emit(res):
     os.write(_JSON_FD if _JSON_FD is not None else 1, (json.dumps(res) + "\n").encode())
 
 
+DUMP_BYTES = 64_000_000 - 4096     # --dump-outputs: the files' budget (64 MB, less the .npy headers)
+
+
+def dump_outputs(out_dir, label_hat):
+    """--dump-outputs: label_hat [nq, C] fp32 of the last timed step as out_dir/label_hat.npy.  Above the budget, a fixed sample of
+    rows (seed 0, ascending ids) whose ids are written beside it as float64 (exact below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    nq, C = label_hat.shape
+    keep = min(nq, DUMP_BYTES // (4 * C + 8))
+    if keep < nq:
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        label_hat = label_hat[rows]
+        np.save(os.path.join(out_dir, "label_hat_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "label_hat.npy"), np.ascontiguousarray(label_hat, dtype=np.float32))
+
+
 def main():
     a = parse()
-    if a.timed_only:
-        a.no_ab = a.no_e2e = a.no_counters = a.no_traffic = a.no_cpu_baseline = True
+    # a plain run is the timed steps and nothing else; --timed-only (what tools/gpu_profile.sh runs) stays lean even with --full
+    lean = a.timed_only or not a.full
+    traffic_note = "skipped (--no-traffic)" if a.no_traffic else "not measured (plain run; --full measures it live)"
+    selftest_note = "skipped (--no-selftest)" if a.no_selftest else "not run (plain run; --full runs it)"
+    if lean:
+        a.no_ab = a.no_e2e = a.no_counters = a.no_traffic = a.no_cpu_baseline = a.no_selftest = True
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
         if a.gpus is not None and a.gpus > 1:
@@ -376,6 +409,13 @@ def main():
                         "rows_per_rank": [(nq * (r + 1)) // world - (nq * r) // world for r in range(world)]}
         else:
             checksum = {"bits": int(cs[0].item()), "sum": float(cs[1:].view(torch.float64).item()), "rows_per_rank": [nq]}
+    if a.dump_outputs:
+        # the last timed step's label_hat: each rank holds its slice of the queries, rank 0 writes them all in query order
+        if dist_on:
+            parts, counts = hdist.allgather_rows(last_out.contiguous())
+            last_out = torch.cat([parts[r, :counts[r]] for r in range(world)])
+        if rank == 0:
+            dump_outputs(a.dump_outputs, last_out.cpu().numpy())
     extra_legs = {}
     if dist_on:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -397,11 +437,11 @@ def main():
             return float(d.item()), float(np.mean(km))
         leg_list = []                   # every rank runs the same legs (they contain collectives); the numbers travel in `mine`
         cl_auto = tuple(index.schedule_info().get("cluster", (1, 1)))
-        if not a.fp16 and cl_auto != (1, 1):
+        if not lean and not a.fp16 and cl_auto != (1, 1):
             index.set_cluster(1, 1, 0)
             leg_list.append(("without_clusters",) + timed_leg())
             index.set_cluster(0, 0, -1)
-        if not a.fp16:
+        if not lean and not a.fp16:
             index.set_fp16(True)
             ms16, k16 = timed_leg()
             leg_list.append(("use_fp16_mode", ms16, k16))
@@ -487,7 +527,7 @@ def main():
                             "label aggregation of this rank's query slice" + (", on a side stream under the next step's kNN kernel" if overlap else
                             ", exposed after the kNN kernel (it owns every CU's registers, nothing can run beside it)"),
                 "packed_list_bytes_per_rank": ex[0].part_bytes,
-                "selftest": selftest if selftest is not None else "skipped (--no-selftest)",
+                "selftest": selftest if selftest is not None else selftest_note,
                 "replicated_label_table": f"uint16 counts (denominator {LABEL_P}), {M * C * 2 / 1e9:.2f} GB per rank",
                 "exchange_split_ms_per_rank": None if overlap else {
                     "all_gather": [round(r[4], 3) for r in per_rank], "merge": [round(r[5], 3) for r in per_rank],
@@ -510,7 +550,7 @@ def main():
         single = world == 1 and not dist_on
         if single and not a.fp16 and not a.no_ab:
             res["xcd_shares_ab"] = safe("equal_shares_leg", legs.equal_shares_leg, index, q, k, device)
-        if single and not a.fp16 and not a.timed_only:
+        if single and not a.fp16 and not lean:
             ab = safe("clusters_ab_leg", legs.clusters_ab_leg, index, q, k, device, flops, peak)
             if "failed" not in ab:        # the timed steps' own number fills the slot of the form they ran
                 ab["clustered_kernel_ms" if ab["clustered_kernel_ms"] is None else "unclustered_kernel_ms"] = kms
@@ -539,7 +579,7 @@ def main():
             res["roofline"]["clock_and_busy_source"] = "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE (child pass, one search)"
             if isinstance(res.get("use_fp16_mode"), dict) and "failed" not in res["use_fp16_mode"]:
                 res["use_fp16_mode"].update(safe("matrix_pipe_counters_fp16", legs.matrix_pipe_counters, a, "knn_f16", True))
-        got = (None, "skipped (--no-traffic)") if a.no_traffic else safe("measure_traffic", legs.measure_traffic, a, kernel)
+        got = (None, traffic_note) if a.no_traffic else safe("measure_traffic", legs.measure_traffic, a, kernel)
         traffic, note = got if isinstance(got, tuple) else (None, str(got))
         if traffic is not None and " on " in note:     # the counter pass saw the instantiation's full name
             res["roofline"]["kernel"] = note.split(" on ", 1)[1].split(":", 1)[0]
@@ -555,7 +595,7 @@ def main():
         if not a.no_cpu_baseline:
             res["cpu_baseline"] = safe("cpu_baseline", legs.cpu_baseline, D, k, M, bank_host, q_host, fetch_note)
         del bank_host
-        res["miou_parity"] = None if a.timed_only else safe("miou_parity", legs.miou_parity, device)
+        res["miou_parity"] = None if lean else safe("miou_parity", legs.miou_parity, device)
         flatten_into_roofline(res)
     if dist_on:
         td.destroy_process_group()

@@ -57,3 +57,32 @@ def test_host_budgets_and_spread():
     assert b["cores"] >= 1 and (m["available_bytes"] is None or m["available_bytes"] > 0)
     assert legs.spread([3.0, 1.0, 2.0]) == {"min": 1.0, "median": 2.0, "max": 3.0}
     assert legs.safe("boom", lambda: 1 / 0)["failed"].startswith("boom")
+
+
+def test_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes label_hat as fp32; above the byte budget a fixed seeded sample of rows (ascending) and their ids (float64)."""
+    import numpy as np
+    bench = _bench()
+    lh = np.random.default_rng(3).random((100, 5), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), lh)
+    assert sorted(os.listdir(tmp_path / "all")) == ["label_hat.npy"]
+    got = np.load(tmp_path / "all" / "label_hat.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, lh)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), lh)
+    rows = np.load(tmp_path / "s1" / "label_hat_rows.npy")
+    part = np.load(tmp_path / "s1" / "label_hat.npy")
+    assert rows.dtype == np.float64 and len(rows) == 1000 // (4 * 5 + 8) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(part, lh[rows.astype(np.int64)]) and rows.nbytes + part.nbytes <= 1000
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "label_hat_rows.npy"))
+
+
+def test_steps_must_be_positive(monkeypatch):
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out" and not a.full

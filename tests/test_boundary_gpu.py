@@ -105,7 +105,7 @@ def _run_bench(args, env_extra, timeout=900):
 
 
 _SMALL = ["--rows", "600000", "--dim", "64", "--classes", "21", "--nq", "3000", "--steps", "3", "--warmup", "1",
-          "--no-cpu-baseline", "--no-traffic"]
+          "--no-cpu-baseline", "--no-traffic", "--full"]
 
 
 def test_bench_gpus_2_runs_two_ranks(cuda_device):
@@ -143,7 +143,7 @@ def test_bench_gpus_8_ragged_shards_equal_the_single_rank_result(cuda_device):
     real all-gather (gloo here: the ranks share cuda:0) -- and the merged + aggregated result carries the same bits as the
     1-rank run (`label_hat_checksum`: int64 sum of the fp32 bit patterns over all queries)."""
     small = ["--rows", "600001", "--dim", "64", "--classes", "21", "--nq", "3001", "--steps", "2", "--warmup", "1",
-             "--no-cpu-baseline", "--no-traffic", "--checksum"]
+             "--no-cpu-baseline", "--no-traffic", "--checksum", "--full"]
     one = _run_bench(["--gpus", "1"] + small, {})
     eight = _run_bench(["--gpus", "8"] + small, {"HBIRD_BENCH_ONE_GPU": "1"}, timeout=1500)
     assert eight["n_gpus"] == 8 and eight["config"]["parallelism"] == "bank-shard8"
@@ -157,6 +157,26 @@ def test_bench_gpus_8_ragged_shards_equal_the_single_rank_result(cuda_device):
     assert c1["bits"] == c8["bits"], (c1, c8)
     assert abs(c1["sum"] - c8["sum"]) <= 1e-9 * abs(c1["sum"])
     assert abs(c1["sum"] - 3001) < 1e-2                           # soft labels: every label_hat row sums to 1
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_output(cuda_device, tmp_path):
+    """A plain run (no --full) is the timed steps and nothing else: --steps sets how many, ms_per_step is one of them, and
+    --dump-outputs writes the last timed step's label_hat -- the same array the checksum sums, and the same bits when two ranks
+    (gloo, sharing cuda:0) each compute a slice of the queries."""
+    small = ["--rows", "600001", "--dim", "64", "--classes", "21", "--nq", "3001", "--steps", "4", "--warmup", "1"]
+    one = _run_bench(["--gpus", "1", "--checksum", "--dump-outputs", str(tmp_path / "one")] + small, {})
+    assert one["steps"] == 4 and one["ms_per_step"] > 0 and one["metric"] == "query-patches/sec" and one["dtype"] == "f32"
+    assert one["value"] == pytest.approx(3001 / (one["ms_per_step"] * 1e-3), rel=1e-9)
+    for leg in ("xcd_shares_ab", "clusters_ab", "use_fp16_mode", "e2e", "cpu_baseline"):
+        assert leg not in one, leg
+    assert one["miou_parity"] is None
+    lh = np.load(tmp_path / "one" / "label_hat.npy")
+    assert lh.dtype == np.float32 and lh.shape == (3001, 21) and sorted(os.listdir(tmp_path / "one")) == ["label_hat.npy"]
+    assert int(lh.view(np.int32).astype(np.int64).sum()) == one["label_hat_checksum"]["bits"]
+    assert np.abs(lh.sum(1) - 1).max() < 1e-4
+    two = _run_bench(["--gpus", "2", "--dump-outputs", str(tmp_path / "two")] + small, {"HBIRD_BENCH_ONE_GPU": "1"})
+    assert two["n_gpus"] == 2 and two["steps"] == 4
+    assert np.array_equal(np.load(tmp_path / "two" / "label_hat.npy").view(np.uint32), lh.view(np.uint32))
 
 
 @pytest.mark.parametrize("metric,shard,fp16", [("dot_product", 1, False), ("l2", 1, False), ("l2", 0, False), ("dot_product", 1, True)])
