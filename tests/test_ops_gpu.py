@@ -260,7 +260,7 @@ def test_k6_upsample_argmax(cuda_device, B, S, C, h, w):
     got = ops.upsample_argmax(torch.from_numpy(lh).cuda(), S, h, w).cpu().numpy()
     ref = oracle.upsample_argmax(lh, S, h, w)
     assert got.shape == (B, 1, h, w)
-    assert (got == ref).mean() > 0.9999
+    assert np.array_equal(got, ref)
 
 
 def test_k6_golden_cluster_map(cuda_device, golden_dir):
@@ -269,6 +269,7 @@ def test_k6_golden_cluster_map(cuda_device, golden_dir):
         C, D, H, ps = g[f"cfg_{name}"][:4].tolist()
         lh = g[f"label_hat_{name}"]
         got = ops.upsample_argmax(torch.from_numpy(lh).cuda(), H // ps, H, H).cpu().numpy()
+        # a fraction, not equality: the fixture comes from torch's CPU F.interpolate, which orders the fp32 arithmetic differently
         assert (got == g[f"cluster_map_{name}"]).mean() > 0.9995
 
 
@@ -311,9 +312,8 @@ def test_k6_k7_fused_equals_the_two_kernels(cuda_device, B, S, C, h, w, ign):
     assert torch.equal(out, pred) and torch.equal(conf1, conf2) and int(conf1.sum()) > 0
     conf3 = torch.zeros((C, C), dtype=torch.int64, device="cuda")
     assert ops.upsample_argmax_confusion(lh, S, gt, conf3, ign) is None and torch.equal(conf3, conf2)
-    ref = oracle.confusion_matrix(gt.cpu().numpy().reshape(-1), pred.cpu().numpy().reshape(-1), C, C, ign) if hasattr(oracle, "confusion_matrix") else None
-    if ref is not None:
-        assert np.array_equal(conf1.cpu().numpy(), ref)
+    ref = oracle.confusion_matrix(gt.cpu().numpy().reshape(-1), pred.cpu().numpy().reshape(-1), C, C, ign)
+    assert np.array_equal(conf1.cpu().numpy(), ref)
     m1 = PredsmIoU(C, C, ignore_index=ign, store_reordered_preds=True); m2 = PredsmIoU(C, C, ignore_index=ign, store_reordered_preds=True)
     m1.update(gt, pred); m2.update_from_label_hat(gt, lh, S)
     assert m1.compute(True, many_to_one=True) == m2.compute(True, many_to_one=True)
