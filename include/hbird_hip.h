@@ -193,14 +193,54 @@ int hb_index_set_timing(hb_index_t* ix, int enable);
 int hb_index_last_knn_ms(const hb_index_t* ix, double* ms);
 /* Overrides for tests: number of workgroups (0 = one per CU) and bank tiles per panel (0 = auto); negative values are errors. */
 int hb_index_set_tuning(hb_index_t* ix, int workgroups, int panel_tiles);
-/* GpuIndexFlatConfig.useFloat16 (search_faiss.py:40): 1 = searches run an fp16 candidate pass (fp16 copies of the
+/* GpuIndexFlatConfig.useFloat16 (search_faiss.py:40).  Four states:
+ * 1 = searches run an fp16 candidate pass (fp16 copies of the
  * fragment tiles, fp16 MFMA, k' >= 2k candidates) followed by an exact fp32 re-rank of the candidates, so the
  * returned indices / distances are those of the fp32 search.  Every query carries a certificate (exact k-th score >
  * k'-th fp16 score + rounding bound); queries that fail it are searched again with the fp32 kernel, so the result is
  * ALWAYS the fp32 result.  Applies to k <= 128; larger k use the fp32 kernel.  2 = the same, but only for banks of at
  * least 4,096 rows with rows x queries x D >= 1.5e10 x (k' / 64)^2, k' = 2k -- below that the fp32 kernel is the faster way to the same result (what the
- * plugin's use_fp16 sets). */
+ * plugin's use_fp16 sets).  0 = the caller asked for the fp32 kernel: no candidate pass, no fp16 copy.
+ * HB_FP16_AUTO (3) = automatic, THE STATE A NEW INDEX STARTS IN: an exact search takes the certified fp16 screen where the screen is known to pay,
+ * and behaves as state 2 there (adaptive use, escalation, counters, share calibration of the candidate kernel).  That is when ALL of these hold:
+ * state 2's own rule; the search is a BIG search -- at least 30,000 k8 stages per workgroup (30-60 ms of fp32 kernel: the bound from which the fp32
+ * kernels calibrate), below which the one-off fp16 copy and the first use's stream synchronisation do not amortise, so smaller searches run exactly
+ * as under 0; the caller has not steered the fp32 kernel on this index -- any call of hb_index_set_variant, hb_index_set_tuning,
+ * hb_index_set_cluster with a shape other than 0 x 0, hb_index_set_cluster_sharing, hb_index_set_xcd_weights with a mode other than 0 or
+ * hb_index_set_search_options PINS the index to the fp32 kernel for the rest of its life (A/B switches of that kernel: who uses them wants to time
+ * and inspect it; an explicit 1 / 2 still selects the candidate pass); the process environment did not say HBIRD_EXACT_SCREEN=0 when the index was
+ * created (A/B runs of one build, fp32 roofline records); the bank has no finite value beyond the fp16 range; and the fp16 copy of the bank (half
+ * the bank's bytes again: a default index of a big bank holds 1.5 x the bank) FITS: fp32 tiles + fp16 tiles within 55 % of the device's memory and
+ * free memory above the copy plus the larger of 1/16 of the device and 2 GiB.  Under 1 / 2 a failed allocation of the copy fails the search; in the
+ * automatic state it never does -- no room, or an allocation that fails all the same, is remembered for the bank's current capacity and the search
+ * runs on the fp32 kernel.  The certificate's reach is characterised on isotropic synthetic rows only: on a bank it cannot certify the adaptive use
+ * ends up on the fp32 kernel at the fp32 kernel's speed, with every 16th search probing the chain.
+ * hb_last_search_path (named beside hb_last_error: a read-only report about the last call, not a setting of the index): what served the last search of a caller -- path = HB_PATH_FP32, HB_PATH_FP16_CHAIN (first pass, second pass for its
+ * failures, fp32 kernel for the rest) or HB_PATH_FP16_WIDE (one pass with k' = 256) -- and why (HB_WHY_*).  hb_exact_screen_replay: the decision
+ * without a GPU (tests): setting, pinned, env_off (HBIRD_EXACT_SCREEN=0 seen), k, ceiling (a later pass of a search with k > 256), rows, nq, d,
+ * stages per workgroup, overflow, have_copy (the fp16 copy exists for this capacity: memory is not asked), declined (no room was found at this
+ * capacity), free / total device bytes, bytes of the fp32 tiles and of the copy -> 1 screen / 0 fp32 kernel, *why = HB_WHY_*. */
+#define HB_FP16_AUTO 3
+#define HB_PATH_FP32 0
+#define HB_PATH_FP16_CHAIN 1
+#define HB_PATH_FP16_WIDE 2
+#define HB_WHY_EXPLICIT_FP32 0   /* state 0 */
+#define HB_WHY_EXPLICIT_FP16 1   /* state 1, or state 2 where its rule holds */
+#define HB_WHY_AUTO 2            /* automatic state, every condition held */
+#define HB_WHY_K 3               /* k > 128 */
+#define HB_WHY_CEILING 4         /* a later pass of a search with k > 256 */
+#define HB_WHY_WORK 5            /* fewer than 4,096 rows or rows x queries x D below state 2's bound */
+#define HB_WHY_SMALL 6           /* automatic: fewer than 30,000 stages per workgroup */
+#define HB_WHY_PINNED 7          /* automatic: the caller steered the fp32 kernel */
+#define HB_WHY_ENV 8             /* automatic: HBIRD_EXACT_SCREEN=0 */
+#define HB_WHY_MEMORY 9          /* automatic: no room for the fp16 copy */
+#define HB_WHY_OVERFLOW 10       /* a finite bank value beyond the fp16 range */
+#define HB_WHY_ADAPTIVE 11       /* most certificates failed lately: the fp32 kernel right away (every 16th search probes) */
 int hb_index_set_fp16(hb_index_t* ix, int enable);
+int hb_last_search_path(const hb_index_t* ix, int* path, int* reason);
+int hb_exact_screen_replay(int setting, int pinned, int env_off, int k, int ceiling, int64_t rows, int64_t nq, int d, int64_t stages_per_wg,
+                           int overflow, int have_copy, int declined, uint64_t free_bytes, uint64_t total_bytes, uint64_t bank_bytes,
+                           uint64_t copy_bytes, int* why);
 /* Number of queries of the last fp16-mode search that needed the exact fp32 re-search. */
 int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n);
 /* What happens to a query whose certificate fails.  mode 0 (default): ESCALATION -- the failing queries, compacted, get a second fp16 pass
@@ -247,7 +287,9 @@ int hb_index_wg_stamps(hb_index_t* ix, uint32_t* out, int max_blocks, int* workg
 /* The clock the last stamped kNN launch ran at, WITHOUT a profiler attached: every workgroup also stamps the shader-cycle counter
  * (s_memtime) beside the real-time counter, and (cycles / 10 ns ticks) x 100 MHz is the clock its CU held over the launch.  out[0] = median
  * over the workgroups (GHz), [1] / [2] = slowest / fastest workgroup, [3] = the launch's span in ms by the stamps (first start to last end).
- * Zeros when the last launch did not stamp (hb_index_set_timing off and no share calibration).  One stream synchronisation. */
+ * Zeros when the last launch did not stamp (hb_index_set_timing off and no share calibration).  One stream synchronisation.
+ * "The last launch" is the last launch of a CALLER's search: the nested searches of a use_fp16 search's uncertified queries neither stamp nor
+ * count (the candidate launch's stamps are kept aside before they start), so this and hb_index_wg_stamps go with hb_index_schedule_info. */
 int hb_index_kernel_clock(hb_index_t* ix, double out[4]);
 /* State of the share calibration of one kernel family (fp16_kernel as above): out[0] = calibration rounds, [1] = 1 when the GUARD has locked
  * the shares -- a share set whose launches (same shape, shortest of at least two) measured 0.15 % slower than the best set seen (the fp16

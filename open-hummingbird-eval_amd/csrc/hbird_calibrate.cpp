@@ -136,6 +136,33 @@ void hb_f16_observe(hb_f16_adapt& a, int how, int64_t nq, int64_t first_failed, 
     a.r12 = first_failed == 0 ? 0.5 * a.r12 : 0.5 * a.r12 + 0.5 * (double)reached_fp32 / (double)nq;
 }
 
+bool hb_screen_choose(const hb_screen_in& in, int* why) {
+    int w = HB_WHY_EXPLICIT_FP32;
+    bool screen = false;
+    const double kc_rel = std::min(256, std::max(64, (2 * in.k + 7) / 8 * 8)) / 64.0;
+    const bool worth = in.rows >= 4096 && (double)in.rows * (double)in.nq * (double)in.d >= 1.5e10 * kc_rel * kc_rel;
+    if (in.setting == 0) w = HB_WHY_EXPLICIT_FP32;
+    else if (in.k > 128) w = HB_WHY_K;
+    else if (in.ceiling) w = HB_WHY_CEILING;       // (only the fp32 pool kernel knows ceilings)
+    else if (in.setting == 1) { screen = true; w = HB_WHY_EXPLICIT_FP16; }
+    else if (!worth) w = HB_WHY_WORK;
+    else if (in.setting == 2) { screen = true; w = HB_WHY_EXPLICIT_FP16; }
+    else if (in.pinned) w = HB_WHY_PINNED;
+    else if (in.env_off) w = HB_WHY_ENV;
+    else if (in.stages_per_wg < 30000) w = HB_WHY_SMALL;
+    else if (in.overflow) w = HB_WHY_OVERFLOW;
+    else if (in.have_copy) { screen = true; w = HB_WHY_AUTO; }
+    else if (in.declined) w = HB_WHY_MEMORY;
+    // the optional re-rank copy's rule (hbird_knn.hip): all copies within 55 % of the device, and free memory above the need plus the larger of
+    // 1/16 of the device and 2 GiB -- the search's workspace comes after the copy, and a device shared with a model or another rank is not
+    // filled to the brim by a copy that only buys speed
+    else if (in.mem_known && !(in.bank_b + in.copy_b <= in.total_b / 100 * 55 &&
+                               in.free_b > in.copy_b + std::max<uint64_t>(in.total_b / 16, (uint64_t)2 << 30))) w = HB_WHY_MEMORY;
+    else { screen = true; w = HB_WHY_AUTO; }
+    if (why) *why = w;
+    return screen;
+}
+
 // ---- test hooks (no GPU): a calibration state fed with synthetic stamp sets -----------------------------------------------------------
 struct hb_calibration { hb_xcd_state st; int fam; };
 extern "C" void* hb_calibration_new(int fp16_kernel) { hb_calibration* h = new hb_calibration(); h->fam = fp16_kernel ? 1 : 0; return h; }
@@ -177,4 +204,15 @@ extern "C" int hb_f16_adapt_replay(int n, const double* f1, const double* f2, in
         hb_f16_observe(a, how, nq, first_failed, fp32);
     }
     return 0;
+}
+// the automatic state's decision for one imagined search (include/hbird_hip.h)
+extern "C" int hb_exact_screen_replay(int setting, int pinned, int env_off, int k, int ceiling, int64_t rows, int64_t nq, int d, int64_t stages_per_wg,
+                                      int overflow, int have_copy, int declined, uint64_t free_bytes, uint64_t total_bytes, uint64_t bank_bytes,
+                                      uint64_t copy_bytes, int* why) {
+    if (!why || setting < 0 || setting > HB_FP16_AUTO || k < 1 || rows < 0 || nq < 0 || d < 1) return -1;
+    hb_screen_in in;
+    in.setting = setting; in.pinned = pinned != 0; in.env_off = env_off != 0; in.k = k; in.ceiling = ceiling != 0; in.rows = rows; in.nq = nq; in.d = d;
+    in.stages_per_wg = stages_per_wg; in.overflow = overflow != 0; in.have_copy = have_copy != 0; in.declined = declined != 0;
+    in.mem_known = true; in.free_b = free_bytes; in.total_b = total_bytes; in.bank_b = bank_bytes; in.copy_b = copy_bytes;
+    return hb_screen_choose(in, why) ? 1 : 0;
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <array>
 #include <stdint.h>
+#include "../../include/hbird_hip.h"
 
 // What one launch's stamps say (wg_stamp, hbird_knn_dev.h: per block, at its start and at its end, {100 MHz real-time counter (low word),
 // XCC id, shader-cycle counter lo, hi}).
@@ -62,3 +63,25 @@ enum { HB_F16_CHAIN = 0, HB_F16_WIDE_FIRST = 1, HB_F16_FP32 = 2 };
 int hb_f16_choose(hb_f16_adapt& a);                                                   // how the next search runs (counts it)
 // what that search saw: `first_failed` of `nq` queries failed the first certificate it ran, `reached_fp32` went to the fp32 kernel
 void hb_f16_observe(hb_f16_adapt& a, int how, int64_t nq, int64_t first_failed, int64_t reached_fp32);
+
+// ---- the automatic state of the fp16 setting (HB_FP16_AUTO, what a new index starts in: include/hbird_hip.h) --------------------------------
+// Whether a search takes the certified fp16 screen.  States 1 / 2 keep their rules (k, ceiling, state 2's work bound); the automatic state adds:
+// a big search (>= 30,000 stages per workgroup), an index the caller has not pinned to the fp32 kernel, no HBIRD_EXACT_SCREEN=0, no overflow,
+// and room for the fp16 copy.  Memory is asked about last and only in the automatic state without a copy: the launcher calls once with
+// mem_known = false (no hipMemGetInfo for searches that stay on the fp32 kernel anyway) and, on "screen", again with the device's figures.
+struct hb_screen_in {
+    int setting = 0;              // 0 / 1 / 2 / HB_FP16_AUTO
+    bool pinned = false;          // hb_index_set_variant / _tuning / _cluster / _cluster_sharing / _xcd_weights / _search_options was used
+    bool env_off = false;         // HBIRD_EXACT_SCREEN=0 at hb_index_create
+    int k = 0;
+    bool ceiling = false;         // a later pass of a search with k > 256
+    int64_t rows = 0, nq = 0;
+    int d = 0;
+    long long stages_per_wg = 0;
+    bool overflow = false;        // the bank holds a finite value beyond the fp16 range
+    bool have_copy = false;       // the fp16 tiles exist for the bank's current capacity
+    bool declined = false;        // ... or were found not to fit at this capacity
+    bool mem_known = false;
+    uint64_t free_b = 0, total_b = 0, bank_b = 0, copy_b = 0;
+};
+bool hb_screen_choose(const hb_screen_in& in, int* why);     // -> the screen (true) or the fp32 kernel; *why = HB_WHY_*

@@ -3,6 +3,7 @@
 #include "hbird_internal.h"
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
 #include <mutex>
@@ -76,6 +77,8 @@ extern "C" int hb_index_create(int d, int metric, int device, hb_index_t** out) 
     HB_HIP(hipMemset(ix->bmax, 0, 4));
     HB_HIP(hipEventCreate(&ix->ev0));
     HB_HIP(hipEventCreate(&ix->ev1));
+    const char* es = getenv("HBIRD_EXACT_SCREEN");      // "0": the automatic fp16 state stays on the fp32 kernel (A/B runs of one build, fp32 roofline records)
+    ix->screen_env_off = es && std::strcmp(es, "0") == 0 ? 1 : 0;
     *out = ix;
     return 0;
 }
@@ -85,7 +88,7 @@ extern "C" int hb_index_free(hb_index_t* ix) {
     (void)hipSetDevice(ix->device);
     (void)hipStreamSynchronize(ix->stream);
     void* ptrs[] = {ix->tiles, ix->binit, ix->bnorm, ix->labels, ix->q_tiles, ix->q_aux, ix->state, ix->sched_dev, ix->tmp,
-                    ix->tiles16, ix->q16, ix->cand, ix->bmax, ix->fb, ix->fb1, ix->sched_esc_dev, ix->bigk, ix->mtmp, ix->f16_flag, ix->labels16, ix->lab_flag, ix->rows32};
+                    ix->tiles16, ix->stamp_keep, ix->q16, ix->cand, ix->bmax, ix->fb, ix->fb1, ix->sched_esc_dev, ix->bigk, ix->mtmp, ix->f16_flag, ix->labels16, ix->lab_flag, ix->rows32};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& c : ix->xcal) { if (c.stamp_host) (void)hipHostFree(c.stamp_host); if (c.stamp_ev) (void)hipEventDestroy(c.stamp_ev); }
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
@@ -121,12 +124,18 @@ extern "C" int hb_index_last_knn_ms(const hb_index_t* ix, double* ms) {
 extern "C" int hb_index_set_tuning(hb_index_t* ix, int workgroups, int panel_tiles) {
     if (!ix) return hb_fail("hb_index_set_tuning: NULL index handle");
     if (workgroups < 0 || panel_tiles < 0) return hb_fail("hb_index_set_tuning: negative value");
-    ix->force_G = workgroups; ix->force_panel = panel_tiles; ix->sched = hb_schedule(); return 0;
+    ix->force_G = workgroups; ix->force_panel = panel_tiles; ix->sched = hb_schedule(); ix->fp32_pinned = 1; return 0;
 }
 extern "C" int hb_index_set_fp16(hb_index_t* ix, int enable) {
     if (!ix) return hb_fail("hb_index_set_fp16: NULL index handle");
-    ix->fp16 = enable == 2 ? 2 : (enable ? 1 : 0);   // 2: only where it pays (hb_launch_knn)
+    // 2: only where it pays; HB_FP16_AUTO: the state a new index starts in (hb_screen_choose); 0: the caller asked for the fp32 kernel
+    ix->fp16 = enable == HB_FP16_AUTO ? HB_FP16_AUTO : enable == 2 ? 2 : (enable ? 1 : 0);
     ix->f16_adapt = hb_f16_adapt();
+    return 0;
+}
+extern "C" int hb_last_search_path(const hb_index_t* ix, int* path, int* reason) {
+    if (!ix || !path || !reason) return hb_fail("hb_last_search_path: NULL pointer");
+    *path = ix->last_path; *reason = ix->last_reason;
     return 0;
 }
 
@@ -152,7 +161,7 @@ extern "C" int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n) {
 extern "C" int hb_index_set_cluster_sharing(hb_index_t* ix, int mode) {
     if (!ix) return hb_fail("hb_index_set_cluster_sharing: NULL index handle");
     if (mode < 0 || mode > 2) return hb_fail("hb_index_set_cluster_sharing: mode must be 0 (automatic), 1 (off) or 2 (on)");
-    ix->xcd_share = mode; ix->sched = hb_schedule();
+    ix->xcd_share = mode; ix->sched = hb_schedule(); ix->fp32_pinned = 1;
     return 0;
 }
 
@@ -173,6 +182,7 @@ extern "C" int hb_index_set_cluster(hb_index_t* ix, int cluster_q, int cluster_b
     if (cluster_q < 0 || cluster_b < 0 || cluster_q * cluster_b > HB_CLUSTER_MAX)
         return hb_fail("hb_index_set_cluster: cluster shape must be 0 x 0 (automatic), 1 x 1 (off) or q x b with q * b <= " + std::to_string(HB_CLUSTER_MAX));
     ix->force_cq = cluster_q; ix->force_cb = cluster_b; ix->sync_lag = sync_lag; ix->sched = hb_schedule();
+    if (cluster_q != 0 || cluster_b != 0) ix->fp32_pinned = 1;      // (0 x 0 = automatic: no steering)
     return 0;
 }
 
@@ -181,13 +191,13 @@ extern "C" int hb_index_set_variant(hb_index_t* ix, int variant) {
     if (variant < 0 || variant > 6) return hb_fail("hb_index_set_variant: unknown kernel variant");
     if (variant == 1 || variant == 2 || variant == 5)
         return hb_fail("hb_index_set_variant: variants 1 (4-wave fp32 kernel), 2 (first fp16 design) and 5 (16x16x32 fp16 kernel) were removed in round 4 (same bits, not faster)");
-    ix->variant = variant;
+    ix->variant = variant; ix->fp32_pinned = 1;
     return 0;
 }
 extern "C" int hb_index_set_search_options(hb_index_t* ix, int phases, int64_t small_limit_stages) {
     if (!ix) return hb_fail("hb_index_set_search_options: NULL index handle");
     if (small_limit_stages < 0) return hb_fail("hb_index_set_search_options: negative limit");
-    ix->phases_on = phases ? 1 : 0; ix->small_limit = small_limit_stages; ix->sched = hb_schedule();
+    ix->phases_on = phases ? 1 : 0; ix->small_limit = small_limit_stages; ix->sched = hb_schedule(); ix->fp32_pinned = 1;
     return 0;
 }
 extern "C" int hb_index_set_xcd_weights(hb_index_t* ix, int mode, const double* w8) {
@@ -200,6 +210,7 @@ extern "C" int hb_index_set_xcd_weights(hb_index_t* ix, int mode, const double* 
         ix->xcal[0].w[x] = w; ix->xcal[1].w[x] = w;
     }
     ix->xcd_balance = mode;
+    if (mode != 0) ix->fp32_pinned = 1;
     for (auto& c : ix->xcal) { c.stamp_pending = 0; c.rounds = mode == 0 ? 0 : 1; c.locked = 0; c.cur_n = 0; c.best_span = 0.0; c.perm_moves = 0; }
     // (the clusters' own decision -- xcal[0].cl_* -- is a property of the box: it survives a change of the share mode)
     ix->sched = hb_schedule();
@@ -237,12 +248,14 @@ extern "C" int hb_index_kernel_clock(hb_index_t* ix, double out[4]) {
     std::vector<double> ghz;
     long long first = 0, last = 0;
     bool any = false;
+    unsigned origin = 0;                                // the start of the first block that stamped (block 0 need not have)
     for (int b = 0; b < G; ++b) {
         const unsigned* sb = h.data() + 8 * (size_t)b;
         const unsigned t0 = sb[0], t1 = sb[4];
         if (t0 == 0u && t1 == 0u) continue;             // the block did not stamp
+        if (!any) origin = t0;
         const unsigned d = t1 - t0;
-        const long long rs = (long long)(int)(t0 - h[0]), re = rs + (long long)d;
+        const long long rs = (long long)(int)(t0 - origin), re = rs + (long long)d;
         if (!any) { first = rs; last = re; any = true; }
         first = std::min(first, rs); last = std::max(last, re);
         const unsigned long long c0 = ((unsigned long long)sb[3] << 32) | sb[2], c1 = ((unsigned long long)sb[7] << 32) | sb[6];

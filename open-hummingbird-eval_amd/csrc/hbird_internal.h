@@ -77,7 +77,12 @@ struct hb_index {
     int xcd_balance = 0;                                 // 0 = automatic (big fp32 searches calibrate the shares from their own workgroups' durations), 1 = equal shares, 2 = as set
     const int* cl_stats_dev = nullptr;                   // {checks, spins, timeouts} of the last clustered launch (in `state`)
     // fp16 candidate mode (use_fp16): fp16 copies of the bank / query fragment tiles, candidate buffers
-    int fp16 = 0, dp16 = 0;
+    int fp16 = HB_FP16_AUTO, dp16 = 0;                    // 0 = the fp32 kernel, 1 = always, 2 = where it pays, HB_FP16_AUTO = the certified screen for big exact searches (hb_screen_choose)
+    int fp32_pinned = 0;                                 // sticky: the caller steered the fp32 kernel (variant, tuning, clusters, shares, search options): the automatic state stays on it
+    int screen_env_off = 0;                              // HBIRD_EXACT_SCREEN=0 when the index was created
+    int64_t f16_declined_cap = -1;                       // automatic state: no room for the fp16 tiles at this capacity (or the allocation failed): not asked again per search
+    int last_path = 0, last_reason = 0;                  // what served the last search of a caller (hb_last_search_path)
+    unsigned* stamp_keep = nullptr; int stamp_keep_blocks = 0;   // the candidate launch's stamps, kept aside while nested searches reuse `state`
     void* tiles16 = nullptr; int64_t f16_cap_rows = 0, f16_rows = 0;
     int* f16_flag = nullptr; int f16_overflow = 0;       // a finite bank value overflowed fp16: the fp32 kernel serves this bank
     // ... and, where memory allows, the bank once more as plain fp32 rows [row][rows32_rs] for the exact re-rank (hbird_knn_f16.hip)

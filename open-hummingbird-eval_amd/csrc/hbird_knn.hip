@@ -659,9 +659,27 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     // 69.3 / 10.6; 21,904 x 768: 4 k 1.43 / 1.09, 1 M 242.7 / 34.3; k = 90, 12,544 x 384: 16 k 1.74 / 2.04, 32 k 3.00 / 2.49, 1 M 70.4 / 13.8.
     // (Until round 4: at least 16,384 rows and rows x queries >= 2^27.)  Same results either way.
     const int esc = ix->esc_level;      // 0: a caller's search; 1: the second fp16 pass over its uncertified queries; 2: the fp32 search of what is left
-    const double kc_rel = std::min(256, std::max(64, (2 * k + 7) / 8 * 8)) / 64.0;
-    bool f16 = ix->fp16 != 0 && k <= 128 && !ceil &&      // (a later pass of a search with k > 256 runs behind a ceiling, which only the fp32 pool kernel knows)
-               (ix->fp16 == 1 || (ix->ntotal >= 4096 && (double)ix->ntotal * (double)nq * (double)ix->d >= 1.5e10 * kc_rel * kc_rel));
+    // Which searches take the candidate pass is hb_screen_choose's decision (hbird_calibrate.cpp, with CPU tests): states 1 / 2 by the rule above;
+    // the AUTOMATIC state (what a new index starts in) like state 2, but only for big searches -- from the 30,000 stages per workgroup at which the
+    // fp32 kernels stamp and calibrate (below) --, on an index whose fp32 kernel the caller has not steered, and where the fp16 copy fits.
+    hb_screen_in sin;
+    sin.setting = ix->fp16; sin.pinned = ix->fp32_pinned != 0; sin.env_off = ix->screen_env_off != 0; sin.k = k; sin.ceiling = ceil;
+    sin.rows = ix->ntotal; sin.nq = nq; sin.d = ix->d; sin.overflow = ix->f16_overflow != 0;
+    sin.stages_per_wg = (long long)((nq + HB_QT - 1) / HB_QT) * ((ix->ntotal + HB_BT - 1) / HB_BT) / std::max(1, ix->force_G > 0 ? ix->force_G : ix->num_cu) * ix->g8;
+    sin.have_copy = ix->tiles16 != nullptr && ix->f16_cap_rows == ix->cap_rows;
+    sin.declined = ix->f16_declined_cap == ix->cap_rows;
+    sin.bank_b = (uint64_t)ix->cap_rows * ix->dp * 4; sin.copy_b = (uint64_t)ix->cap_rows * ix->dp16 * 2;
+    const bool automatic = ix->fp16 == HB_FP16_AUTO;
+    int why = HB_WHY_EXPLICIT_FP32;
+    bool f16 = hb_screen_choose(sin, &why);
+    if (f16 && automatic && !sin.have_copy && nq > 0 && ix->ntotal > 0) {      // the copy has to be made: only where it leaves the device room
+        if (ix->tiles16) { HB_HIP(hipFree(ix->tiles16)); ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0; }      // (the bank grew: the old copy goes first)
+        size_t free_b = 0, total_b = 0;
+        HB_HIP(hipMemGetInfo(&free_b, &total_b));
+        sin.mem_known = true; sin.free_b = free_b; sin.total_b = total_b;
+        f16 = hb_screen_choose(sin, &why);
+        if (!f16) ix->f16_declined_cap = ix->cap_rows;
+    }
     // ADAPTIVE use (mode 2, round 6): on a bank whose neighbours sit closer together than fp16 can tell apart -- token worlds with little
     // noise: profiles/r06/final/fp16_cliff_*.json -- most certificates fail, and passes that certify nothing are pure overhead.  The index keeps
     // moving averages of the share of queries that failed the first certificate (r1) and of the share that reached the fp32 kernel (r12):
@@ -669,9 +687,9 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     // search walks the whole chain again, so a bank (or a query stream) that changes is noticed.  Same bits on every path.
     bool wide_first = false;
     int how16 = HB_F16_CHAIN;
-    if (f16 && esc == 0 && ix->fp16 == 2 && ix->fp16_escalation == 0) {       // (the policy itself: hbird_calibrate.cpp, with CPU tests)
+    if (f16 && esc == 0 && (ix->fp16 == 2 || automatic) && ix->fp16_escalation == 0) {       // (the policy itself: hbird_calibrate.cpp, with CPU tests)
         how16 = hb_f16_choose(ix->f16_adapt);
-        if (how16 == HB_F16_FP32) { f16 = false; ix->f16_skipped = 1; }
+        if (how16 == HB_F16_FP32) { f16 = false; ix->f16_skipped = 1; why = HB_WHY_ADAPTIVE; }
         else if (how16 == HB_F16_WIDE_FIRST) wide_first = true;
     }
     if (!f16 && esc == 0) { ix->last_fp16_fallbacks = ix->f16_skipped ? nq : 0; ix->last_fp16_escalated = 0; ix->f16_skipped = 0; }      // a plain fp32 search: nothing fell back (the counters are not left over from an earlier search)
@@ -683,19 +701,36 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
         if (!ix->f16_flag) { HB_HIP(hipMalloc((void**)&ix->f16_flag, 4)); HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s0)); }
         if (ix->f16_cap_rows != ix->cap_rows) {
             if (ix->tiles16) HB_HIP(hipFree(ix->tiles16));
-            ix->tiles16 = nullptr; ix->f16_rows = 0;
-            HB_HIP(hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2));
-            HB_HIP(hipMemsetAsync(ix->tiles16, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0));
-            ix->f16_cap_rows = ix->cap_rows;
+            ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0;
+            // states 1 / 2: the caller asked for the copy, no memory for it is the search's error.  Automatic: the copy only buys speed, so an
+            // allocation that fails all the same (the device filled up since hipMemGetInfo) is remembered for this capacity and the fp32 kernel answers
+            if (!automatic) HB_HIP(hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2));
+            else if (hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2) != hipSuccess) {
+                (void)hipGetLastError();
+                ix->tiles16 = nullptr; ix->f16_declined_cap = ix->cap_rows;
+                f16 = false; why = HB_WHY_MEMORY;
+                if (esc == 0) { ix->last_fp16_fallbacks = 0; ix->last_fp16_escalated = 0; }
+            }
+            if (ix->tiles16) {
+                HB_HIP(hipMemsetAsync(ix->tiles16, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0));
+                ix->f16_cap_rows = ix->cap_rows;
+            }
         }
-        if (ix->f16_rows < ix->ntotal) {
+        if (f16 && ix->f16_rows < ix->ntotal) {
             const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
             if (hb_launch_tiles_to_f16(ix->tiles, ix->g8, (_Float16*)ix->tiles16, ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
             ix->f16_rows = ix->ntotal;
             HB_HIP(hipMemcpyAsync(&ix->f16_overflow, ix->f16_flag, 4, hipMemcpyDeviceToHost, s0));
             HB_HIP(hipStreamSynchronize(s0));
         }
-        if (ix->f16_overflow) { f16 = false; if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; } }
+        if (f16 && ix->f16_overflow) {
+            f16 = false; why = HB_WHY_OVERFLOW;
+            if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; }
+            if (automatic) {      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
+                HB_HIP(hipFree(ix->tiles16));
+                ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0;
+            }
+        }
         // ... and the row-major fp32 copy for the re-rank (hbird_knn_f16.hip).  Automatic: by the bank's size (below; a 10 M x 768 bank:
         // 30.7 GB of tiles + 15.4 GB of fp16 tiles + 30.7 GB of rows, of 288)
         if (f16 && ix->rerank_copy != 2) {
@@ -734,6 +769,7 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     // fp16 mode: the fused kernel collects kc >= 2k candidates, the fp32 chain arithmetic re-ranks them
     // k' = 2k, at least 64 (rounded up to 8, not to 64 as until round 4: the candidate kernel's time is linear in k' -- 300,000 x 768, 21,904
     // queries: k' = 64 / 128 / 192 / 256 -> 12.95 / 15.85 / 20.7 / 25.0 ms -- so k = 33 paid for 128 candidates where it needs 66)
+    if (esc == 0) { ix->last_path = !f16 ? HB_PATH_FP32 : wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = why; }
     const int kc = f16 ? (esc == 1 || wide_first ? 256 : std::min(256, std::max(64, (2 * k + 7) / 8 * 8))) : k;     // (the second pass: the widest list the re-rank takes)
     // Small searches (few stages per workgroup) on the kernel with register-resident query fragments run on POOLS even for k <= 32:
     // phased, with the bisection cold start and the scan epilogue (hbird_knn_bd.hip <WIDE, COLD>) a pool takes a tile's survivors in one
@@ -868,8 +904,10 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     if (ensure_bytes(&ix->state, &ix->state_bytes, 2 * state_half + 2 * state_aux + floor_bytes + prog_bytes + stamp_bytes)) return -1;
 
     knn_args a;
-    a.wg_stamp = (ix->time_kernels || (balance && ix->xcd_balance == 0)) ? reinterpret_cast<unsigned*>(ix->state + 2 * state_half + 2 * state_aux + floor_bytes + prog_bytes) : nullptr;
-    ix->wg_stamp_dev = a.wg_stamp; ix->wg_stamp_blocks = sc.G;
+    // (a nested search of uncertified queries neither stamps nor counts as "the last launch": hb_index_kernel_clock / hb_index_wg_stamps describe the
+    // caller's search, as hb_index_schedule_info does)
+    a.wg_stamp = esc == 0 && (ix->time_kernels || (balance && ix->xcd_balance == 0)) ? reinterpret_cast<unsigned*>(ix->state + 2 * state_half + 2 * state_aux + floor_bytes + prog_bytes) : nullptr;
+    if (esc == 0) { ix->wg_stamp_dev = a.wg_stamp; ix->wg_stamp_blocks = sc.G; }
     if (a.wg_stamp) HB_HIP(hipMemsetAsync(a.wg_stamp, 0, stamp_bytes, s));   // a block that never stamps reads 0 / 0 (hb_stamps_summarise)
     a.bank_tiles = ix->tiles; a.binit = ix->binit; a.q_tiles = ix->q_tiles;
     a.ceil_s = ix->ceil_s_dev; a.ceil_i = ix->ceil_i_dev;
@@ -1023,6 +1061,17 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
             if (hb_launch_gather_rows(q_dev, nq, ix->d, d_rows, nf, d_q, s)) return -1;
             if (hb_launch_gather_rows(again16 ? flo : kth, nq, 1, d_rows, nf, d_seed, s)) return -1;
             if (hb_launch_rows_to_tiles(d_q, nf, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, s)) return -1;
+            // the nested search takes `state` for its own pools (and may move it): the candidate launch's stamps go aside first
+            if (esc == 0 && a.wg_stamp) {
+                if (ix->stamp_keep_blocks < sc.G) {
+                    if (ix->stamp_keep) HB_HIP(hipFree(ix->stamp_keep));
+                    ix->stamp_keep = nullptr; ix->stamp_keep_blocks = 0;
+                    HB_HIP(hipMalloc((void**)&ix->stamp_keep, stamp_bytes));
+                    ix->stamp_keep_blocks = sc.G;
+                }
+                HB_HIP(hipMemcpyAsync(ix->stamp_keep, a.wg_stamp, stamp_bytes, hipMemcpyDeviceToDevice, s));
+                ix->wg_stamp_dev = ix->stamp_keep;
+            }
             float* saved_aux = ix->q_aux;
             ix->q_aux = d_aux;                       // chain ||q||^2 of the re-searched queries (L2 distances)
             int rc = hb_launch_query_aux(d_q, nf, ix->d, d_aux, d_aux + nf, s);

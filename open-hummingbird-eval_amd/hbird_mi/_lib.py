@@ -70,6 +70,7 @@ SIGNATURES = {
     "hb_index_set_tuning": (c_int, [c_void_p, c_int, c_int]),
     "hb_index_set_fp16": (c_int, [c_void_p, c_int]),
     "hb_index_last_fp16_fallbacks": (c_int, [c_void_p, POINTER(c_int64)]),
+    "hb_last_search_path": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "hb_index_set_fp16_escalation": (c_int, [c_void_p, c_int]),
     "hb_index_last_fp16_escalated": (c_int, [c_void_p, POINTER(c_int64)]),
     "hb_schedule_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, POINTER(c_int64)]),
@@ -97,6 +98,8 @@ SIGNATURES = {
     "hb_calibration_state": (c_int, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
     "hb_calibration_feed": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_double), POINTER(c_int), c_int, c_double]),
     "hb_f16_adapt_replay": (c_int, [c_int, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int)]),
+    "hb_exact_screen_replay": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int, c_int, c_int,
+                                       c_uint64, c_uint64, c_uint64, c_uint64, POINTER(c_int)]),
     "hb_set_layout_form": (c_int, [c_int]),
     "hb_index_set_rerank_copy": (c_int, [c_void_p, c_int]),
     "hb_index_rerank_copy_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
@@ -125,7 +128,7 @@ def lib() -> ctypes.CDLL:
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
         for name, (res, args) in SIGNATURES.items():
-            if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name == "hb_f16_adapt_replay" or name == "hb_last_error"):
+            if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree
             fn.restype = res

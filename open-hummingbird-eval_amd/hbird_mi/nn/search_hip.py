@@ -268,8 +268,24 @@ class HipFlatIndex:
     def set_fp16(self, enable):
         """fp16 candidate pass + exact fp32 re-rank (GpuIndexFlatConfig.useFloat16 of the reference).  True / 1: always;
         2: only where it is faster than the fp32 kernel -- banks of at least 4,096 rows with rows x queries x D >= 1.5e10 x (k' / 64)^2 (same results
-        either way)."""
-        _lib.check(_lib.lib().hb_index_set_fp16(self._h, 2 if enable == 2 and enable is not True else int(bool(enable))))
+        either way).  False / 0: the fp32 kernel, no fp16 copy.  "auto": the state a new index starts in -- big exact searches take the certified
+        fp16 screen where it is known to pay and its copy fits (hb_index_set_fp16, include/hbird_hip.h; last_search_path() says what ran)."""
+        if isinstance(enable, str):
+            if enable != "auto":
+                raise ValueError(f"set_fp16: {enable!r} (False / True / 2 / 'auto')")
+            mode = 3                          # HB_FP16_AUTO
+        else:
+            mode = 2 if enable == 2 and enable is not True else int(bool(enable))
+        _lib.check(_lib.lib().hb_index_set_fp16(self._h, mode))
+
+    SEARCH_PATHS = ("fp32", "fp16_chain", "fp16_wide")
+    SEARCH_REASONS = ("explicit_fp32", "explicit_fp16", "auto", "k", "ceiling", "work", "small", "pinned", "env", "memory", "overflow", "adaptive")
+
+    def last_search_path(self) -> dict:
+        """What served the last search (hb_last_search_path): the fp32 kernel, the fp16 chain or one wide fp16 pass, and why (HB_WHY_*)."""
+        path, why = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.lib().hb_last_search_path(self._h, ctypes.byref(path), ctypes.byref(why)))
+        return {"path": self.SEARCH_PATHS[path.value], "reason": self.SEARCH_REASONS[why.value]}
 
     def last_fp16_fallbacks(self) -> int:
         n = ctypes.c_int64(0)
@@ -773,7 +789,8 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
 
     Keyword surface of search_faiss.py:7: `distance_measure` ("dot_product" | "l2" | "euclidean"),
     `idx_shard`, `use_fp16` (fp16 candidate pass + exact fp32 re-rank: same answers as fp32, several times
-    faster), `gpu_ids`.
+    faster), `gpu_ids`.  With `use_fp16=False` the index stays in its automatic state: big exact searches take the same certified screen
+    where it pays and its fp16 copy (half the bank again) fits; `exact_screen=False` holds it to fp32 kernels and fp32 memory only.
     Unknown keywords are swallowed like the reference's **kwargs.  Like the Faiss class it does not call
     the base constructor (search_faiss.py:7-32) and copies the bank to the GPU(s) at construction (78-81).
 
@@ -793,6 +810,7 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
         self.distance_measure = distance_measure.lower()
         self.idx_shard = idx_shard
         self.use_fp16 = use_fp16
+        self.exact_screen = bool(kwargs.pop("exact_screen", True))     # use_fp16=False: the index's automatic state (True) or the fp32 kernel only (False)
         self.rerank_copy = int(kwargs.pop("rerank_copy", 0))     # use_fp16 only: the re-rank's row-major copy of the bank (0 automatic, 1 always, 2 never)
         self.embed_d = feature_memory.size(1)
 
@@ -833,7 +851,7 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
         else:
             out = [HipFlatIndex(self.embed_d, _METRICS[self.distance_measure], self.local_gpus[0])]
         for index in out:
-            index.set_fp16(2 if self.use_fp16 else 0)                                   # search_faiss.py:40; only where it pays
+            index.set_fp16(2 if self.use_fp16 else "auto" if self.exact_screen else 0)  # search_faiss.py:40; only where it pays
             index.set_rerank_copy(self.rerank_copy)
         return out
 
