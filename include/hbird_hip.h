@@ -14,6 +14,10 @@
  * with RCCL, one process with several GPUs uses an hb_multi_t, declared below.  Calls on one handle must be serialised by the caller; work is
  * enqueued on the handle's stream (hb_index_set_stream) and host-pointer variants synchronise it.
  * `*_on_device` = 1 means the pointer is device memory of the handle's GPU, 0 means host memory.
+ *
+ * Shapes are checked before anything is launched or allocated: a negative count (rows, queries, images, ids), a width, class count or
+ * patch count that is not positive, and -- in a call that has work to do -- k < 1, a metric other than HB_METRIC_IP / HB_METRIC_L2 or a
+ * NULL array fail with a message that names the entry and the argument.  A call with a count of 0 is empty work and returns 0.
  */
 #ifndef HBIRD_HIP_H
 #define HBIRD_HIP_H
@@ -86,7 +90,9 @@ int hb_index_aggregate(hb_index_t* ix, const float* q, int64_t nq, const int64_t
  * computed identically everywhere; only the order of the fp32 sum differs from hb_index_aggregate (within 1e-6).  Device pointers. */
 int hb_index_aggregate_partial(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,
                                int64_t id_base, float beta, const float* norms_all, int64_t n_all, float* out_partial);
-/* feature_memory.index_select(0, idx) (hbird_eval.py:632) for return_knn_details; out[n, d]. */
+/* feature_memory.index_select(0, idx) (hbird_eval.py:632) for return_knn_details; out[n, d].  ids are global: row id - id_base of
+ * this index.  An id outside [id_base, id_base + ntotal) -- a missing neighbour (-1), another shard's row -- gives a zero row, as
+ * hb_gather_rows and hb_index_gather_labels do; nothing outside the bank is read. */
 int hb_index_reconstruct(hb_index_t* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out,
                          int io_on_device);
 /* label_memory.index_select(0, idx) (hbird_eval.py:633); out[n, c]. */
@@ -114,7 +120,11 @@ int hb_index_set_label_count_table(hb_index_t* ix, const uint16_t* counts, const
 int hb_index_set_score_output(hb_index_t* ix, int enable);
 int hb_index_distances_from_scores(hb_index_t* ix, const float* q, int64_t nq, int k, float* dist_inout);
 /* k-way merge of per-shard results laid out [parts][nq][k] (faiss.IndexShards' merge, search_faiss.py:
- * 53-63; here fed by an RCCL all-gather).  Device pointers. */
+ * 53-63; here fed by an RCCL all-gather).  Device pointers.  metric 0: out_dist holds scores, larger is better; metric 1:
+ * distances, smaller is better.  Order of the output: present entries (id >= 0) before missing ones (id < 0, whatever score they
+ * carry; they come out as id -1 with -inf / +inf), then the better score, then the lower id, then the lower part.  An id that
+ * appears in two parts is NOT deduplicated: both entries are kept, in part order (shards hold disjoint rows, so a search never
+ * produces one).  parts * k is bounded by the kernel's LDS (about 4,900 candidates); beyond it the call fails and writes nothing. */
 int hb_merge_topk(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
                   int64_t* out_idx, float* out_dist, void* hip_stream);
 /* The same merge on PACKED per-shard lists, so that one rank's result travels in ONE all-gather message: a packed

@@ -165,7 +165,11 @@ __global__ __launch_bounds__(256) void patch_select_kernel(const float* __restri
 
 extern "C" int hb_patch_scores(const float* label, int64_t B, int SS, int C, float* scores, int* nonempty, int* nz_count,
                                void* stream) {
+    if (B < 0) return hb_fail("hb_patch_scores: B is negative");
+    if (SS <= 0) return hb_fail("hb_patch_scores: SS must be positive");
+    if (C <= 0) return hb_fail("hb_patch_scores: C must be positive");
     if (B == 0) return 0;
+    if (!label || !scores || !nonempty || !nz_count) return hb_fail("hb_patch_scores: NULL pointer");
     if (B > 65535) return hb_fail("hb_patch_scores: more than 65,535 images per call");
     if ((size_t)C * 4 > 60000) return hb_fail("hb_patch_scores: too many classes");
     hipStream_t s = (hipStream_t)stream;
@@ -199,7 +203,11 @@ extern "C" int hb_patch_scores(const float* label, int64_t B, int SS, int C, flo
 
 extern "C" int hb_patch_select(const float* scores, const int* nonempty, const float* r, const int64_t* r_off, int64_t B,
                                int SS, int K, int64_t* out_idx, float* out_scores, void* stream) {
+    if (B < 0) return hb_fail("hb_patch_select: B is negative");
+    if (SS <= 0) return hb_fail("hb_patch_select: SS must be positive");
+    if (K < 0) return hb_fail("hb_patch_select: K is negative");
     if (B == 0) return 0;
+    if (!scores || !nonempty || !r_off || (K > 0 && !out_idx)) return hb_fail("hb_patch_select: NULL pointer");
     if (K > SS) return hb_fail("hb_patch_select: K exceeds the number of patches per image");
     if ((size_t)SS * 4 > 60000) return hb_fail("hb_patch_select: too many patches per image");
     if (B > 65535) return hb_fail("hb_patch_select: more than 65,535 images per call");

@@ -570,7 +570,9 @@ extern "C" int hb_index_search_aggregate(hb_index_t* ix, const float* q, int64_t
 extern "C" int hb_index_aggregate(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist,
                                   int k, int64_t id_base, float beta, float* out_label_hat, int io_on_device) {
     if (!ix) return hb_fail("hb_index_aggregate: NULL index handle");
+    if (nq < 0) return hb_fail("hb_index_aggregate: nq is negative");
     if (nq == 0) return 0;
+    if (k < 1) return hb_fail("hb_index_aggregate: k must be positive");
     if (!io_on_device) return hb_fail("hb_index_aggregate: host pointers are not supported, pass device memory");
     if (!(beta > 0.f)) return hb_fail("hb_index_aggregate: beta must be positive");
     hb_range range("hbird:aggregate");
@@ -584,7 +586,9 @@ extern "C" int hb_index_aggregate(hb_index_t* ix, const float* q, int64_t nq, co
 extern "C" int hb_index_aggregate_partial(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,
                                           int64_t id_base, float beta, const float* norms_all, int64_t n_all, float* out_partial) {
     if (!ix) return hb_fail("hb_index_aggregate_partial: NULL index handle");
+    if (nq < 0) return hb_fail("hb_index_aggregate_partial: nq is negative");
     if (nq == 0) return 0;
+    if (k < 1) return hb_fail("hb_index_aggregate_partial: k must be positive");
     if (!q || !idx || !dist || !norms_all || !out_partial) return hb_fail("hb_index_aggregate_partial: NULL pointer");
     if (!(beta > 0.f)) return hb_fail("hb_index_aggregate_partial: beta must be positive");
     hb_range range("hbird:aggregate_partial");
@@ -601,7 +605,10 @@ extern "C" int hb_index_aggregate_partial(hb_index_t* ix, const float* q, int64_
 
 static int gather_impl(hb_index* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out, int io_on_device,
                        bool labels) {
+    const char* who = labels ? "hb_index_gather_labels" : "hb_index_reconstruct";
+    if (n < 0) return hb_fail(std::string(who) + ": n is negative");
     if (n == 0) return 0;
+    if (!ids || !out) return hb_fail(std::string(who) + ": ids / out is NULL");
     HB_HIP(hipSetDevice(ix->device));
     const int width = labels ? ix->c : ix->d;
     if (labels && !ix->labels && !ix->labels16) return hb_fail("hb_index_gather_labels: no labels stored");
@@ -621,7 +628,7 @@ static int gather_impl(hb_index* ix, const int64_t* ids, int64_t n, int64_t id_b
         if (ix->label_P ? hb_launch_gather_label_counts(ix->labels16, ix->nlabels, width, ix->lab_stride(), ix->label_P, d_ids, n, d_out, ix->stream)
                         : hb_launch_gather_rows(ix->labels, ix->nlabels, width, d_ids, n, d_out, ix->stream)) return -1;
     } else {
-        if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->d, d_ids, n, id_base, d_out, ix->stream)) return -1;
+        if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->d, d_ids, n, id_base, ix->ntotal, d_out, ix->stream)) return -1;
     }
     if (!io_on_device) {
         HB_HIP(hipMemcpyAsync(out, d_out, (size_t)n * width * 4, hipMemcpyDeviceToHost, ix->stream));
@@ -691,7 +698,9 @@ extern "C" int hb_index_set_score_output(hb_index_t* ix, int enable) {
 
 extern "C" int hb_index_distances_from_scores(hb_index_t* ix, const float* q, int64_t nq, int k, float* dist_inout) {
     if (!ix) return hb_fail("hb_index_distances_from_scores: NULL index handle");
+    if (nq < 0) return hb_fail("hb_index_distances_from_scores: nq is negative");
     if (nq == 0 || ix->metric != 1) return 0;            // inner product: the score is the distance
+    if (k < 1) return hb_fail("hb_index_distances_from_scores: k must be positive");
     if (!q || !dist_inout) return hb_fail("hb_index_distances_from_scores: NULL pointer");
     HB_HIP(hipSetDevice(ix->device));
     if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
@@ -703,6 +712,9 @@ extern "C" int hb_merge_topk(const float* dist_parts, const int64_t* idx_parts, 
                              int64_t* out_idx, float* out_dist, void* stream) {
     hb_range range("hbird:merge_topk");
     if (parts < 1 || k < 1) return hb_fail("hb_merge_topk: bad shape");
+    if (nq < 0) return hb_fail("hb_merge_topk: nq is negative");
+    if (nq == 0) return 0;
+    if (metric != HB_METRIC_IP && metric != HB_METRIC_L2) return hb_fail("hb_merge_topk: metric must be 0 (scores, larger is better) or 1 (distances)");
     if (nq > 0 && (!dist_parts || !idx_parts || !out_idx || !out_dist)) return hb_fail("hb_merge_topk: NULL pointer");
     return hb_launch_merge_parts(dist_parts, idx_parts, parts, nq, k, metric, nq * (int64_t)k, nq * (int64_t)k, out_idx, out_dist,
                                  (hipStream_t)stream);
@@ -717,7 +729,9 @@ extern "C" int hb_merge_topk_packed(const void* packed_parts, int64_t part_bytes
                                     int64_t* out_idx, float* out_dist, void* stream) {
     hb_range range("hbird:merge_topk");
     if (parts < 1 || k < 1) return hb_fail("hb_merge_topk_packed: bad shape");
+    if (nq < 0) return hb_fail("hb_merge_topk_packed: nq is negative");
     if (nq == 0) return 0;
+    if (metric != HB_METRIC_IP && metric != HB_METRIC_L2) return hb_fail("hb_merge_topk_packed: metric must be 0 (scores, larger is better) or 1 (distances)");
     if (!packed_parts || !out_idx || !out_dist) return hb_fail("hb_merge_topk_packed: NULL pointer");
     if (part_bytes < nq * (int64_t)k * 12 || part_bytes % 8 != 0)
         return hb_fail("hb_merge_topk_packed: part_bytes must be a multiple of 8 and hold nq*k ids (int64) + nq*k scores (fp32)");
@@ -727,15 +741,26 @@ extern "C" int hb_merge_topk_packed(const void* packed_parts, int64_t part_bytes
 }
 
 extern "C" int hb_normalize_rows(const float* x, int64_t n, int d, float* out, void* stream) {
+    if (n < 0) return hb_fail("hb_normalize_rows: n is negative");
+    if (d <= 0) return hb_fail("hb_normalize_rows: d must be positive");
+    if (n > 0 && (!x || !out)) return hb_fail("hb_normalize_rows: x / out is NULL");
     return hb_launch_normalize_rows(x, n, d, out, (hipStream_t)stream);
 }
 extern "C" int hb_patch_label_hist(const int64_t* y, int64_t B, int H, int W, int ps, int C, int map255, float* out,
                                    void* stream) {
+    if (B < 0) return hb_fail("hb_patch_label_hist: B is negative");
+    if (H < 0 || W < 0) return hb_fail("hb_patch_label_hist: H / W is negative");
+    if (C <= 0) return hb_fail("hb_patch_label_hist: C must be positive");
+    if (B > 0 && H > 0 && W > 0 && (!y || !out)) return hb_fail("hb_patch_label_hist: y / out is NULL");
     hb_range range("hbird:patch_label_hist");
     return hb_launch_patch_label_hist(y, B, H, W, ps, C, map255, out, (hipStream_t)stream);
 }
 extern "C" int hb_gather_rows(const float* src, int64_t src_rows, int width, const int64_t* ids, int64_t n, float* out,
                               void* stream) {
+    if (n < 0) return hb_fail("hb_gather_rows: n is negative");
+    if (src_rows < 0) return hb_fail("hb_gather_rows: src_rows is negative");
+    if (width <= 0) return hb_fail("hb_gather_rows: width must be positive");
+    if (n > 0 && (!ids || !out || (src_rows > 0 && !src))) return hb_fail("hb_gather_rows: src / ids / out is NULL");
     return hb_launch_gather_rows(src, src_rows, width, ids, n, out, (hipStream_t)stream);
 }
 extern "C" int hb_upsample_argmax(const float* label_hat, int64_t B, int S, int C, int h, int w, int64_t* out,

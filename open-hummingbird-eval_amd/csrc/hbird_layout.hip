@@ -40,13 +40,29 @@ __global__ __launch_bounds__(256) void rows_to_tiles_kernel(const float* __restr
         const int i = tid >> 3, sub = tid & 7;
         const int64_t r = r_base + i;
         double acc = 0.0;
-        if (r < n_valid) {
+        if ((NORMALIZE || IS_BANK) && r < n_valid) {      // (queries need no norm here: query_aux_kernel computes theirs)
             const float* row = src + r * (int64_t)d;
             if ((d & 3) == 0) {
-                const float4* row4 = reinterpret_cast<const float4*>(row);
-                for (int k4 = sub; k4 < (d >> 2); k4 += 8) {
-                    float4 v = row4[k4];
-                    acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+                // 16-byte loads only from a 16-byte aligned row (d % 4 == 0: every row shares the source's alignment).  An unaligned source
+                // -- a tensor view that starts an odd number of floats into its allocation -- brings the same four values by 4-byte loads
+                // and adds them in the same order, so the bits of the norm do not depend on the pointer.  The 4-byte loads are VOLATILE:
+                // the compiler otherwise merges four adjacent loads back into one global_load_dwordx4 (it takes an under-aligned 16-byte
+                // global load for legal on this target) and folds the two arms into one; tests/test_bank_paths_cpu.py reads the
+                // disassembly and fails when the unaligned arm holds anything but single-dword loads.
+                const bool al16 = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+                if (al16) {
+                    const float4* row4 = reinterpret_cast<const float4*>(row);
+                    for (int k4 = sub; k4 < (d >> 2); k4 += 8) {
+                        const float4 v = row4[k4];
+                        acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+                    }
+                } else {
+                    const volatile float* vrow = row;
+                    for (int k4 = sub; k4 < (d >> 2); k4 += 8) {
+                        float4 v;
+                        v.x = vrow[4 * k4]; v.y = vrow[4 * k4 + 1]; v.z = vrow[4 * k4 + 2]; v.w = vrow[4 * k4 + 3];
+                        acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+                    }
                 }
             } else {
                 for (int k = sub; k < d; k += 8) { float v = row[k]; acc += (double)v * v; }
@@ -311,17 +327,19 @@ int hb_launch_query_aux(const float* q, int64_t nq, int d, float* qn2, float* qn
 }
 
 // Gather bank rows back to row-major (return_knn_details: key_features of hbird_eval.py:632,635).
-// ids < 0 (missing neighbour) produce zero rows.  One wave per output row.
+// ids < 0 (missing neighbour) and ids outside [id_base, id_base + ntotal) (another shard's rows, a wrong id_base) produce zero rows,
+// as gather_rows_kernel and gather_label_counts_kernel do.  One wave per output row.
 __global__ __launch_bounds__(256) void tiles_to_rows_kernel(const float* __restrict__ tiles, int g8, int d,
                                                             const int64_t* __restrict__ ids, int64_t n,
-                                                            int64_t id_base, float* __restrict__ out) {
+                                                            int64_t id_base, int64_t ntotal, float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t o = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (o >= n) return;
     const int64_t gid = ids[o];
     float* dst = out + o * (int64_t)d;
-    if (gid < 0) { for (int k = lane; k < d; k += 64) dst[k] = 0.0f; return; }
-    const int64_t r = gid - id_base;
+    // (the difference in unsigned arithmetic: a very negative id_base must not overflow it)
+    if (gid < 0 || gid < id_base || (uint64_t)gid - (uint64_t)id_base >= (uint64_t)ntotal) { for (int k = lane; k < d; k += 64) dst[k] = 0.0f; return; }
+    const int64_t r = (int64_t)((uint64_t)gid - (uint64_t)id_base);
     const float* base = tiles + ((r >> 5) * (int64_t)g8) * HB_BLK;
     const int i = (int)(r & 31);
     for (int k = lane; k < d; k += 64) {
@@ -330,10 +348,10 @@ __global__ __launch_bounds__(256) void tiles_to_rows_kernel(const float* __restr
     }
 }
 
-int hb_launch_tiles_to_rows(const float* tiles, int g8, int d, const int64_t* ids, int64_t n, int64_t id_base,
+int hb_launch_tiles_to_rows(const float* tiles, int g8, int d, const int64_t* ids, int64_t n, int64_t id_base, int64_t ntotal,
                             float* out, hipStream_t s) {
     if (n == 0) return 0;
-    tiles_to_rows_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(tiles, g8, d, ids, n, id_base, out);
+    tiles_to_rows_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(tiles, g8, d, ids, n, id_base, ntotal, out);
     HB_HIP(hipGetLastError());
     return 0;
 }

@@ -68,6 +68,18 @@ def patch_scores(label: torch.Tensor):
 def patch_select(scores: torch.Tensor, nonempty: torch.Tensor, r: torch.Tensor, r_off: torch.Tensor, K: int,
                  want_scores: bool = False):
     """noise multiply + K smallest per image, ascending (reference hbird_eval.py:497-511)."""
+    # the C entry takes bare pointers: a tensor of another dtype would be read as noise, so dtypes and shapes are checked here (and
+    # before the device check, so that the refusal does not need a GPU)
+    for name, t, dt in (("scores", scores, torch.float32), ("nonempty", nonempty, torch.int32), ("r", r, torch.float32),
+                        ("r_off", r_off, torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"patch_select: {name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+    if scores.dim() != 2 or tuple(nonempty.shape) != tuple(scores.shape):
+        raise ValueError(f"patch_select: scores and nonempty must both be [B, SS], got {tuple(scores.shape)} and {tuple(nonempty.shape)}")
+    if tuple(r_off.shape) != (scores.shape[0],):
+        raise ValueError(f"patch_select: r_off must be [B] = [{scores.shape[0]}], got {tuple(r_off.shape)}")
+    if r.dim() != 1:
+        raise ValueError(f"patch_select: r must be one-dimensional, got {tuple(r.shape)}")
     _need_cuda(scores, nonempty, r, r_off)
     B, SS = scores.shape
     out = torch.empty((B, K), dtype=torch.int64, device=scores.device)
