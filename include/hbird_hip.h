@@ -33,7 +33,10 @@ typedef struct hb_index hb_index_t;
 #define HB_MAX_K 2048  /* neighbours per query of a search -- faiss-gpu's own limit (the reference forwards any k, search_faiss.py:84-85; its default
                         * is 30).  k <= 32 keeps the lists in LDS, k <= 256 is one pass over candidate pools, beyond that ceil(k / 256) passes,
                         * each behind the last neighbour of the one before: a search of k = 1024 costs four searches of k = 256. */
-#define HB_MAX_K_AGGREGATE 256   /* ... of the fused search + label aggregation (K5 keeps a query's k weights in LDS) and of sharded merges */
+#define HB_MAX_K_AGGREGATE 256   /* ... of the LDS-resident entries: hb_index_search_aggregate / hb_index_aggregate / hb_index_aggregate_partial keep a
+                                  * query's k weights in a fixed 256-entry LDS array, hb_merge_topk stages parts * k candidates in LDS.  Beyond it the
+                                  * hb_bigk_* family below serves every k up to HB_MAX_K (same results; for k <= 256 the same bits). */
+#define HB_BIGK_MAX_PARTS 64     /* lists per query that hb_bigk_merge_topk merges */
 
 const char* hb_last_error(void);
 /* faiss.get_num_gpus(), search_faiss.py:14 */
@@ -124,7 +127,8 @@ int hb_index_distances_from_scores(hb_index_t* ix, const float* q, int64_t nq, i
  * distances, smaller is better.  Order of the output: present entries (id >= 0) before missing ones (id < 0, whatever score they
  * carry; they come out as id -1 with -inf / +inf), then the better score, then the lower id, then the lower part.  An id that
  * appears in two parts is NOT deduplicated: both entries are kept, in part order (shards hold disjoint rows, so a search never
- * produces one).  parts * k is bounded by the kernel's LDS (about 4,900 candidates); beyond it the call fails and writes nothing. */
+ * produces one).  parts * k is bounded by the kernel's LDS (about 4,900 candidates); beyond it the call fails and writes nothing
+ * (hb_bigk_merge_topk below has no such bound, for lists that are sorted). */
 int hb_merge_topk(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
                   int64_t* out_idx, float* out_dist, void* hip_stream);
 /* The same merge on PACKED per-shard lists, so that one rank's result travels in ONE all-gather message: a packed
@@ -134,6 +138,28 @@ int hb_merge_topk(const float* dist_parts, const int64_t* idx_parts, int parts, 
 int64_t hb_packed_list_bytes(int64_t nq, int k);
 int hb_merge_topk_packed(const void* packed_parts, int64_t part_bytes, int parts, int64_t nq, int k, int metric,
                          int64_t* out_idx, float* out_dist, void* hip_stream);
+
+/* ---- k beyond 256: label aggregation and merges for 1 <= k <= HB_MAX_K ---------------------------------------
+ * The three K5 entries take the argument lists of hb_index_search_aggregate / hb_index_aggregate / hb_index_aggregate_partial and
+ * compute the same thing in the same arithmetic order (for k <= 256 the output bits are equal); a query's weights live in k * 8 bytes
+ * of dynamic LDS instead of a fixed array.  hb_bigk_aggregate and hb_bigk_aggregate_partial take device pointers.  Errors as for the
+ * old entries (hb_last_error): NULL handle / pointer, k outside [1, 2048], beta <= 0, label rows missing. */
+int hb_bigk_search_aggregate(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta,
+                             float* out_label_hat, int64_t* out_idx_opt, float* out_dist_opt, int io_on_device);
+int hb_bigk_aggregate(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,
+                      int64_t id_base, float beta, float* out_label_hat, int io_on_device);
+int hb_bigk_aggregate_partial(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,
+                              int64_t id_base, float beta, const float* norms_all, int64_t n_all, float* out_partial);
+/* hb_merge_topk / hb_merge_topk_packed without the bound on parts * k: parts <= HB_BIGK_MAX_PARTS, k <= HB_MAX_K, same arguments, same
+ * key (present before missing, better score, lower id, lower part), same output (missing entries last as id -1 with -inf / +inf).
+ * PRECONDITION: every one of the parts * nq input lists is already sorted best-first by (score descending -- metric 1: distance
+ * ascending --, id ascending) and holds its missing entries (id < 0) only at its tail: what a search leaves (with score output, what
+ * hb_index_set_score_output leaves).  Each element finds its output rank by binary searches in the other parts' lists, nothing is
+ * staged.  Lists that break the precondition give an unspecified selection (never a write outside the outputs). */
+int hb_bigk_merge_topk(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
+                       int64_t* out_idx, float* out_dist, void* hip_stream);
+int hb_bigk_merge_topk_packed(const void* packed_parts, int64_t part_bytes, int parts, int64_t nq, int k, int metric,
+                              int64_t* out_idx, float* out_dist, void* hip_stream);
 
 /* ---- several GPUs behind one handle ------------------------------------------------------------------ */
 /* faiss.index_cpu_to_gpu_multiple_py(resources, index_cpu, gpus=gpu_ids) with co.shard = idx_shard, search_faiss.py:50-76:
@@ -153,6 +179,7 @@ int hb_multi_add(hb_multi_t* m, const float* x, int64_t n, int normalize);
 int64_t hb_multi_ntotal(const hb_multi_t* m);
 int hb_multi_shard_rows(const hb_multi_t* m, int64_t* rows, int n);
 int hb_multi_set_fp16(hb_multi_t* m, int enable);
+/* 1 <= k <= HB_MAX_K, shards and replicas alike (the shards' lists are merged on the host). */
 int hb_multi_search(hb_multi_t* m, const float* q, int64_t nq, int k, int64_t* out_idx, float* out_dist);
 
 /* ---- bank build (device pointers, enqueued on hip_stream) -------------------------------------- */

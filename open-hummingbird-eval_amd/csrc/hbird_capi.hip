@@ -495,10 +495,11 @@ extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t 
 static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta, float* out_lab,
-                       int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate) {
+                       int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate, bool bigk = false) {
+    // bigk: the aggregation is hbird_bigk.hip's K5 (hb_bigk_search_aggregate), whose k goes as far as the search's
     if (nq < 0) return hb_fail("hb_index_search: negative query count");
     if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search: k must be in [1, " + std::to_string(HB_MAX_K) + "] (faiss-gpu's own limit)");
-    if (aggregate && k > HB_MAX_K_AGGREGATE)
+    if (aggregate && !bigk && k > HB_MAX_K_AGGREGATE)
         return hb_fail("hb_index_search_aggregate: k must be in [1, " + std::to_string(HB_MAX_K_AGGREGATE) + "] (plain searches take k up to " + std::to_string(HB_MAX_K) + ")");
     if (nq == 0) return 0;
     if (!q) return hb_fail("hb_index_search: q is NULL");
@@ -538,7 +539,7 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     }
     if (aggregate) {
         hb_range r("hbird:aggregate");
-        if (hb_launch_aggregate(ix, ix->q_aux + nq, d_idx, d_dist, nq, k, id_base, beta, d_lab, ix->stream)) return -1;
+        if ((bigk ? hb_launch_aggregate_bigk : hb_launch_aggregate)(ix, ix->q_aux + nq, d_idx, d_dist, nq, k, id_base, beta, d_lab, ix->stream, nullptr, 0)) return -1;
     }
     if (!io_on_device) {
         if (out_idx) HB_HIP(hipMemcpyAsync(out_idx, d_idx, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ix->stream));
@@ -601,6 +602,88 @@ extern "C" int hb_index_aggregate_partial(hb_index_t* ix, const float* q, int64_
     if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
     if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
     return hb_launch_aggregate(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_partial, ix->stream, norms_all, n_all);
+}
+
+// ---- k beyond 256: the hb_bigk_* family (hbird_bigk.hip).  Argument lists of their hb_index_* / hb_merge_* counterparts, 1 <= k <= HB_MAX_K.
+static std::string bigk_range(const char* who) { return std::string(who) + ": k must be in [1, " + std::to_string(HB_MAX_K) + "]"; }
+
+extern "C" int hb_bigk_search_aggregate(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta,
+                                        float* out_label_hat, int64_t* out_idx_opt, float* out_dist_opt, int io_on_device) {
+    if (!ix) return hb_fail("hb_bigk_search_aggregate: NULL index handle");
+    if (nq > 0 && !out_label_hat) return hb_fail("hb_bigk_search_aggregate: out_label_hat is NULL");
+    if (k < 1 || k > HB_MAX_K) return hb_fail(bigk_range("hb_bigk_search_aggregate"));
+    if (!(beta > 0.f)) return hb_fail("hb_bigk_search_aggregate: beta must be positive");
+    if (!ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal)) return hb_fail("hb_bigk_search_aggregate: label rows missing (hb_index_add_labels)");
+    if (hb_labels_checked(ix)) return -1;
+    return search_impl(ix, q, nq, k, id_base, beta, out_label_hat, out_idx_opt, out_dist_opt, io_on_device, true, true);
+}
+
+extern "C" int hb_bigk_aggregate(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist,
+                                 int k, int64_t id_base, float beta, float* out_label_hat, int io_on_device) {
+    if (!ix) return hb_fail("hb_bigk_aggregate: NULL index handle");
+    if (nq < 0) return hb_fail("hb_bigk_aggregate: nq is negative");
+    if (k < 1 || k > HB_MAX_K) return hb_fail(bigk_range("hb_bigk_aggregate"));
+    if (!(beta > 0.f)) return hb_fail("hb_bigk_aggregate: beta must be positive");
+    if (nq == 0) return 0;
+    if (!q || !idx || !dist || !out_label_hat) return hb_fail("hb_bigk_aggregate: NULL pointer");
+    if (!io_on_device) return hb_fail("hb_bigk_aggregate: host pointers are not supported, pass device memory");
+    hb_range range("hbird:aggregate_bigk");
+    HB_HIP(hipSetDevice(ix->device));
+    if (hb_labels_checked(ix)) return -1;
+    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
+    return hb_launch_aggregate_bigk(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_label_hat, ix->stream);
+}
+
+extern "C" int hb_bigk_aggregate_partial(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,
+                                         int64_t id_base, float beta, const float* norms_all, int64_t n_all, float* out_partial) {
+    if (!ix) return hb_fail("hb_bigk_aggregate_partial: NULL index handle");
+    if (nq < 0) return hb_fail("hb_bigk_aggregate_partial: nq is negative");
+    if (k < 1 || k > HB_MAX_K) return hb_fail(bigk_range("hb_bigk_aggregate_partial"));
+    if (!(beta > 0.f)) return hb_fail("hb_bigk_aggregate_partial: beta must be positive");
+    if (nq == 0) return 0;
+    if (!q || !idx || !dist || !norms_all || !out_partial) return hb_fail("hb_bigk_aggregate_partial: NULL pointer");
+    hb_range range("hbird:aggregate_partial_bigk");
+    HB_HIP(hipSetDevice(ix->device));
+    if (hb_labels_checked(ix)) return -1;
+    if (ix->ntotal == 0) {   // an empty shard owns no neighbour: its partial sums are zero
+        HB_HIP(hipMemsetAsync(out_partial, 0, (size_t)nq * ix->c * 4, ix->stream));
+        return 0;
+    }
+    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
+    return hb_launch_aggregate_bigk(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_partial, ix->stream, norms_all, n_all);
+}
+
+static int bigk_merge_checks(const char* who, int parts, int64_t nq, int k, int metric) {
+    if (parts < 1 || parts > HB_BIGK_MAX_PARTS) return hb_fail(std::string(who) + ": parts must be in [1, " + std::to_string(HB_BIGK_MAX_PARTS) + "]");
+    if (k < 1 || k > HB_MAX_K) return hb_fail(bigk_range(who));
+    if (nq < 0) return hb_fail(std::string(who) + ": nq is negative");
+    if (metric != HB_METRIC_IP && metric != HB_METRIC_L2) return hb_fail(std::string(who) + ": metric must be 0 (scores, larger is better) or 1 (distances)");
+    return 0;
+}
+
+extern "C" int hb_bigk_merge_topk(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
+                                  int64_t* out_idx, float* out_dist, void* stream) {
+    hb_range range("hbird:merge_topk_bigk");
+    if (bigk_merge_checks("hb_bigk_merge_topk", parts, nq, k, metric)) return -1;
+    if (nq == 0) return 0;
+    if (!dist_parts || !idx_parts || !out_idx || !out_dist) return hb_fail("hb_bigk_merge_topk: NULL pointer");
+    return hb_launch_merge_sorted_parts(dist_parts, idx_parts, parts, nq, k, metric, nq * (int64_t)k, nq * (int64_t)k, out_idx, out_dist,
+                                        (hipStream_t)stream);
+}
+
+extern "C" int hb_bigk_merge_topk_packed(const void* packed_parts, int64_t part_bytes, int parts, int64_t nq, int k, int metric,
+                                         int64_t* out_idx, float* out_dist, void* stream) {
+    hb_range range("hbird:merge_topk_bigk");
+    if (bigk_merge_checks("hb_bigk_merge_topk_packed", parts, nq, k, metric)) return -1;
+    if (nq == 0) return 0;
+    if (!packed_parts || !out_idx || !out_dist) return hb_fail("hb_bigk_merge_topk_packed: NULL pointer");
+    if (part_bytes < nq * (int64_t)k * 12 || part_bytes % 8 != 0)
+        return hb_fail("hb_bigk_merge_topk_packed: part_bytes must be a multiple of 8 and hold nq*k ids (int64) + nq*k scores (fp32)");
+    const char* base = reinterpret_cast<const char*>(packed_parts);
+    return hb_launch_merge_sorted_parts(reinterpret_cast<const float*>(base + nq * (int64_t)k * 8), reinterpret_cast<const int64_t*>(base),
+                                        parts, nq, k, metric, part_bytes / 4, part_bytes / 8, out_idx, out_dist, (hipStream_t)stream);
 }
 
 static int gather_impl(hb_index* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out, int io_on_device,

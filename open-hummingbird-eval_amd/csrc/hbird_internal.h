@@ -161,6 +161,11 @@ int hb_launch_aggregate(const hb_index* ix, const float* qnorm, const int64_t* i
                         int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);
 int hb_launch_merge_parts(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
                           int64_t dist_stride, int64_t idx_stride, int64_t* out_idx, float* out_dist, hipStream_t s);
+// k beyond 256 (hbird_bigk.hip): K5 for 1 <= k <= HB_MAX_K with hb_launch_aggregate's tables and bits, and the merge of SORTED per-shard lists
+int hb_launch_aggregate_bigk(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq,
+                             int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);
+int hb_launch_merge_sorted_parts(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
+                                 int64_t dist_stride, int64_t idx_stride, int64_t* out_idx, float* out_dist, hipStream_t s);
 int hb_launch_patch_label_hist(const int64_t* y, int64_t B, int H, int W, int ps, int C, int map255, float* out,
                                hipStream_t s);
 int hb_launch_normalize_rows(const float* x, int64_t n, int d, float* out, hipStream_t s);

@@ -26,7 +26,7 @@ from hbird_mi import dist as hdist
 from hbird_mi import ops
 from hbird_mi import tiling
 from hbird_mi.models import FeatureExtractor, FeatureExtractorSimple
-from hbird_mi.nn.search_hip import HipFlatIndex, HipMultiIndex, MAX_K, merge_topk, merge_topk_packed, _METRICS
+from hbird_mi.nn.search_hip import HipFlatIndex, HipMultiIndex, check_k, k5, merge_topk, merge_topk_packed, _METRICS
 from hbird_mi.utils.eval_metrics import PredsmIoU
 
 try:
@@ -117,8 +117,7 @@ class HbirdEvaluation:
             if self.local_gpus[0] != self.gpu:
                 self.gpu = self.local_gpus[0]
                 self.gpu_device = torch.device("cuda", self.gpu)
-        if not 1 <= n_neighbours <= MAX_K:
-            raise ValueError(f"n_neighbours={n_neighbours} outside the supported range [1, {MAX_K}]")
+        check_k(n_neighbours, "n_neighbours")        # [1, 2048]: faiss-gpu's own range (the reference hands n_neighbours straight to it)
         # idx_shard keeps the reference's default (False, search_faiss.py:7): with several ranks that means a full bank
         # replica per rank and data-parallel validation batches (faiss.IndexReplicas, 65-74); idx_shard=True row-shards
         # the bank over the ranks (faiss.IndexShards, 53-63) -- the mode for banks that should not be built N times
@@ -185,6 +184,7 @@ class HbirdEvaluation:
         """An evaluator over a bank that is already resident in a `HipFlatIndex` (rows + label rows added by the caller): `evaluate` runs
         as usual, nothing is built.  Not in the reference (its bank only ever comes from `_create_memory`); used by `bench.py --e2e` to time
         the evaluation loop against the synthetic 10 M-row bank, and handy for banks produced elsewhere."""
+        check_k(n_neighbours, "n_neighbours")
         self = cls.__new__(cls)
         self.nn_params, self.device, self.nn_method = {}, device, "hip"
         dev = torch.device(device)
@@ -542,10 +542,10 @@ class HbirdEvaluation:
         k = self.n_neighbours
         self.index.use_current_stream()
         if not self.sharded and not want_details:
-            lh = self.index.search_aggregate(q, k, beta=0.02, id_base=0)
+            lh = k5(self.index, "search_aggregate", k)(q, k, beta=0.02, id_base=0)
             return lh.view(B, N, -1), None, None
         idx, dist = self.find_neighbours(q, k)
-        lh = self.index.aggregate(q, idx, dist, beta=0.02, id_base=self.id_base)
+        lh = k5(self.index, "aggregate", k)(q, idx, dist, beta=0.02, id_base=self.id_base)
         return lh.view(B, N, -1), idx, dist
 
     def _replicated_label_rows(self, ids: torch.Tensor) -> torch.Tensor:
@@ -754,7 +754,7 @@ class HbirdEvaluation:
                 if self.label_shard:
                     # every rank: the weights of the full lists, the label sum over the neighbours it owns; the all-reduce completes it
                     self.index.use_current_stream()
-                    lh_all = self.index.aggregate_partial(q_flat_all, idx, dist, self._label_table[1], beta=0.02, id_base=self.id_base)
+                    lh_all = k5(self.index, "aggregate_partial", k)(q_flat_all, idx, dist, self._label_table[1], beta=0.02, id_base=self.id_base)
                     torch.distributed.all_reduce(lh_all)
                 kf_all, kl_all = None, None
                 if want_details:
@@ -780,7 +780,7 @@ class HbirdEvaluation:
                 if self.label_shard:
                     label_hat = lh_all[lo:lo + q.shape[0]].contiguous().view(B, N, -1)
                 else:
-                    label_hat = self.index.aggregate(q.contiguous(), my_idx, my_dist, beta=0.02).view(B, N, -1)
+                    label_hat = k5(self.index, "aggregate", k)(q.contiguous(), my_idx, my_dist, beta=0.02).view(B, N, -1)
                 if want_details:
                     kl = (kl_all[lo:lo + q.shape[0]].reshape(B, N, k, -1) if self.label_shard
                           else self._replicated_label_rows(my_idx.reshape(-1)).view(B, N, k, -1))

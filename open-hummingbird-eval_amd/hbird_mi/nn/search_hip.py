@@ -19,8 +19,22 @@ from hbird_mi import _lib
 from hbird_mi.nn.search_base import NearestNeighborSearchBase
 
 _METRICS = {"dot_product": 0, "l2": 1, "euclidean": 1}
-MAX_K = 256          # of the fused search + label aggregation (HbirdEvaluation) and of sharded searches: HB_MAX_K_AGGREGATE
-MAX_K_SEARCH = 2048  # of a plain search on one GPU -- faiss-gpu's own limit (the reference forwards any k, search_faiss.py:84-85): HB_MAX_K
+MAX_K = 256          # of the LDS-resident entries (hb_index_search_aggregate / _aggregate / _aggregate_partial, hb_merge_topk): HB_MAX_K_AGGREGATE
+MAX_K_SEARCH = 2048  # of every search, aggregation and merge -- faiss-gpu's own limit (the reference forwards any k, search_faiss.py:84-85): HB_MAX_K
+_MERGE_LDS = 60000   # bytes of LDS the old merge kernel stages parts * k candidates in (hb_launch_merge_parts)
+
+
+def k5(index, name: str, k: int):
+    """THE routing between the two K5 families: `name` ("search_aggregate" / "aggregate" / "aggregate_partial") of a HipFlatIndex for this
+    k -- the LDS-resident entry up to 256 (launch for launch what it always was), its `_bigk` twin beyond (hb_bigk_*).  A HipMultiIndex
+    has no twins: its methods come back as they are and route through here on its aggregation handle."""
+    return getattr(index, name + "_bigk" if k > MAX_K and hasattr(index, name + "_bigk") else name)
+
+
+def check_k(k: int, what: str = "k"):
+    """1 <= k <= 2048 or the ValueError faiss-gpu raises for its k-select limit."""
+    if not 1 <= k <= MAX_K_SEARCH:
+        raise ValueError(f"{what}={k} outside the supported range [1, {MAX_K_SEARCH}] (faiss-gpu's own limit)")
 
 
 def _ptr(t):
@@ -165,6 +179,37 @@ class HipFlatIndex:
         out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
         _lib.check(_lib.lib().hb_index_aggregate_partial(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base),
                                                          float(beta), _ptr(norms_all), norms_all.shape[0], _ptr(out)))
+        return out
+
+    # k beyond 256: the hb_bigk_* twins of the three methods above (same arguments, same results, for k <= 256 the same bits; k <= 2048)
+    def search_aggregate_bigk(self, q, k: int, beta: float = 0.02, id_base: int = 0, want_neighbours: bool = False):
+        on_dev, q = self._as_f32(q)
+        nq = q.shape[0]
+        new = (lambda shape, dt: torch.empty(shape, dtype=dt, device=q.device)) if on_dev else \
+            (lambda shape, dt: np.empty(shape, dtype=np.int64 if dt == torch.int64 else np.float32))
+        out = new((nq, self.num_classes), torch.float32)
+        idx = new((nq, k), torch.int64) if want_neighbours else None
+        dist = new((nq, k), torch.float32) if want_neighbours else None
+        _lib.check(_lib.lib().hb_bigk_search_aggregate(self._h, _ptr(q), nq, int(k), int(id_base), float(beta),
+                                                        _ptr(out), _ptr(idx), _ptr(dist), int(on_dev)))
+        return (out, idx, dist) if want_neighbours else out
+
+    def aggregate_bigk(self, q, idx, dist, beta: float = 0.02, id_base: int = 0):
+        assert q.is_cuda and idx.is_cuda and dist.is_cuda
+        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous()
+        out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().hb_bigk_aggregate(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1],
+                                                 int(id_base), float(beta), _ptr(out), 1))
+        return out
+
+    def aggregate_partial_bigk(self, q, idx, dist, norms_all: torch.Tensor, beta: float = 0.02, id_base: int = 0):
+        assert q.is_cuda and idx.is_cuda and dist.is_cuda and norms_all.is_cuda
+        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous(); norms_all = norms_all.contiguous().float()
+        if self.ntotal == 0:                 # an empty shard owns no neighbour
+            return torch.zeros((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
+        out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().hb_bigk_aggregate_partial(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base),
+                                                        float(beta), _ptr(norms_all), norms_all.shape[0], _ptr(out)))
         return out
 
     @property
@@ -384,27 +429,34 @@ class HipFlatIndex:
         return d
 
 
+def _merge_fits_lds(parts: int, k: int) -> bool:
+    """parts * k candidates fit the old merge kernel's LDS staging (hb_launch_merge_parts' own test)."""
+    n = parts * k
+    return (n * 4 + 15) // 16 * 16 + n * 8 <= _MERGE_LDS
+
+
 def merge_topk(dist_parts: torch.Tensor, idx_parts: torch.Tensor, metric: int):
-    """[parts, nq, k] CUDA tensors -> merged (idx [nq,k], dist [nq,k]); hb_merge_topk."""
+    """[parts, nq, k] CUDA tensors -> merged (idx [nq,k], dist [nq,k]); hb_merge_topk while parts * k fits its LDS staging, beyond that
+    hb_bigk_merge_topk, whose lists must be sorted best-first with the missing entries last (what a search returns)."""
     parts, nq, k = dist_parts.shape
     dist_parts = dist_parts.contiguous(); idx_parts = idx_parts.contiguous()
     idx = torch.empty((nq, k), dtype=torch.int64, device=dist_parts.device)
     dist = torch.empty((nq, k), dtype=torch.float32, device=dist_parts.device)
     s = torch.cuda.current_stream(dist_parts.device).cuda_stream
-    _lib.check(_lib.lib().hb_merge_topk(_ptr(dist_parts), _ptr(idx_parts), parts, nq, k, int(metric), _ptr(idx),
-                                        _ptr(dist), ctypes.c_void_p(s)))
+    entry = _lib.lib().hb_merge_topk if _merge_fits_lds(parts, k) else _lib.lib().hb_bigk_merge_topk
+    _lib.check(entry(_ptr(dist_parts), _ptr(idx_parts), parts, nq, k, int(metric), _ptr(idx), _ptr(dist), ctypes.c_void_p(s)))
     return idx, dist
 
 
 def merge_topk_packed(recv: torch.Tensor, part_bytes: int, parts: int, nq: int, k: int, metric: int):
     """The gathered buffer of a dist.PackedTopK (CUDA, `parts` packed lists part_bytes apart) -> merged (idx, dist);
-    hb_merge_topk_packed reads it in place."""
+    hb_merge_topk_packed reads it in place (hb_bigk_merge_topk_packed where parts * k is beyond its staging: sorted lists, see merge_topk)."""
     assert recv.is_cuda and recv.is_contiguous() and recv.numel() * recv.element_size() >= parts * part_bytes
     idx = torch.empty((nq, k), dtype=torch.int64, device=recv.device)
     dist = torch.empty((nq, k), dtype=torch.float32, device=recv.device)
     s = torch.cuda.current_stream(recv.device).cuda_stream
-    _lib.check(_lib.lib().hb_merge_topk_packed(_ptr(recv), int(part_bytes), int(parts), int(nq), int(k), int(metric), _ptr(idx),
-                                               _ptr(dist), ctypes.c_void_p(s)))
+    entry = _lib.lib().hb_merge_topk_packed if _merge_fits_lds(parts, k) else _lib.lib().hb_bigk_merge_topk_packed
+    _lib.check(entry(_ptr(recv), int(part_bytes), int(parts), int(nq), int(k), int(metric), _ptr(idx), _ptr(dist), ctypes.c_void_p(s)))
     return idx, dist
 
 
@@ -727,7 +779,7 @@ class HipMultiIndex:
         self._tables()
         with torch.cuda.device(self.home):
             self.agg.use_current_stream()
-            return self.agg.aggregate(q.to(self.home), idx, dist, beta=beta, id_base=id_base)
+            return k5(self.agg, "aggregate", idx.shape[1])(q.to(self.home), idx, dist, beta=beta, id_base=id_base)
 
     def search_aggregate(self, q, k: int, beta: float = 0.02, id_base: int = 0, want_neighbours: bool = False):
         """K4 on every GPU, merge on the home device, K5 there (hb_index_aggregate on the merged lists)."""
@@ -871,12 +923,9 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
     def find_nearest_neighbors(self, q, k=None):
         if k is None:
             k = self.n_neighbors
-        sharded = (self.idx_shard and self.world > 1) or self.multi is not None
-        top = MAX_K if sharded else MAX_K_SEARCH
-        if not 1 <= k <= top:
-            # faiss-gpu raises for k > 2048 (its k-select limit); here one GPU takes the same 2048 (beyond 256 in ceil(k / 256) passes),
-            # a sharded or multi-GPU index 256 (the merge of the shards' lists)
-            raise ValueError(f"k={k} outside the supported range [1, {top}]" + (" of a sharded index (one GPU: up to 2048, faiss-gpu's own limit)" if sharded else " (faiss-gpu's own limit)"))
+        # faiss-gpu raises for k > 2048 (its k-select limit); so does every index here, one GPU or sharded (beyond 256 in ceil(k / 256)
+        # passes, the shards' lists merged by hb_bigk_merge_topk where they outgrow hb_merge_topk's staging)
+        check_k(k)
         if isinstance(q, torch.Tensor) and q.is_cuda:
             idx, dist = self._search_device(q, k)
             return idx, dist
