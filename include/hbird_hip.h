@@ -290,6 +290,8 @@ int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n);
  * that reached the fp32 kernel). */
 int hb_index_set_fp16_escalation(hb_index_t* ix, int mode);
 int hb_index_last_fp16_escalated(const hb_index_t* ix, int64_t* n);
+/* The mean-centred form of the fp16 copy -- hb_index_set_fp16_centre, hb_index_fp16_centre_info, hb_multi_set_fp16_centre -- is declared in
+ * hbird_hip_centre.h, which this header includes at its end. */
 /* kNN kernel variant, for A/B runs and tests (same results): 0 = default; 3 = the fp32 kernel with register-resident query fragments
  * wherever it applies (D padded to a multiple of 32: what the default does too); 4 = never that kernel (both operands staged through
  * LDS); 6 = small fp32 searches with k <= 32 on sorted LDS lists as until round 3 (the default runs them on phased candidate pools).
@@ -408,6 +410,8 @@ int hb_schedule_plan_phased(int nqt, int nbt, int workgroups, int panel_tiles, i
 /* hb_schedule_plan / _phased for the work list of hb_index_set_cluster_sharing(ix, 2). */
 int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, int d, int cluster_q, int cluster_b, int phased,
                             int* segs_out, int64_t max_segs, int64_t stats[8]);
+
+#include "hbird_hip_centre.h"
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,7 @@ extern "C" int hb_index_free(hb_index_t* ix) {
     void* ptrs[] = {ix->tiles, ix->binit, ix->bnorm, ix->labels, ix->q_tiles, ix->q_aux, ix->state, ix->sched_dev, ix->tmp,
                     ix->tiles16, ix->stamp_keep, ix->q16, ix->cand, ix->bmax, ix->fb, ix->fb1, ix->sched_esc_dev, ix->bigk, ix->mtmp, ix->f16_flag, ix->labels16, ix->lab_flag, ix->rows32};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    hb_centre_drop(ix);
     for (auto& c : ix->xcal) { if (c.stamp_host) (void)hipHostFree(c.stamp_host); if (c.stamp_ev) (void)hipEventDestroy(c.stamp_ev); }
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
@@ -131,6 +132,35 @@ extern "C" int hb_index_set_fp16(hb_index_t* ix, int enable) {
     // 2: only where it pays; HB_FP16_AUTO: the state a new index starts in (hb_screen_choose); 0: the caller asked for the fp32 kernel
     ix->fp16 = enable == HB_FP16_AUTO ? HB_FP16_AUTO : enable == 2 ? 2 : (enable ? 1 : 0);
     ix->f16_adapt = hb_f16_adapt();
+    return 0;
+}
+// The mean-centred form of the fp16 copy (hbird_f16_centre.hip).  A change drops the copy: the next screened search builds it in the new form.
+extern "C" int hb_index_set_fp16_centre(hb_index_t* ix, int on) {
+    if (!ix) return hb_fail("hb_index_set_fp16_centre: NULL index handle");
+    if (on != 0 && on != 1) return hb_fail("hb_index_set_fp16_centre: on must be 0 (the plain fp16 copy) or 1 (the mean-centred copy)");
+    if (on == ix->fp16_centre) return 0;
+    HB_HIP(hipSetDevice(ix->device));
+    HB_HIP(hipStreamSynchronize(ix->stream));
+    if (ix->tiles16) { HB_HIP(hipFree(ix->tiles16)); ix->tiles16 = nullptr; }
+    ix->f16_rows = 0; ix->f16_cap_rows = 0; ix->f16_overflow = 0; ix->f16_declined_cap = -1;
+    if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, ix->stream));      // (the flag speaks of the values of the copy's form)
+    hb_centre_drop(ix);
+    ix->fp16_centre = on; ix->last_centred = 0;
+    ix->f16_adapt = hb_f16_adapt();      // (the failing shares belong to the form that was measured)
+    return 0;
+}
+extern "C" int hb_index_fp16_centre_info(const hb_index_t* ix, double out[8]) {
+    if (!ix || !out) return hb_fail("hb_index_fp16_centre_info: NULL pointer");
+    for (int i = 0; i < 8; ++i) out[i] = 0.0;
+    const hb_centre_state& c = ix->centre;
+    HB_HIP(hipSetDevice(ix->device));
+    float sc[4] = {0, 0, 0, 0}, bmax = 0.0f;
+    HB_HIP(hipStreamSynchronize(ix->stream));
+    HB_HIP(hipMemcpy(&bmax, ix->bmax, 4, hipMemcpyDeviceToHost));
+    const bool active = ix->fp16_centre && c.active && ix->tiles16 && c.sc;
+    if (active) HB_HIP(hipMemcpy(sc, c.sc, 16, hipMemcpyDeviceToHost));
+    out[0] = active ? 1.0 : 0.0; out[1] = sc[1]; out[2] = sc[0]; out[3] = bmax; out[4] = sc[3]; out[5] = active ? (double)c.rows : 0.0;
+    out[6] = ix->fp16_centre; out[7] = ix->last_centred;
     return 0;
 }
 extern "C" int hb_last_search_path(const hb_index_t* ix, int* path, int* reason) {
@@ -349,6 +379,7 @@ extern "C" int hb_index_reset(hb_index_t* ix) {
     }
     HB_HIP(hipMemsetAsync(ix->bmax, 0, 4, s));
     ix->ntotal = 0; ix->nlabels = 0; ix->lab_checked = 0; ix->f16_rows = 0; ix->f16_overflow = 0; ix->rows32_rows = 0;
+    ix->centre.rows = 0;      // (f16_rows = 0: a centred copy derives its mean anew from the rows of the next search)
     if (ix->lab_flag) HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, s));
     if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s));
     return 0;

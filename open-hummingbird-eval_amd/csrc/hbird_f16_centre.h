@@ -1,0 +1,25 @@
+// The mean-centred form of the fp16 candidate copy (hbird_f16_centre.hip): state kept per index, and what the re-rank kernels take of it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+struct hb_index;
+
+struct hb_centre_state {
+    float* mu = nullptr;            // [max(dp16, dp)] column mean of the rows present when the copy was made (0 on the padding dimensions)
+    float* g = nullptr;             // [cap_rows] mu.(b - mu), k-ascending fp32 chain
+    float* init16 = nullptr;        // [cap_rows] the candidate kernel's row init of the current search: fmaf(t, g, binit)
+    float* sc = nullptr;            // device scalars {cmax = max ||b - mu||, ||mu|| (rounded up), mu.mu, t of the last search}
+    char* qaux = nullptr; size_t qaux_bytes = 0;   // per search: [c_q nq][||q - t mu|| nq][partial sums of c_q]
+    int64_t cap_rows = 0;           // capacity the row arrays were allocated for
+    int64_t rows = 0;               // rows converted with mu
+    int active = 0;                 // the fp16 copy holds centred rows (0: no copy yet, or a non-finite / all-zero mean: the plain copy)
+};
+
+// per-query constants of one centred pass, for the re-rank: c_q = q.mu, ||q - t mu||, the device scalars above
+struct hb_centre_view { const float* cq; const float* qcn; const float* sc; };
+
+void hb_centre_drop(hb_index* ix);
+int hb_centre_convert(hb_index* ix, hipStream_t s, int* centred_out);
+int hb_centre_queries(hb_index* ix, int64_t nq, int first, _Float16* q16, hb_centre_view* view, hipStream_t s);

@@ -7,6 +7,7 @@
 #include <vector>
 #include "hbird_schedule.h"
 #include "hbird_calibrate.h"
+#include "hbird_f16_centre.h"
 
 // ---- tile geometry of the kNN kernel (see DESIGN.md "Data layout in HBM") -------------------
 #define HB_RT 32         // rows per fragment tile (MFMA 32x32x2)
@@ -89,6 +90,10 @@ struct hb_index {
     float* rows32 = nullptr; int64_t rows32_cap_rows = 0, rows32_rows = 0; int rows32_rs = 0;
     int rerank_copy = 0;                                 // 0 = automatic, 1 = always, 2 = never (hb_index_set_rerank_copy)
     int64_t rows32_declined_cap = -1;                    // automatic mode found no room for the copy at this capacity: not asked again per search
+    // the mean-centred form of that copy (hb_index_set_fp16_centre; hbird_f16_centre.hip): mu, two floats per row, four device scalars
+    int fp16_centre = 0;                                 // the setting: 0 = the plain copy (default), 1 = centred
+    int last_centred = 0;                                // the last search of a caller ran its candidate pass on the centred copy
+    hb_centre_state centre;
     void* q16 = nullptr; size_t q16_bytes = 0;
     char* cand = nullptr; size_t cand_bytes = 0;
     float* bmax = nullptr;                               // device scalar: max bank-row norm
@@ -143,11 +148,12 @@ int hb_launch_rerank_rows(const float* rows, int rs, const float* binit, int d, 
                           const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
                           unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric,
                           int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in = nullptr, float* kth_out = nullptr,
-                          float* floor_out = nullptr);
+                          float* floor_out = nullptr, const hb_centre_view* cv = nullptr);
 int hb_launch_rerank(const float* tiles, const float* binit, int g8, int d, const float* q, const float* qn2,
                      const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
                      unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric, int64_t ntotal, int64_t* out_idx,
-                     float* out_dist, hipStream_t s, const float* seed_in = nullptr, float* kth_out = nullptr, float* floor_out = nullptr);
+                     float* out_dist, hipStream_t s, const float* seed_in = nullptr, float* kth_out = nullptr, float* floor_out = nullptr,
+                     const hb_centre_view* cv = nullptr);
 int hb_launch_bnorm_max(const float* bnorm, int64_t n, float* bmax, hipStream_t s);
 int hb_launch_scatter_rows(const int64_t* rows, int64_t n, int k, const int64_t* src_idx, const float* src_dist,
                            int64_t* out_idx, float* out_dist, hipStream_t s);

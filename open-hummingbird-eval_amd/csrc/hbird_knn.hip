@@ -718,7 +718,10 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
         }
         if (f16 && ix->f16_rows < ix->ntotal) {
             const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
-            if (hb_launch_tiles_to_f16(ix->tiles, ix->g8, (_Float16*)ix->tiles16, ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
+            // (hb_index_set_fp16_centre: the rows as fl32(b - mu) with their per-row term, hbird_f16_centre.hip; a bank without a usable mean: the plain copy)
+            int centred = 0;
+            if (ix->fp16_centre && hb_centre_convert(ix, s0, &centred)) return -1;
+            if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, (_Float16*)ix->tiles16, ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
             ix->f16_rows = ix->ntotal;
             HB_HIP(hipMemcpyAsync(&ix->f16_overflow, ix->f16_flag, 4, hipMemcpyDeviceToHost, s0));
             HB_HIP(hipStreamSynchronize(s0));
@@ -769,7 +772,8 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     // fp16 mode: the fused kernel collects kc >= 2k candidates, the fp32 chain arithmetic re-ranks them
     // k' = 2k, at least 64 (rounded up to 8, not to 64 as until round 4: the candidate kernel's time is linear in k' -- 300,000 x 768, 21,904
     // queries: k' = 64 / 128 / 192 / 256 -> 12.95 / 15.85 / 20.7 / 25.0 ms -- so k = 33 paid for 128 candidates where it needs 66)
-    if (esc == 0) { ix->last_path = !f16 ? HB_PATH_FP32 : wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = why; }
+    const bool centred = f16 && ix->fp16_centre && ix->centre.active;      // this pass runs on the centred copy
+    if (esc == 0) { ix->last_path = !f16 ? HB_PATH_FP32 : wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = why; ix->last_centred = centred ? 1 : 0; }
     const int kc = f16 ? (esc == 1 || wide_first ? 256 : std::min(256, std::max(64, (2 * k + 7) / 8 * 8))) : k;     // (the second pass: the widest list the re-rank takes)
     // Small searches (few stages per workgroup) on the kernel with register-resident query fragments run on POOLS even for k <= 32:
     // phased, with the bisection cold start and the scan epilogue (hbird_knn_bd.hip <WIDE, COLD>) a pool takes a tile's survivors in one
@@ -972,13 +976,17 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
         // fp16 copy of the query fragment tiles (the bank's is up to date: top of this function)
         const int64_t nqp = (int64_t)nqt * HB_QT;
         if (ensure_bytes((char**)&ix->q16, &ix->q16_bytes, (size_t)nqp * ix->dp16 * 2)) return -1;
-        if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, (_Float16*)ix->q16, ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
+        // centred: fp16 tiles of q - t mu, c_q and ||q - t mu|| per query; a caller's search also derives t and, from it, the rows' init values
+        hb_centre_view cview{nullptr, nullptr, nullptr};
+        if (centred) { if (hb_centre_queries(ix, nq, esc == 0, (_Float16*)ix->q16, &cview, s)) return -1; }
+        else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, (_Float16*)ix->q16, ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
+        const hb_centre_view* cv = centred ? &cview : nullptr;
         if (ensure_bytes(&ix->cand, &ix->cand_bytes, (size_t)nq * kc * 12)) return -1;
         int64_t* cand_idx = reinterpret_cast<int64_t*>(ix->cand);
         float* cand_dist = reinterpret_cast<float*>(ix->cand + (size_t)nq * kc * 8);
         knn16_args h;
         h.wg_stamp = a.wg_stamp;
-        h.bank16 = reinterpret_cast<const _Float16*>(ix->tiles16); h.binit = ix->binit; h.q16 = reinterpret_cast<const _Float16*>(ix->q16); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
+        h.bank16 = reinterpret_cast<const _Float16*>(ix->tiles16); h.binit = centred ? ix->centre.init16 : ix->binit; h.q16 = reinterpret_cast<const _Float16*>(ix->q16); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
         h.state_s = a.state_s; h.state_i = a.state_i; h.g16 = ix->dp16 / 16; h.k = kc; h.klw = klw;
         h.state_cnt = a.state_cnt; h.state_thr = a.state_thr; h.gthr = a.gthr;
         h.wg_member = a.wg_member; h.prog = a.prog; h.cl = a.cl; h.lag = a.lag; h.cl_stats = a.cl_stats;
@@ -1014,9 +1022,9 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
         const float* seed_in = esc == 1 ? ix->seed_dev : nullptr;
         if (ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal) {
             if (hb_launch_rerank_rows(ix->rows32, ix->rows32_rs, ix->binit, ix->d, q_dev, ix->q_aux, cand_idx, cand_dist, ix->q_aux + nq, ix->bmax,
-                                      cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo)) return -1;
+                                      cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
         } else if (hb_launch_rerank(ix->tiles, ix->binit, ix->g8, ix->d, q_dev, ix->q_aux, cand_idx, cand_dist, ix->q_aux + nq, ix->bmax,
-                                    cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo)) return -1;
+                                    cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
         if (ix->time_kernels) {
             HB_HIP(hipEventSynchronize(ix->ev1));
             float ms = 0.f;

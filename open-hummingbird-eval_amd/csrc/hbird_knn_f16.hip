@@ -273,12 +273,16 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
 //            search of this query (ties pass: floor_from_key);
 //   floor_out[query]: kth - 1.001 E, a hair lower: every row that can still enter the top k has an exact score >= kth, hence an fp16 score
 //            above this -- the floor of a second, wider fp16 pass (0.001 E is twenty times the rounding of these few operations).
+// CENTRED (hbird_f16_centre.hip): the pass ran on q - t mu and b - mu and its scores lack the query's constant c_q = q.mu -- every comparison of
+// an exact score with a pass score adds it to the latter; floor_out seeds the second PASS and is written in the pass' units (kth - c_q - 1.001 E'),
+// kth_out seeds the fp32 kernel and stays exact.
 struct hb_rerank_seeds { const float* seed_in; float* kth_out; float* floor_out; };
-__device__ __forceinline__ bool hb_rerank_finish(const hb_rerank_seeds& sd, int64_t qi, bool ok, bool list_not_full, bool have_kth, float s, float E) {
-    if (sd.seed_in && list_not_full && have_kth && !ok) ok = s > sd.seed_in[qi] + E;
+template <bool CENTRED>
+__device__ __forceinline__ bool hb_rerank_finish(const hb_rerank_seeds& sd, int64_t qi, bool ok, bool list_not_full, bool have_kth, float s, float E, float cq) {
+    if (sd.seed_in && list_not_full && have_kth && !ok) ok = CENTRED ? s > sd.seed_in[qi] + cq + E : s > sd.seed_in[qi] + E;
     if (sd.kth_out) {
-        const bool fin = have_kth && E < INFINITY && fabsf(s) < INFINITY;      // (false for NaN as well)
-        float f = s - 1.001f * E;
+        const bool fin = have_kth && E < INFINITY && fabsf(s) < INFINITY && (!CENTRED || fabsf(cq) < INFINITY);      // (false for NaN as well)
+        float f = CENTRED ? s - cq - 1.001f * E : s - 1.001f * E;
         f = f - fabsf(f) * 2.4e-7f - 1e-37f;
         sd.kth_out[qi] = fin ? s : -INFINITY;
         sd.floor_out[qi] = fin ? f : -INFINITY;
@@ -286,16 +290,28 @@ __device__ __forceinline__ bool hb_rerank_finish(const hb_rerank_seeds& sd, int6
     return ok;
 }
 
+// The centred pass' bound E' >= |pass score + c_q - exact score| (derivation: DESIGN.md 4).  qc = ||fl(q - t mu)||, cmax = max ||fl(b - mu)||,
+// qn = ||q||, bmax = max ||b||, mun = ||mu||; D' = D + 4 pays for the fmaf of init16 and the additions of the comparison itself.
+__device__ __forceinline__ float hb_centred_E(const hb_centre_view& cv, int64_t qi, float qn, float bmax, int d, int metric) {
+    const float cmax = cv.sc[0], mun = cv.sc[1], at = fabsf(cv.sc[3]), qc = cv.qcn[qi];
+    const float du = (float)(d + 4) * 1.2e-7f;
+    return qc * cmax * (1.05f / 1024.0f + du)                                                      // fp16 images of both centred operands; the pass' fp32 sums
+           + du * (qn * bmax + qn * mun + 2.0f * at * mun * cmax + (metric == 1 ? bmax * bmax : 0.0f))   // exact chain; chain of c_q; chain of g, init16 and its share of the sums; |row init|
+           + (qc + cmax) * sqrtf((float)d) * 6e-8f                                                 // fp16 subnormal inputs
+           + 1e-30f;
+}
+
 // Exact re-rank: one wave per query; lane j scores candidates j, j+64, ... with the fp32 chain arithmetic of the fp32
 // kernel (acc = row init; acc = fmaf(q_k, b_k, acc) for k ascending over the fp32 fragment tiles), then the wave
 // ranks them by (score desc, id asc) and writes the best k.
+template <bool CENTRED>
 __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ tiles, const float* __restrict__ binit, int g8,
                                                      int d, const float* __restrict__ q, const float* __restrict__ qn2,
                                                      const int64_t* __restrict__ cand, const float* __restrict__ cand_score,
                                                      const float* __restrict__ qnorm, const float* __restrict__ bmax,
                                                      unsigned char* __restrict__ certified, int kc, int64_t nq, int k,
                                                      int64_t id_base, int metric, int out_metric, int64_t ntotal,
-                                                     int64_t* __restrict__ out_idx, float* __restrict__ out_dist, hb_rerank_seeds sd) {
+                                                     int64_t* __restrict__ out_idx, float* __restrict__ out_dist, hb_rerank_seeds sd, hb_centre_view cv) {
     __shared__ float s_sc[4][256];
     __shared__ int64_t s_id[4][256];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -308,10 +324,12 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ t
     // score is more than 2E below the k-th's is exactly below k of them and cannot be in the answer.  Its row is not read (a row
     // is 2 x D/8 sixteen-byte pieces 512 B apart: the re-rank is bound by the sectors it touches; 50,176 x 384, 12,544 queries:
     // 0.96 ms of a 2.4 ms search).  A non-finite E (query norm) skips nothing, and fails the certificate.
-    const float E = qnorm[qi] * bmax[0] * (1.05f / 1024.0f + (float)d * 2.4e-7f)
-                    + (qnorm[qi] + bmax[0]) * sqrtf((float)d) * 6e-8f                 // fp16 subnormal inputs
-                    + (metric == 1 ? (float)d * 1.2e-7f * 0.5f * bmax[0] * bmax[0] : 0.0f)  // |row init| in the sums
-                    + 1e-30f;
+    const float E = CENTRED ? hb_centred_E(cv, qi, qnorm[qi], bmax[0], d, metric)
+                            : qnorm[qi] * bmax[0] * (1.05f / 1024.0f + (float)d * 2.4e-7f)
+                              + (qnorm[qi] + bmax[0]) * sqrtf((float)d) * 6e-8f                 // fp16 subnormal inputs
+                              + (metric == 1 ? (float)d * 1.2e-7f * 0.5f * bmax[0] * bmax[0] : 0.0f)  // |row init| in the sums
+                              + 1e-30f;
+    const float cq = CENTRED ? cv.cq[qi] : 0.0f;
     const float cut = (k <= kc && cand[qi * (int64_t)kc + (k - 1)] >= 0) ? cand_score[qi * (int64_t)kc + (k - 1)] - 2.0f * E : -INFINITY;
     for (int c = lane; c < kc; c += 64) {
         const int64_t row = cand[qi * (int64_t)kc + c];
@@ -354,12 +372,12 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ t
             // (||q|| <= 65504 rules that out; a NaN / inf norm fails the test too), and a candidate list that is not full
             // although the bank has kc rows has lost rows to NaN / -inf fp16 scores that nothing bounds.
             const int64_t last = cand[qi * (int64_t)kc + kc - 1];
-            const bool finite_q = qnorm[qi] <= 65504.0f;
+            const bool finite_q = CENTRED ? (cv.qcn[qi] <= 65504.0f && qnorm[qi] < INFINITY && fabsf(cq) < INFINITY) : qnorm[qi] <= 65504.0f;   // (centred: the operands of the pass are q - t mu)
             bool ok = last < 0 && ntotal < kc && finite_q;   // fewer than kc rows exist: every row was a candidate
             if (last >= 0 && id >= 0 && finite_q) {
-                ok = s > cand_score[qi * (int64_t)kc + kc - 1] + E;
+                ok = CENTRED ? s > cand_score[qi * (int64_t)kc + kc - 1] + cq + E : s > cand_score[qi * (int64_t)kc + kc - 1] + E;
             }
-            ok = hb_rerank_finish(sd, qi, ok, last < 0, id >= 0 && finite_q, s, E);
+            ok = hb_rerank_finish<CENTRED>(sd, qi, ok, last < 0, id >= 0 && finite_q, s, E, cq);
             certified[qi] = ok ? 1 : 0;
         }
         if (rank < k) {
@@ -377,12 +395,14 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ t
 int hb_launch_rerank(const float* tiles, const float* binit, int g8, int d, const float* q, const float* qn2,
                      const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
                      unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric,
-                     int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in, float* kth_out, float* floor_out) {
+                     int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in, float* kth_out, float* floor_out,
+                     const hb_centre_view* cv) {
     if (nq == 0) return 0;
     if (kc > 256) return hb_fail("hb_index_search: too many candidates for the re-rank kernel");
-    rerank_kernel<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s>>>(tiles, binit, g8, d, q, qn2, cand, cand_score, qnorm, bmax,
-                                                                     certified, kc, nq, k, id_base, metric, out_metric, ntotal, out_idx, out_dist,
-                                                                     hb_rerank_seeds{seed_in, kth_out, floor_out});
+    auto fn = cv ? rerank_kernel<true> : rerank_kernel<false>;
+    fn<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s>>>(tiles, binit, g8, d, q, qn2, cand, cand_score, qnorm, bmax,
+                                                          certified, kc, nq, k, id_base, metric, out_metric, ntotal, out_idx, out_dist,
+                                                          hb_rerank_seeds{seed_in, kth_out, floor_out}, cv ? *cv : hb_centre_view{nullptr, nullptr, nullptr});
     HB_HIP(hipGetLastError());
     return 0;
 }
@@ -422,13 +442,14 @@ int hb_launch_tiles_to_rows(const float* t32, int g8, float* rows, int rs, int64
 
 #define RRW_NONE 0xFFFFFFFFu
 #define RRW_STRIDE 36      // dwords per row of the LDS image: 128 B of values + 16 B (lane t's b128 reads of row t: no bank conflicts)
+template <bool CENTRED>
 __global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restrict__ rows, int rs, const float* __restrict__ binit,
                                                           int d, const float* __restrict__ q, const float* __restrict__ qn2,
                                                           const int64_t* __restrict__ cand, const float* __restrict__ cand_score,
                                                           const float* __restrict__ qnorm, const float* __restrict__ bmax,
                                                           unsigned char* __restrict__ certified, int kc, int64_t nq, int k,
                                                           int64_t id_base, int metric, int out_metric, int64_t ntotal,
-                                                          int64_t* __restrict__ out_idx, float* __restrict__ out_dist, hb_rerank_seeds sd) {
+                                                          int64_t* __restrict__ out_idx, float* __restrict__ out_dist, hb_rerank_seeds sd, hb_centre_view cv) {
     __shared__ float s_sc[4][256];
     __shared__ unsigned s_id[4][256];                    // bank rows (below 2^32); RRW_NONE: no candidate
     __shared__ int s_act[4][256];
@@ -438,10 +459,12 @@ __global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restric
     if (qi >= nq) return;   // wave-uniform
     const float* qr = q + qi * (int64_t)d;
     // (E and the skip rule: rerank_kernel)
-    const float E = qnorm[qi] * bmax[0] * (1.05f / 1024.0f + (float)d * 2.4e-7f)
-                    + (qnorm[qi] + bmax[0]) * sqrtf((float)d) * 6e-8f
-                    + (metric == 1 ? (float)d * 1.2e-7f * 0.5f * bmax[0] * bmax[0] : 0.0f)
-                    + 1e-30f;
+    const float E = CENTRED ? hb_centred_E(cv, qi, qnorm[qi], bmax[0], d, metric)
+                            : qnorm[qi] * bmax[0] * (1.05f / 1024.0f + (float)d * 2.4e-7f)
+                              + (qnorm[qi] + bmax[0]) * sqrtf((float)d) * 6e-8f
+                              + (metric == 1 ? (float)d * 1.2e-7f * 0.5f * bmax[0] * bmax[0] : 0.0f)
+                              + 1e-30f;
+    const float cq = CENTRED ? cv.cq[qi] : 0.0f;
     const float cut = (k <= kc && cand[qi * (int64_t)kc + (k - 1)] >= 0) ? cand_score[qi * (int64_t)kc + (k - 1)] - 2.0f * E : -INFINITY;
     // the candidates that need an exact score, compacted: s_act[0 .. n_act)
     int n_act = 0;
@@ -530,10 +553,10 @@ __global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restric
         }
         if (rank == k - 1) {   // the certificate: rerank_kernel
             const int64_t last = cand[qi * (int64_t)kc + kc - 1];
-            const bool finite_q = qnorm[qi] <= 65504.0f;
+            const bool finite_q = CENTRED ? (cv.qcn[qi] <= 65504.0f && qnorm[qi] < INFINITY && fabsf(cq) < INFINITY) : qnorm[qi] <= 65504.0f;   // (centred: the operands of the pass are q - t mu)
             bool ok = last < 0 && ntotal < kc && finite_q;
-            if (last >= 0 && id >= 0 && finite_q) ok = s > cand_score[qi * (int64_t)kc + kc - 1] + E;
-            ok = hb_rerank_finish(sd, qi, ok, last < 0, id >= 0 && finite_q, s, E);
+            if (last >= 0 && id >= 0 && finite_q) ok = CENTRED ? s > cand_score[qi * (int64_t)kc + kc - 1] + cq + E : s > cand_score[qi * (int64_t)kc + kc - 1] + E;
+            ok = hb_rerank_finish<CENTRED>(sd, qi, ok, last < 0, id >= 0 && finite_q, s, E, cq);
             certified[qi] = ok ? 1 : 0;
         }
         if (rank < k) {
@@ -551,12 +574,14 @@ __global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restric
 int hb_launch_rerank_rows(const float* rows, int rs, const float* binit, int d, const float* q, const float* qn2,
                           const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
                           unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric,
-                          int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in, float* kth_out, float* floor_out) {
+                          int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in, float* kth_out, float* floor_out,
+                          const hb_centre_view* cv) {
     if (nq == 0) return 0;
     if (kc > 256) return hb_fail("hb_index_search: too many candidates for the re-rank kernel");
-    rerank_rows_kernel<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s>>>(rows, rs, binit, d, q, qn2, cand, cand_score, qnorm, bmax,
-                                                                          certified, kc, nq, k, id_base, metric, out_metric, ntotal, out_idx, out_dist,
-                                                                          hb_rerank_seeds{seed_in, kth_out, floor_out});
+    auto fn = cv ? rerank_rows_kernel<true> : rerank_rows_kernel<false>;
+    fn<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s>>>(rows, rs, binit, d, q, qn2, cand, cand_score, qnorm, bmax,
+                                                          certified, kc, nq, k, id_base, metric, out_metric, ntotal, out_idx, out_dist,
+                                                          hb_rerank_seeds{seed_in, kth_out, floor_out}, cv ? *cv : hb_centre_view{nullptr, nullptr, nullptr});
     HB_HIP(hipGetLastError());
     return 0;
 }

@@ -90,6 +90,12 @@ extern "C" int hb_multi_set_fp16(hb_multi_t* m, int enable) {
     return 0;
 }
 
+extern "C" int hb_multi_set_fp16_centre(hb_multi_t* m, int on) {
+    if (!m) return hb_fail("hb_multi_set_fp16_centre: NULL handle");
+    for (hb_index_t* p : m->ix) if (hb_index_set_fp16_centre(p, on)) return -1;      // every shard its own mean
+    return 0;
+}
+
 extern "C" int hb_multi_reserve(hb_multi_t* m, int64_t n_rows) {
     if (!m) return hb_fail("hb_multi_reserve: NULL handle");
     const int n = (int)m->ix.size();

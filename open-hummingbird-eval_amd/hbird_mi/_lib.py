@@ -115,6 +115,13 @@ SIGNATURES = {
     "hb_index_schedule_info": (c_int, [c_void_p, POINTER(c_int64)]),
 }
 
+# ... and include/hbird_hip_centre.h (the mean-centred form of the fp16 copy), which hbird_hip.h includes
+SIGNATURES_CENTRE = {
+    "hb_index_set_fp16_centre": (c_int, [c_void_p, c_int]),
+    "hb_index_fp16_centre_info": (c_int, [c_void_p, POINTER(c_double)]),
+    "hb_multi_set_fp16_centre": (c_int, [c_void_p, c_int]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -136,7 +143,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

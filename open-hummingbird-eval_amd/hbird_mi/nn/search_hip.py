@@ -51,6 +51,7 @@ class HipFlatIndex:
     def __init__(self, d: int, metric: int, device: int):
         self._h = ctypes.c_void_p()
         self.d, self.metric, self.device = int(d), int(metric), int(device)
+        self._fp16_centre = False
         L = _lib.lib()
         rc = L.hb_index_create(self.d, self.metric, self.device, ctypes.byref(self._h))
         if rc != 0:
@@ -330,7 +331,25 @@ class HipFlatIndex:
         """What served the last search (hb_last_search_path): the fp32 kernel, the fp16 chain or one wide fp16 pass, and why (HB_WHY_*)."""
         path, why = ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(_lib.lib().hb_last_search_path(self._h, ctypes.byref(path), ctypes.byref(why)))
-        return {"path": self.SEARCH_PATHS[path.value], "reason": self.SEARCH_REASONS[why.value]}
+        out = {"path": self.SEARCH_PATHS[path.value], "reason": self.SEARCH_REASONS[why.value]}
+        if self._fp16_centre:                 # (the field exists while centring is switched on: an index left alone reports what it always did)
+            out["centred"] = self.fp16_centre_info()["last_search_centred"]
+        return out
+
+    def set_fp16_centre(self, on: bool = True):
+        """The fp16 candidate copy in its mean-centred form (hb_index_set_fp16_centre, include/hbird_hip_centre.h): the pass runs on q - t mu and
+        b - mu, so the certificate's bound scales with the centred norms -- banks with massive activations certify at the first pass.  Same results
+        (the fp32 search's bits) on or off; off on a new index.  A change drops the fp16 copy, the next screened search rebuilds it."""
+        _lib.check(_lib.lib().hb_index_set_fp16_centre(self._h, int(bool(on))))
+        self._fp16_centre = bool(on)
+
+    def fp16_centre_info(self) -> dict:
+        """hb_index_fp16_centre_info: centred (the copy holds centred rows), mu_norm, cmax = max ||b - mu||, bmax = max ||b||, t of the last centred
+        search, rows converted with mu, the setting, and whether the last search ran centred."""
+        out = (ctypes.c_double * 8)()
+        _lib.check(_lib.lib().hb_index_fp16_centre_info(self._h, out))
+        return {"centred": bool(out[0]), "mu_norm": float(out[1]), "cmax": float(out[2]), "bmax": float(out[3]), "t": float(out[4]),
+                "rows": int(out[5]), "setting": bool(out[6]), "last_search_centred": bool(out[7])}
 
     def last_fp16_fallbacks(self) -> int:
         n = ctypes.c_int64(0)
@@ -545,6 +564,14 @@ class HipMultiIndex:
     def set_rerank_copy(self, mode: int = 0):
         for ix in self.indexes:
             ix.set_rerank_copy(mode)
+
+    def set_fp16_centre(self, on: bool = True):
+        """HipFlatIndex.set_fp16_centre on every shard / replica: each derives the mean of its own rows (the merged lists are the same bits)."""
+        for ix in self.indexes:
+            ix.set_fp16_centre(on)
+
+    def fp16_centre_info(self) -> list:
+        return [ix.fp16_centre_info() for ix in self.indexes]
 
     def last_fp16_fallbacks(self) -> int:
         return self._fallbacks
@@ -863,6 +890,7 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
         self.idx_shard = idx_shard
         self.use_fp16 = use_fp16
         self.exact_screen = bool(kwargs.pop("exact_screen", True))     # use_fp16=False: the index's automatic state (True) or the fp32 kernel only (False)
+        self.fp16_centre = bool(kwargs.pop("fp16_centre", False))     # the fp16 copy in its mean-centred form (set_fp16_centre): same results, a tighter certificate on ViT-shaped banks
         self.rerank_copy = int(kwargs.pop("rerank_copy", 0))     # use_fp16 only: the re-rank's row-major copy of the bank (0 automatic, 1 always, 2 never)
         self.embed_d = feature_memory.size(1)
 
@@ -905,6 +933,8 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
         for index in out:
             index.set_fp16(2 if self.use_fp16 else "auto" if self.exact_screen else 0)  # search_faiss.py:40; only where it pays
             index.set_rerank_copy(self.rerank_copy)
+            if self.fp16_centre:
+                index.set_fp16_centre(True)
         return out
 
     def _add_features_to_index(self, feature_memory):
