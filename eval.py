@@ -50,6 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--nn-method", choices=["hip", "faiss", "scann"], default="hip")
     p.add_argument("--nn-param", action="append", default=[], metavar="KEY=VALUE")
     p.add_argument("--memory-size", type=int, default=None)
+    p.add_argument("--memory-sizes", type=_positive_int, nargs="+", default=None, metavar="N",
+                   help="memory-size sweep out of ONE bank build (not in the reference): the bank is built at --memory-size, every listed "
+                        "size up to it is evaluated on a view of that bank; the result JSON then also carries miou_by_memory_size")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -157,10 +160,18 @@ def main(argv: Optional[List[str]] = None) -> None:
                               num_workers=args.num_workers, ignore_index=args.ignore_index,
                               train_fs_path=args.train_fs_path, val_fs_path=args.val_fs_path,
                               frame_size=tuple(args.frame_size) if args.frame_size else None,
-                              window_stride=args.window_stride, f_mem_p=args.f_mem_p, l_mem_p=args.l_mem_p)
+                              window_stride=args.window_stride, f_mem_p=args.f_mem_p, l_mem_p=args.l_mem_p,
+                              **({"memory_sizes": args.memory_sizes} if args.memory_sizes else {}))
     from hbird_mi import hbird_eval as _he
+    by_size = None
+    if args.memory_sizes:
+        by_size = {str(k): float(v) for k, v in result.items()}
+        # the headline figure: the built bank's own size when it was listed, else the largest listed one
+        result = result[args.memory_size] if args.memory_size in result else result[max(result)] if result else float("nan")
     summary = {"miou": float(result), "seconds": round(time.time() - t0, 3), "nn_method": args.nn_method,
                "dataset": args.dataset_name, "n_neighbours": args.n_neighbours, **_he.last_run_info}
+    if by_size is not None:
+        summary["miou_by_memory_size"] = by_size
     print(json.dumps(summary))
     if args.out:
         with open(args.out, "w") as f:

@@ -102,6 +102,8 @@ int hb_index_reconstruct(hb_index_t* ix, const int64_t* ids, int64_t n, int64_t 
 int hb_index_gather_labels(hb_index_t* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out,
                            int io_on_device);
 
+/* Sub-bank views -- hb_index_add_from, hb_index_select_rows: an index out of selected rows of another one, gathered on the device -- are
+ * declared in hbird_hip_select.h, which this header includes at its end. */
 /* Multi-GPU aggregation tables: borrow device arrays labels[n, c] / norms[n] that cover the GLOBAL id range
  * [id_base, id_base + n) (the all-gathered label_memory and bank-row norms); NULL restores the index's own
  * tables.  hb_index_copy_norms exports this shard's row norms (ntotal floats) for that all-gather. */
@@ -412,6 +414,7 @@ int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, i
                             int* segs_out, int64_t max_segs, int64_t stats[8]);
 
 #include "hbird_hip_centre.h"
+#include "hbird_hip_select.h"
 
 #ifdef __cplusplus
 }

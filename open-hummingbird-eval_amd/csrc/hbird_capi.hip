@@ -475,14 +475,11 @@ int hb_labels_checked(hb_index* ix) {
     return 0;
 }
 
-extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t n, int c, int on_device) {
-    if (!ix) return hb_fail("hb_index_add_labels: NULL index handle");
-    if (n < 0 || c <= 0) return hb_fail("hb_index_add_labels: bad shape");
-    if (n == 0) return 0;
-    HB_HIP(hipSetDevice(ix->device));
-    if (ix->c != 0 && ix->c != c && ix->nlabels > 0) return hb_fail("hb_index_add_labels: class count changed");
+// The label table of `ix` for rows of c classes, with room for n more rows (hb_index_add_labels, hb_index_add_from): a table of another
+// width goes (an emptied index -- hb_index_reset keeps allocations -- takes rows of another width: `lab_cap` counts rows of the OLD width),
+// capacity follows the bank's, else grows x 1.5.  Sets ix->c.
+int hb_labels_ensure(hb_index* ix, int c, int64_t n) {
     if (ix->c != c && ix->lab_cap > 0) {
-        // an emptied index (hb_index_reset keeps allocations) takes rows of another width: `lab_cap` counts rows of the OLD width
         HB_HIP(hipStreamSynchronize(ix->stream));
         if (ix->labels) HB_HIP(hipFree(ix->labels));
         if (ix->labels16) HB_HIP(hipFree(ix->labels16));
@@ -502,6 +499,17 @@ extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t 
         if (ix->label_P) ix->labels16 = (uint16_t*)nl; else ix->labels = (float*)nl;
         ix->lab_cap = cap;
     }
+    return 0;
+}
+
+extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t n, int c, int on_device) {
+    if (!ix) return hb_fail("hb_index_add_labels: NULL index handle");
+    if (n < 0 || c <= 0) return hb_fail("hb_index_add_labels: bad shape");
+    if (n == 0) return 0;
+    HB_HIP(hipSetDevice(ix->device));
+    if (ix->c != 0 && ix->c != c && ix->nlabels > 0) return hb_fail("hb_index_add_labels: class count changed");
+    if (hb_labels_ensure(ix, c, n)) return -1;
+    const size_t ls = (size_t)ix->lab_stride();  // elements per stored row (counts: padded to 16 bytes)
     if (ix->label_P) {
         // values j / P (what K2 produces, hbird_eval.py:319-320) stored as the uint16 count j: half the table, the same fp32 value back
         if (!ix->lab_flag) { HB_HIP(hipMalloc((void**)&ix->lab_flag, 4)); HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, ix->stream)); }

@@ -162,6 +162,7 @@ int hb_knn_f16_launch(const knn16_args& args, int grid, hipStream_t s);
 // label storage: fp32 values, or uint16 counts of values j / P (exactly the fp32 value: K2 computes (float)j / (float)P)
 int hb_launch_labels_to_counts(const float* src, int64_t rows, int c, int dst_stride, int P, uint16_t* dst, int* flag, hipStream_t s);
 int hb_launch_gather_label_counts(const uint16_t* src, int64_t src_rows, int c, int src_stride, int P, const int64_t* ids, int64_t n, float* out, hipStream_t s);
+int hb_labels_ensure(hb_index* ix, int c, int64_t n);   // the label table for rows of c classes with room for n more rows (sets ix->c)
 int hb_labels_checked(hb_index* ix);   // 0, or fails when a stored label was not a multiple of 1 / label_P
 int hb_launch_aggregate(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq,
                         int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);

@@ -122,6 +122,12 @@ SIGNATURES_CENTRE = {
     "hb_multi_set_fp16_centre": (c_int, [c_void_p, c_int]),
 }
 
+# ... and include/hbird_hip_select.h (sub-bank views, csrc/hbird_select.hip: rows of one index gathered into another on the device)
+SIGNATURES_SELECT = {
+    "hb_index_add_from": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "hb_index_select_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_void_p)]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -143,7 +149,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

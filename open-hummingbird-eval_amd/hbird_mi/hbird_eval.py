@@ -25,6 +25,7 @@ import torch
 from hbird_mi import dist as hdist
 from hbird_mi import ops
 from hbird_mi import tiling
+from hbird_mi import views
 from hbird_mi.models import FeatureExtractor, FeatureExtractorSimple
 from hbird_mi.nn.search_hip import HipFlatIndex, HipMultiIndex, check_k, k5, merge_topk, merge_topk_packed, _METRICS
 from hbird_mi.utils.eval_metrics import PredsmIoU
@@ -91,6 +92,11 @@ class HbirdEvaluation:
         self.f_mem_p = f_mem_p
         self.l_mem_p = l_mem_p
         self.num_sampled_features: Optional[int] = None
+        # geometry of a bank built here (memory_view): cumulative row offsets of the (epoch, image) blocks in build order, images per epoch
+        # (rows kept per block by the bounded build: num_sampled_features).  A loaded bank has none.
+        self._bank_block_starts: Optional[List[int]] = None
+        self._dataset_images: Optional[int] = None
+        self._dataset_size = dataset_size
         self.rank, self.world = hdist.rank_world()
 
         distance = str(nn_params.get("distance_measure", "dot_product")).lower()
@@ -205,6 +211,7 @@ class HbirdEvaluation:
         self.index.set_num_classes(num_classes)
         self.id_base, self.total_rows, self._label_table = 0, index.ntotal, None
         self.bank_loaded, self.bank_build_s, self.batches_loaded = True, 0.0, 0
+        self._bank_block_starts = self._dataset_images = self._dataset_size = None      # no build geometry (memory_view: rows_per_image=)
         return self
 
     def _align_cpu_rng(self) -> None:
@@ -240,6 +247,7 @@ class HbirdEvaluation:
         need_all = self.memory_size is not None or not self.sharded
         self.batches_loaded = 0
         self._mixed_patch_sizes = False
+        self._bank_block_starts = [0]
         failure = None
         with torch.no_grad():
             for ep in tqdm(range(self.augmentation_epoch), desc="Augmentation loop"):
@@ -261,6 +269,8 @@ class HbirdEvaluation:
                 elif failure is not None:
                     raise failure
         self.id_base = 0          # a sharded build learns its id base from the ranks' row counts (_finalize_shards)
+        n_blocks = len(self._bank_block_starts) - 1
+        self._dataset_images = n_blocks // max(1, self.augmentation_epoch)
         return self.index.ntotal
 
     def _create_memory_epoch(self, batches, base, n_batches, own_lo, own_hi, total_flat, num_classes, S, state) -> None:
@@ -298,6 +308,7 @@ class HbirdEvaluation:
                 self.index.use_current_stream()
                 self.index.add(feats.reshape(-1, feats.shape[-1]), normalize=True)   # K1 (324-329)
                 self.index.add_labels(label.reshape(-1, num_classes))
+                self._record_blocks(feats.shape[0], feats.shape[1])
             else:
                 K = int(self.num_sampled_features)
                 lab = label.reshape(bs, S * S, num_classes)
@@ -318,7 +329,13 @@ class HbirdEvaluation:
                 self.index.use_current_stream()
                 self.index.add(sampled, normalize=True)                                # 335, 352-353
                 self.index.add_labels(ops.gather_rows(lab.reshape(-1, num_classes), rows))   # 344-354
+                self._record_blocks(bs, K)
         state["presized"] = presized
+
+    def _record_blocks(self, images: int, rows_each: int) -> None:
+        """Build geometry: `images` more (epoch, image) blocks of `rows_each` rows were appended (S x S unbounded, K bounded)."""
+        last = self._bank_block_starts[-1]
+        self._bank_block_starts.extend(last + rows_each * (i + 1) for i in range(images))
 
     def _set_label_denominator(self, P: int) -> None:
         """Every soft label is j / P, P = patch_size ** 2 (the mean of a one-hot over a patch's P pixels, hbird_eval.py:319-320): the
@@ -524,6 +541,100 @@ class HbirdEvaluation:
                                "saved as ONE reference-format file pair now (INTEGRATION.md); rebuilding", p)
         logger.warning("Memory files not found or paths not provided; skipping load.")
         return False
+
+    # ------------------------------------------------------------------------------------------------
+    # sub-bank views: the bank of a smaller memory size / of an image subset out of this one, without a ViT pass (hbird_mi/views.py)
+    # ------------------------------------------------------------------------------------------------
+    def _view_geometry(self, memory_size, images, rows_per_image):
+        """(row ids, block starts, images per epoch, rows per image or None, dataset_size) of the view `memory_size=` / `images=` select out
+        of this bank's (epoch, image) blocks; ValueError where the bank has no such view."""
+        n_total = self.index.ntotal
+        aug = max(1, int(self.augmentation_epoch))
+        starts = self._bank_block_starts
+        bounded = self.memory_size is not None and self.num_sampled_features is not None
+        built_k = int(self.num_sampled_features) if bounded else None
+        if rows_per_image is not None:
+            rpi = int(rows_per_image)
+            if rpi < 1 or n_total % rpi != 0 or (n_total // rpi) % aug != 0:
+                raise ValueError(f"memory_view: {n_total} rows are not {aug} epoch(s) of whole images of rows_per_image={rows_per_image} rows")
+            starts = list(range(0, n_total + 1, rpi))
+            built_k = rpi if self.memory_size is not None else None
+        if starts is None:
+            raise ValueError("memory_view: this bank was not built here (loaded, or from_index): it has no geometry -- pass rows_per_image= or rows=")
+        n_images = (len(starts) - 1) // aug
+        blocks, dataset_size = None, self._dataset_size
+        if images is not None:
+            img = [int(i) for i in (images.tolist() if isinstance(images, torch.Tensor) else images)]
+            if any(i < 0 or i >= n_images for i in img):
+                raise ValueError(f"memory_view: an image index lies outside [0, {n_images})")
+            blocks = [ep * n_images + i for ep in range(aug) for i in img]
+            n_images = dataset_size = len(img)
+        per_block = None
+        if memory_size is not None:
+            if built_k is None:
+                raise ValueError("memory_view: memory_size= needs a bank built bounded (with memory_size set): a bounded bank keeps the patches "
+                                 "with the smallest noisy scores of every image -- out of an unbounded bank it would have been SAMPLED, not truncated")
+            per_block = views.per_image_rows(int(memory_size), dataset_size if dataset_size is not None else n_images, aug)
+            if per_block > built_k:
+                raise ValueError(f"memory_view: memory_size={memory_size} keeps {per_block} rows per image, the bank was built with {built_k}")
+        ids = views.view_rows(starts, per_block=per_block, blocks=blocks)      # (a block listed twice: ValueError)
+        st = torch.as_tensor(starts, dtype=torch.int64)
+        lens = st[1:] - st[:-1]
+        if blocks is not None:
+            lens = lens[torch.as_tensor(sorted(blocks), dtype=torch.int64)]
+        if per_block is not None:
+            lens = lens.clamp(max=per_block)
+        return ids, [0] + torch.cumsum(lens, 0).tolist(), n_images, (per_block if per_block is not None else built_k), dataset_size
+
+    def memory_view(self, memory_size: Optional[int] = None, images=None, rows=None, rows_per_image: Optional[int] = None,
+                    n_neighbours: Optional[int] = None) -> "HbirdEvaluation":
+        """A new evaluator over selected rows of this bank: same extractor, its index is `self.index.select_rows(...)` (a device gather, 1 x the
+        view's rows of memory), made the `from_index` way; nn_params' use_fp16 / rerank_copy / fp16_centre carry over.  Not in the reference, whose
+        memory-size table and data-efficiency file sets cost one bank build per point.
+
+        `rows=`            any row list; works on every single-index evaluator; the view has no geometry.
+        `memory_size=`     only on a bank built BOUNDED: the bounded build keeps per (epoch, image) the K patches with the smallest noisy scores in
+                           ascending order (hbird_eval.py:146-147, 497-511) and the noise does not depend on K, so the bank of a smaller
+                           memory_size is the first K_m rows of every block -- bit for bit what a build from scratch gives.  K_m =
+                           views.per_image_rows(memory_size, dataset_size, augmentation_epoch); ValueError when it exceeds the built K.  An
+                           UNBOUNDED bank has no such prefix: a bounded bank of it would have been sampled, not truncated -- ValueError.
+        `images=`          image indices in loader order, taken in every epoch (the view keeps the build's row order).  Combined with
+                           `memory_size=` the per-image ROW COUNT follows the subset (dataset_size = len(images)); the rows are still the ones
+                           the full build's noise chose -- a bounded build on the subset alone draws other noise and samples other patches.
+        `rows_per_image=`  the geometry of a loaded or `from_index` bank (equal blocks; the row count must divide evenly).
+        The view gets a geometry of its own, so views of views work.  ValueError under torch.distributed and with several GPUs in one process."""
+        if self.world > 1 or self.sharded or len(self.local_gpus) > 1 or not isinstance(self.index, HipFlatIndex):
+            raise ValueError("memory_view: views are single-index -- not available under torch.distributed or with several GPUs in one process")
+        starts_new = images_new = k_new = dataset_size_new = None
+        if rows is not None:
+            if memory_size is not None or images is not None or rows_per_image is not None:
+                raise ValueError("memory_view: rows= stands alone (no memory_size / images / rows_per_image beside it)")
+            ids = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(list(rows), dtype=torch.int64)
+        elif memory_size is None and images is None:
+            raise ValueError("memory_view: one of memory_size=, images= or rows= is needed")
+        else:
+            ids, starts_new, images_new, k_new, dataset_size_new = self._view_geometry(memory_size, images, rows_per_image)
+        with torch.cuda.device(self.gpu_device):
+            self.index.use_current_stream()
+            index = self.index.select_rows(ids)
+            index.use_current_stream()
+        view = HbirdEvaluation.from_index(self.feature_extractor, index, self.num_classes,
+                                          n_neighbours=self.n_neighbours if n_neighbours is None else n_neighbours, device=self.device)
+        view.nn_method = self.nn_method
+        view.nn_params = {k: self.nn_params[k] for k in ("distance_measure", "use_fp16", "rerank_copy", "fp16_centre") if k in self.nn_params}
+        if view.nn_params.get("use_fp16", False):
+            index.set_fp16(2)
+            index.set_rerank_copy(int(view.nn_params.get("rerank_copy", 0)))
+        if view.nn_params.get("fp16_centre", False):
+            index.set_fp16_centre(True)
+        view.augmentation_epoch = self.augmentation_epoch
+        view.compress_labels = self.compress_labels
+        view.memory_size = memory_size if memory_size is not None else self.memory_size
+        view.num_sampled_features = k_new
+        view._bank_block_starts, view._dataset_images = starts_new, images_new
+        view._dataset_size = dataset_size_new
+        view.bank_loaded = False
+        return view
 
     # ------------------------------------------------------------------------------------------------
     # query path (reference evaluate 184-265, _find_nearest_key_to_query 611-637, _cross_attention 575-609)
@@ -811,7 +922,7 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      memory_size: Optional[int] = None, num_workers: int = 8, ignore_index: int = 255,
                      train_fs_path: Optional[str] = None, val_fs_path: Optional[str] = None,
                      frame_size: Optional[Tuple[int, int]] = None, window_stride: Optional[int] = None,
-                     f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None):
+                     f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -819,7 +930,12 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     bank build from the window crops, evaluation stitched over the windows (BASELINE cfg-5, hbird_mi/tiling.py).
     `f_mem_p` / `l_mem_p`: the bank's file pair (the constructor arguments the reference never passes, hbird_eval.py:701-712):
     a first run builds the bank and saves it there, a later run with both files present loads it and skips the build --
-    one bank reused across runs, for any number of ranks."""
+    one bank reused across runs, for any number of ranks.
+    `memory_sizes=[...]` (a fifth one): the memory-size sweep of the reference's mIoU table out of ONE bank build -- the bank is built at
+    `memory_size`, every listed size <= memory_size is evaluated on a view of it (`HbirdEvaluation.memory_view`: the rows a build at that
+    size would hold, bit for bit), and the call returns {size: what the call returns for that size alone}."""
+    if memory_sizes is not None and memory_size is None:
+        raise ValueError("memory_sizes needs memory_size: the bank is built once, at memory_size, and the listed sizes are views of it")
     if nn_params is None:
         nn_params = {}
     eval_spatial_resolution = input_size // patch_size                                   # 671
@@ -854,5 +970,19 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     last_run_info.clear()
     last_run_info.update(bank_loaded=bool(evaluator.bank_loaded), bank_build_s=float(evaluator.bank_build_s),
                          bank_rows=int(evaluator.total_rows), train_batches_loaded=int(evaluator.batches_loaded))
-    return evaluator.evaluate(val_loader, eval_spatial_resolution=eval_spatial_resolution,
-                              return_knn_details=return_knn_details, ignore_index=effective_ignore, window=window)
+    if memory_sizes is None:
+        return evaluator.evaluate(val_loader, eval_spatial_resolution=eval_spatial_resolution,
+                                  return_knn_details=return_knn_details, ignore_index=effective_ignore, window=window)
+    results = {}
+    for size in memory_sizes:
+        size = int(size)
+        if size > memory_size or size in results:
+            continue
+        # (a bank loaded from its file pair has no recorded geometry: its blocks are the K rows per image this memory_size keeps)
+        ev = evaluator if size == memory_size else evaluator.memory_view(
+            memory_size=size, rows_per_image=evaluator.num_sampled_features if evaluator.bank_loaded else None)
+        results[size] = ev.evaluate(val_loader, eval_spatial_resolution=eval_spatial_resolution,
+                                    return_knn_details=return_knn_details, ignore_index=effective_ignore, window=window)
+        if ev is not evaluator:
+            ev.index.close()
+    return results

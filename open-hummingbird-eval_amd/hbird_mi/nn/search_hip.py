@@ -248,6 +248,46 @@ class HipFlatIndex:
         _lib.check(_lib.lib().hb_index_gather_labels(self._h, _ptr(ids), n, 0, _ptr(out), int(on_dev)))
         return out
 
+    # sub-bank views (hb_index_add_from / hb_index_select_rows, csrc/hbird_select.hip): rows of one index gathered into another on the device
+    def _ids64(self, ids):
+        """ids -> (on_device, contiguous int64 tensor [n]); integer ids only (a float or bool array is refused, not truncated); a CUDA
+        tensor must live on this index's GPU."""
+        if not isinstance(ids, torch.Tensor):
+            arr = np.asarray(ids)
+            if arr.size and not np.issubdtype(arr.dtype, np.integer):
+                raise ValueError(f"row ids must be integers, got {arr.dtype}")
+            return False, torch.from_numpy(np.ascontiguousarray(arr.reshape(-1), dtype=np.int64))
+        if ids.numel() and (ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool):
+            raise ValueError(f"row ids must be integers, got {ids.dtype}")
+        ids = ids.detach().reshape(-1).to(torch.int64).contiguous()
+        if ids.is_cuda and ids.device.index != self.device:
+            raise ValueError("ids live on another GPU than the index")
+        return ids.is_cuda, ids
+
+    def add_from(self, src: "HipFlatIndex", ids):
+        """Append rows `ids` (host or device int64 tensor; any order, duplicates allowed) of `src` to this index, tile to tile: tiles, norms and
+        the L2 row constants verbatim, label rows in their stored form when `src` holds them.  ValueError for an id outside `src`, for
+        `src is self`, and for indexes that differ in width, metric, device, class count or label denominator -- the index is then unchanged."""
+        if not isinstance(src, HipFlatIndex):
+            raise ValueError("add_from: views are single-index (the source must be a HipFlatIndex)")
+        on_dev, ids = self._ids64(ids)
+        _lib.check(_lib.lib().hb_index_add_from(self._h, src._h, _ptr(ids), ids.numel(), int(on_dev)), ValueError)
+        if hasattr(src, "_c") and ids.numel() and int(_lib.lib().hb_index_nlabels(src._h)) > 0:
+            self._c = src._c           # label rows came along: the destination's class count is the source's (an emptied one adopted it)
+
+    def select_rows(self, ids) -> "HipFlatIndex":
+        """A NEW index holding rows `ids` of this one (hb_index_select_rows): 1 x its rows of memory, label rows included; its fp16 state,
+        calibration and workspace are its own (a new index's).  ValueError for an id outside this index."""
+        on_dev, ids = self._ids64(ids)
+        view = HipFlatIndex.__new__(HipFlatIndex)
+        view._h = ctypes.c_void_p()
+        view.d, view.metric, view.device = self.d, self.metric, self.device
+        view._fp16_centre = False
+        _lib.check(_lib.lib().hb_index_select_rows(self._h, _ptr(ids), ids.numel(), int(on_dev), ctypes.byref(view._h)), ValueError)
+        if hasattr(self, "_c"):
+            view._c = self._c
+        return view
+
     def copy_norms(self) -> torch.Tensor:
         """L2 norms of this shard's stored rows (CUDA tensor [ntotal])."""
         out = torch.empty((self.ntotal,), dtype=torch.float32, device=torch.device("cuda", self.device))
@@ -861,6 +901,9 @@ class HipMultiIndex:
 
     def set_label_table(self, labels, norms, id_base: int = 0):
         raise RuntimeError("HipMultiIndex keeps its own label table on the home device")
+
+    def select_rows(self, ids):
+        raise ValueError("HipMultiIndex.select_rows: views are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")
 
 
 class NearestNeighborSearchHIP(NearestNeighborSearchBase):
