@@ -30,6 +30,18 @@ def _positive_int(v: str) -> int:
     return i
 
 
+def _positive_float(v: str) -> float:
+    f = float(v)
+    if not (f > 0 and f != float("inf")):
+        raise argparse.ArgumentTypeError("must be a finite positive number")
+    return f
+
+
+def grid_key(k: int, beta: float) -> str:
+    """How a configuration of --grid-k / --grid-beta is keyed in the result JSON."""
+    return f"k={int(k)},beta={float(beta)!r}"
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Hummingbird retrieval evaluation on MI355X (hbird_mi.hbird_evaluation).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -53,6 +65,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--memory-sizes", type=_positive_int, nargs="+", default=None, metavar="N",
                    help="memory-size sweep out of ONE bank build (not in the reference): the bank is built at --memory-size, every listed "
                         "size up to it is evaluated on a view of that bank; the result JSON then also carries miou_by_memory_size")
+    p.add_argument("--grid-k", type=_positive_int, nargs="+", default=None, metavar="N",
+                   help="sweep over n_neighbours out of ONE validation pass with one search per batch (not in the reference); the result JSON "
+                        "then carries miou_grid, keyed 'k=30,beta=0.02' (with --memory-sizes: miou_grid_by_memory_size)")
+    p.add_argument("--grid-beta", type=_positive_float, nargs="+", default=None, metavar="B",
+                   help="sweep over the softmax temperature of the label aggregation (0.02 in the reference), see --grid-k")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -161,9 +178,19 @@ def main(argv: Optional[List[str]] = None) -> None:
                               train_fs_path=args.train_fs_path, val_fs_path=args.val_fs_path,
                               frame_size=tuple(args.frame_size) if args.frame_size else None,
                               window_stride=args.window_stride, f_mem_p=args.f_mem_p, l_mem_p=args.l_mem_p,
-                              **({"memory_sizes": args.memory_sizes} if args.memory_sizes else {}))
+                              **({"memory_sizes": args.memory_sizes} if args.memory_sizes else {}),
+                              **({"grid_k": args.grid_k, "grid_beta": args.grid_beta} if args.grid_k or args.grid_beta else {}))
     from hbird_mi import hbird_eval as _he
-    by_size = None
+    by_size = grid = grid_by_size = None
+    if args.grid_k or args.grid_beta:
+        def headline(res):      # the configuration the plain run evaluates when the grid holds it, else the grid's first
+            return res.get((args.n_neighbours, 0.02), next(iter(res.values()))) if res else float("nan")
+        if args.memory_sizes:
+            grid_by_size = {str(size): {grid_key(k, b): float(v) for (k, b), v in res.items()} for size, res in result.items()}
+            result = {size: headline(res) for size, res in result.items()}
+        else:
+            grid = {grid_key(k, b): float(v) for (k, b), v in result.items()}
+            result = headline(result)
     if args.memory_sizes:
         by_size = {str(k): float(v) for k, v in result.items()}
         # the headline figure: the built bank's own size when it was listed, else the largest listed one
@@ -172,6 +199,10 @@ def main(argv: Optional[List[str]] = None) -> None:
                "dataset": args.dataset_name, "n_neighbours": args.n_neighbours, **_he.last_run_info}
     if by_size is not None:
         summary["miou_by_memory_size"] = by_size
+    if grid is not None:
+        summary["miou_grid"] = grid
+    if grid_by_size is not None:
+        summary["miou_grid_by_memory_size"] = grid_by_size
     print(json.dumps(summary))
     if args.out:
         with open(args.out, "w") as f:

@@ -534,8 +534,9 @@ extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t 
 static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta, float* out_lab,
-                       int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate, bool bigk = false) {
+                       int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate, bool bigk = false, const hb_grid_spec* grid = nullptr) {
     // bigk: the aggregation is hbird_bigk.hip's K5 (hb_bigk_search_aggregate), whose k goes as far as the search's
+    // grid: the aggregation is hbird_grid.hip's, over the grid's configurations (k is its largest; out_lab holds one [nq, c] slab each)
     if (nq < 0) return hb_fail("hb_index_search: negative query count");
     if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search: k must be in [1, " + std::to_string(HB_MAX_K) + "] (faiss-gpu's own limit)");
     if (aggregate && !bigk && k > HB_MAX_K_AGGREGATE)
@@ -550,7 +551,8 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     // staging area in ix->tmp: [queries (host path)] [idx] [dist] [label_hat (host path)]
     const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4);
     const size_t b_idx = al256((size_t)nq * k * 8), b_dist = al256((size_t)nq * k * 4);
-    const size_t b_lab = (aggregate && !io_on_device) ? al256((size_t)nq * ix->c * 4) : 0;
+    const size_t lab_bytes = (size_t)nq * ix->c * 4 * (grid ? (size_t)grid->nk * grid->nb : 1);
+    const size_t b_lab = (aggregate && !io_on_device) ? al256(lab_bytes) : 0;
     const bool t_idx = !io_on_device || !out_idx, t_dist = !io_on_device || !out_dist;
     const size_t need = b_q + (t_idx ? b_idx : 0) + (t_dist ? b_dist : 0) + b_lab;
     if (need && grow((void**)&ix->tmp, &ix->tmp_bytes, need)) return -1;
@@ -578,12 +580,14 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     }
     if (aggregate) {
         hb_range r("hbird:aggregate");
-        if ((bigk ? hb_launch_aggregate_bigk : hb_launch_aggregate)(ix, ix->q_aux + nq, d_idx, d_dist, nq, k, id_base, beta, d_lab, ix->stream, nullptr, 0)) return -1;
+        if (grid) {
+            if (hb_launch_aggregate_grid(ix, ix->q_aux + nq, d_idx, d_dist, nq, k, id_base, *grid, d_lab, ix->stream)) return -1;
+        } else if ((bigk ? hb_launch_aggregate_bigk : hb_launch_aggregate)(ix, ix->q_aux + nq, d_idx, d_dist, nq, k, id_base, beta, d_lab, ix->stream, nullptr, 0)) return -1;
     }
     if (!io_on_device) {
         if (out_idx) HB_HIP(hipMemcpyAsync(out_idx, d_idx, (size_t)nq * k * 8, hipMemcpyDeviceToHost, ix->stream));
         if (out_dist) HB_HIP(hipMemcpyAsync(out_dist, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ix->stream));
-        if (aggregate) HB_HIP(hipMemcpyAsync(out_lab, d_lab, (size_t)nq * ix->c * 4, hipMemcpyDeviceToHost, ix->stream));
+        if (aggregate) HB_HIP(hipMemcpyAsync(out_lab, d_lab, lab_bytes, hipMemcpyDeviceToHost, ix->stream));
         HB_HIP(hipStreamSynchronize(ix->stream));
     }
     return 0;
@@ -621,6 +625,43 @@ extern "C" int hb_index_aggregate(hb_index_t* ix, const float* q, int64_t nq, co
     if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
     if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
     return hb_launch_aggregate(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_label_hat, ix->stream);
+}
+
+// ---- evaluation grids (hbird_grid.hip, include/hbird_hip_grid.h): every (k, beta) of a grid from one list per query.  Everything is
+// checked before the first launch: a failing call leaves no half-written output behind.
+static bool grid_labels_missing(const hb_index* ix) {
+    return !ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal);
+}
+
+extern "C" int hb_index_aggregate_grid(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k_list,
+                                       int64_t id_base, const int* ks, int nk, const float* betas, int nb, float* out, int io_on_device) {
+    if (!ix) return hb_fail("hb_index_aggregate_grid: NULL index handle");
+    if (nq < 0) return hb_fail("hb_index_aggregate_grid: nq is negative");
+    hb_grid_spec gs;
+    if (hb_grid_check("hb_index_aggregate_grid", ks, nk, betas, nb, k_list, &gs)) return -1;
+    if (grid_labels_missing(ix)) return hb_fail("hb_index_aggregate_grid: label rows missing (hb_index_add_labels)");
+    if (nq == 0) return 0;
+    if (!q || !idx || !dist || !out) return hb_fail("hb_index_aggregate_grid: NULL pointer");
+    if (!io_on_device) return hb_fail("hb_index_aggregate_grid: host pointers are not supported, pass device memory");
+    hb_range range("hbird:aggregate_grid");
+    HB_HIP(hipSetDevice(ix->device));
+    if (hb_labels_checked(ix)) return -1;
+    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
+    return hb_launch_aggregate_grid(ix, ix->q_aux + nq, idx, dist, nq, k_list, id_base, gs, out, ix->stream);
+}
+
+extern "C" int hb_index_search_aggregate_grid(hb_index_t* ix, const float* q, int64_t nq, int64_t id_base, const int* ks, int nk,
+                                              const float* betas, int nb, float* out, int64_t* out_idx_opt, float* out_dist_opt,
+                                              int io_on_device) {
+    if (!ix) return hb_fail("hb_index_search_aggregate_grid: NULL index handle");
+    hb_grid_spec gs;
+    if (hb_grid_check("hb_index_search_aggregate_grid", ks, nk, betas, nb, -1, &gs)) return -1;
+    if (nq > 0 && !out) return hb_fail("hb_index_search_aggregate_grid: out is NULL");
+    if (grid_labels_missing(ix)) return hb_fail("hb_index_search_aggregate_grid: label rows missing (hb_index_add_labels)");
+    if (hb_labels_checked(ix)) return -1;
+    // the search of hb_index_search_aggregate at the grid's largest k, then the grid's aggregation on its lists
+    return search_impl(ix, q, nq, gs.ks[nk - 1], id_base, 0.f, out, out_idx_opt, out_dist_opt, io_on_device, true, false, &gs);
 }
 
 extern "C" int hb_index_aggregate_partial(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,

@@ -173,6 +173,12 @@ int hb_launch_aggregate_bigk(const hb_index* ix, const float* qnorm, const int64
                              int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);
 int hb_launch_merge_sorted_parts(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
                                  int64_t dist_stride, int64_t idx_stride, int64_t* out_idx, float* out_dist, hipStream_t s);
+// a grid of (k, beta) configurations over one list per query (hbird_grid.hip): cfg = ik * nb + ib; hb_grid_check validates a caller's
+// arrays (k_list < 0: the list is a search's own, at ks[nk - 1]) and fills the spec the kernel takes by value
+struct hb_grid_spec { int ks[16]; float betas[16]; int nk, nb; };
+int hb_grid_check(const char* who, const int* ks, int nk, const float* betas, int nb, int k_list, hb_grid_spec* gs);
+int hb_launch_aggregate_grid(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq, int k_list,
+                             int64_t id_base, const hb_grid_spec& gs, float* out, hipStream_t s);
 int hb_launch_patch_label_hist(const int64_t* y, int64_t B, int H, int W, int ps, int C, int map255, float* out,
                                hipStream_t s);
 int hb_launch_normalize_rows(const float* x, int64_t n, int d, float* out, hipStream_t s);

@@ -128,6 +128,15 @@ SIGNATURES_SELECT = {
     "hb_index_select_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_void_p)]),
 }
 
+# ... and include/hbird_hip_grid.h (evaluation grids, csrc/hbird_grid.hip: every (k, beta) of a grid aggregated from one neighbour list per query)
+GRID_MAX_CONFIGS = 16      # HB_GRID_MAX_CONFIGS
+SIGNATURES_GRID = {
+    "hb_index_aggregate_grid": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, POINTER(c_int), c_int,
+                                        POINTER(c_float), c_int, c_void_p, c_int]),
+    "hb_index_search_aggregate_grid": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(c_int), c_int, POINTER(c_float), c_int,
+                                               c_void_p, c_void_p, c_void_p, c_int]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -149,7 +158,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

@@ -49,6 +49,14 @@ _NN_METHODS = ("hip", "faiss", "scann")
 last_run_info: Dict[str, Any] = {}
 
 
+def _check_beta(beta) -> float:
+    """The softmax temperature of the label aggregation: a finite positive number (K5 refuses anything else)."""
+    import math
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not (math.isfinite(beta) and beta > 0):
+        raise ValueError(f"beta={beta!r}: the softmax temperature must be a finite positive number")
+    return float(beta)
+
+
 class HbirdEvaluation:
     """Same constructor as the reference (hbird_eval.py:97-111).
 
@@ -62,13 +70,14 @@ class HbirdEvaluation:
     hbird_eval.py:165-172): when both `f_mem_p` and `l_mem_p` name existing files the bank is LOADED from them
     (`load_memory`) and the training loader is never touched; otherwise the bank is built and saved there as in the reference.
     `bank_loaded` / `bank_build_s` say which happened and how long it took.
+    `beta` (trailing keyword): the softmax temperature of the label aggregation, the reference's literal 0.02 (hbird_eval.py:575-609).
     """
 
     def __init__(self, feature_extractor: torch.nn.Module, train_loader, num_classes: int, n_neighbours: int = 30,
                  augmentation_epoch: int = 1, device: torch.device | str = "cpu", nn_method: str = "scann",
                  nn_params: Optional[Dict[str, Any]] = None, memory_size: Optional[int] = None,
                  dataset_size: Optional[int] = None, f_mem_p: Optional[str] = None,
-                 l_mem_p: Optional[str] = None, reuse_memory: bool = False) -> None:
+                 l_mem_p: Optional[str] = None, reuse_memory: bool = False, beta: float = 0.02) -> None:
         if nn_params is None:
             nn_params = {}
         self.nn_params = nn_params
@@ -88,6 +97,7 @@ class HbirdEvaluation:
         self.augmentation_epoch = augmentation_epoch
         self.memory_size = memory_size
         self.n_neighbours = n_neighbours
+        self.beta = _check_beta(beta)
         self.num_classes = num_classes
         self.f_mem_p = f_mem_p
         self.l_mem_p = l_mem_p
@@ -188,12 +198,13 @@ class HbirdEvaluation:
 
     @classmethod
     def from_index(cls, feature_extractor: torch.nn.Module, index, num_classes: int, n_neighbours: int = 30,
-                   device: torch.device | str = "cuda") -> "HbirdEvaluation":
+                   device: torch.device | str = "cuda", beta: float = 0.02) -> "HbirdEvaluation":
         """An evaluator over a bank that is already resident in a `HipFlatIndex` (rows + label rows added by the caller): `evaluate` runs
         as usual, nothing is built.  Not in the reference (its bank only ever comes from `_create_memory`); used by `bench.py --e2e` to time
         the evaluation loop against the synthetic 10 M-row bank, and handy for banks produced elsewhere."""
         check_k(n_neighbours, "n_neighbours")
         self = cls.__new__(cls)
+        self.beta = _check_beta(beta)
         self.nn_params, self.device, self.nn_method = {}, device, "hip"
         dev = torch.device(device)
         self.gpu = dev.index if dev.type == "cuda" and dev.index is not None else torch.cuda.current_device()
@@ -619,7 +630,8 @@ class HbirdEvaluation:
             index = self.index.select_rows(ids)
             index.use_current_stream()
         view = HbirdEvaluation.from_index(self.feature_extractor, index, self.num_classes,
-                                          n_neighbours=self.n_neighbours if n_neighbours is None else n_neighbours, device=self.device)
+                                          n_neighbours=self.n_neighbours if n_neighbours is None else n_neighbours, device=self.device,
+                                          beta=self.beta)
         view.nn_method = self.nn_method
         view.nn_params = {k: self.nn_params[k] for k in ("distance_measure", "use_fp16", "rerank_copy", "fp16_centre") if k in self.nn_params}
         if view.nn_params.get("use_fp16", False):
@@ -655,10 +667,10 @@ class HbirdEvaluation:
         k = self.n_neighbours
         self.index.use_current_stream()
         if not self.sharded and not want_details:
-            lh = k5(self.index, "search_aggregate", k)(q, k, beta=0.02, id_base=0)
+            lh = k5(self.index, "search_aggregate", k)(q, k, beta=self.beta, id_base=0)
             return lh.view(B, N, -1), None, None
         idx, dist = self.find_neighbours(q, k)
-        lh = k5(self.index, "aggregate", k)(q, idx, dist, beta=0.02, id_base=self.id_base)
+        lh = k5(self.index, "aggregate", k)(q, idx, dist, beta=self.beta, id_base=self.id_base)
         return lh.view(B, N, -1), idx, dist
 
     def _replicated_label_rows(self, ids: torch.Tensor) -> torch.Tensor:
@@ -735,6 +747,63 @@ class HbirdEvaluation:
             return jac, details
         logger.info("Evaluation complete.")
         return jac
+
+    def evaluate_grid(self, val_loader, eval_spatial_resolution: int, n_neighbours=None, betas=None, views=None, ignore_index: int = 255,
+                      window=None, return_knn_details: bool = False) -> Dict[tuple, float]:
+        """`evaluate` for every (k, beta) of a grid out of ONE pass over the loader (not in the reference, where every value of n_neighbours
+        or of the temperature costs a full evaluation).  Per batch the tokens are computed once and every bank is searched ONCE, at the largest
+        k: the engine's lists are the exact top-k under one total order with deterministic score bits, so the best k are the first k entries
+        of the best k_max and beta only enters after the search (`search_aggregate_grid`; DESIGN.md section 4, "Evaluation grids").  Every
+        configuration has its own metric object; its mIoU is what a separate `HbirdEvaluation(n_neighbours=k, beta=beta).evaluate(...)` returns.
+
+        `n_neighbours`, `betas`: a value or a list each (duplicates dropped, sorted); default: the evaluator's own n_neighbours / beta.
+        `views={key: HbirdEvaluation}`: the banks to evaluate -- evaluators that share this one's extractor, the `memory_view`s of one bank
+        (this evaluator itself may be among them); the batch's tokens serve every bank.  Without `views` the bank is this evaluator's.
+        -> {(k, beta): mIoU}, with `views` {(key, k, beta): mIoU}.
+        Single index or a HipMultiIndex in one process.  ValueError under torch.distributed, with `window=` and with `return_knn_details`."""
+        from hbird_mi.nn.search_hip import grid_plan
+        if window is not None:
+            raise ValueError("evaluate_grid: sliding windows (window=) are not supported; call evaluate per configuration")
+        if return_knn_details:
+            raise ValueError("evaluate_grid: return_knn_details is not supported; call evaluate per configuration")
+        banks = {None: self} if views is None else dict(views)
+        if not banks:
+            raise ValueError("evaluate_grid: views is empty")
+        for key, ev in banks.items():
+            if not isinstance(ev, HbirdEvaluation):
+                raise ValueError(f"evaluate_grid: views[{key!r}] is not an HbirdEvaluation")
+            if ev.world > 1 or ev.sharded:
+                raise ValueError("evaluate_grid: not available under torch.distributed (row shards or replicas): one index, or several GPUs "
+                                 "in one process")
+            if ev.num_classes != self.num_classes or ev.gpu_device != self.gpu_device:
+                raise ValueError(f"evaluate_grid: views[{key!r}] differs from this evaluator in class count or device")
+        if self.world > 1 or self.sharded:
+            raise ValueError("evaluate_grid: not available under torch.distributed (row shards or replicas): one index, or several GPUs in "
+                             "one process")
+        plan = grid_plan(self.n_neighbours if n_neighbours is None else n_neighbours, self.beta if betas is None else betas)
+        metrics = {key: [PredsmIoU(self.num_classes, self.num_classes, ignore_index=ignore_index, device=self.gpu_device,
+                                   store_reordered_preds=False) for _ in plan.configs] for key in banks}
+        self.feature_extractor = self.feature_extractor.to(self.device)
+        S = eval_spatial_resolution
+        logger.info("Starting grid evaluation loop: %d configurations, %d bank(s)...", len(plan.configs), len(banks))
+        with torch.no_grad(), torch.cuda.device(self.gpu_device):
+            for bi, (x, y) in tqdm(self._prefetched(enumerate(val_loader), True), desc="Grid evaluation loop"):
+                y = (y.to(self.gpu_device) * 255).long()
+                feats = self._tokens(x)
+                B, N, D = feats.shape
+                q = feats.reshape(B * N, D).contiguous()
+                for key, ev in banks.items():
+                    ev.index.use_current_stream()
+                    lh = ev.index.search_aggregate_grid(q, plan.ks, plan.betas, id_base=0)        # [configs, B * N, C]: one search
+                    for i, m in enumerate(metrics[key]):
+                        m.update_from_label_hat(y, lh[i].view(B, N, -1), S)
+        out = {}
+        for key in banks:
+            for (k, beta), m in zip(plan.configs, metrics[key]):
+                jac = m.compute(is_global_zero=True, sync_distributed=False, return_reordered=False)[0]
+                out[(k, beta) if views is None else (key, k, beta)] = jac
+        logger.info("Grid evaluation complete.")
+        return out
 
     # -- batch prefetch + stage timing of the evaluation loop ---------------------------------------------------------------------
     def _prefetched(self, batches, to_gpu: bool):
@@ -867,7 +936,7 @@ class HbirdEvaluation:
                 if self.label_shard:
                     # every rank: the weights of the full lists, the label sum over the neighbours it owns; the all-reduce completes it
                     self.index.use_current_stream()
-                    lh_all = k5(self.index, "aggregate_partial", k)(q_flat_all, idx, dist, self._label_table[1], beta=0.02, id_base=self.id_base)
+                    lh_all = k5(self.index, "aggregate_partial", k)(q_flat_all, idx, dist, self._label_table[1], beta=self.beta, id_base=self.id_base)
                     torch.distributed.all_reduce(lh_all)
                 kf_all, kl_all = None, None
                 if want_details:
@@ -893,7 +962,7 @@ class HbirdEvaluation:
                 if self.label_shard:
                     label_hat = lh_all[lo:lo + q.shape[0]].contiguous().view(B, N, -1)
                 else:
-                    label_hat = k5(self.index, "aggregate", k)(q.contiguous(), my_idx, my_dist, beta=0.02).view(B, N, -1)
+                    label_hat = k5(self.index, "aggregate", k)(q.contiguous(), my_idx, my_dist, beta=self.beta).view(B, N, -1)
                 if want_details:
                     kl = (kl_all[lo:lo + q.shape[0]].reshape(B, N, k, -1) if self.label_shard
                           else self._replicated_label_rows(my_idx.reshape(-1)).view(B, N, k, -1))
@@ -922,7 +991,8 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      memory_size: Optional[int] = None, num_workers: int = 8, ignore_index: int = 255,
                      train_fs_path: Optional[str] = None, val_fs_path: Optional[str] = None,
                      frame_size: Optional[Tuple[int, int]] = None, window_stride: Optional[int] = None,
-                     f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, memory_sizes=None):
+                     f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, grid_k=None, grid_beta=None,
+                     memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -933,7 +1003,11 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     one bank reused across runs, for any number of ranks.
     `memory_sizes=[...]` (a fifth one): the memory-size sweep of the reference's mIoU table out of ONE bank build -- the bank is built at
     `memory_size`, every listed size <= memory_size is evaluated on a view of it (`HbirdEvaluation.memory_view`: the rows a build at that
-    size would hold, bit for bit), and the call returns {size: what the call returns for that size alone}."""
+    size would hold, bit for bit), and the call returns {size: what the call returns for that size alone}.
+    `grid_k=[...]` / `grid_beta=[...]` (either or both; the other defaults to `n_neighbours` / 0.02): the sweep over n_neighbours and the softmax
+    temperature out of ONE validation pass with one search per batch (`HbirdEvaluation.evaluate_grid`); the call returns {(k, beta): mIoU},
+    combined with `memory_sizes` {size: {(k, beta): mIoU}} -- still one validation pass, over all sizes.  Not with sliding windows,
+    return_knn_details or torch.distributed (ValueError)."""
     if memory_sizes is not None and memory_size is None:
         raise ValueError("memory_sizes needs memory_size: the bank is built once, at memory_size, and the listed sizes are views of it")
     if nn_params is None:
@@ -970,6 +1044,28 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     last_run_info.clear()
     last_run_info.update(bank_loaded=bool(evaluator.bank_loaded), bank_build_s=float(evaluator.bank_build_s),
                          bank_rows=int(evaluator.total_rows), train_batches_loaded=int(evaluator.batches_loaded))
+    if grid_k is not None or grid_beta is not None:
+        grid = dict(n_neighbours=n_neighbours if grid_k is None else grid_k, betas=evaluator.beta if grid_beta is None else grid_beta,
+                    ignore_index=effective_ignore, window=window, return_knn_details=return_knn_details)
+        if memory_sizes is None:
+            return evaluator.evaluate_grid(val_loader, eval_spatial_resolution, **grid)
+        views = {}
+        for size in memory_sizes:
+            size = int(size)
+            if size > memory_size or size in views:
+                continue
+            views[size] = evaluator if size == memory_size else evaluator.memory_view(
+                memory_size=size, rows_per_image=evaluator.num_sampled_features if evaluator.bank_loaded else None)
+        results = {size: {} for size in views}
+        try:
+            if views:
+                for (size, k, beta), v in evaluator.evaluate_grid(val_loader, eval_spatial_resolution, views=views, **grid).items():
+                    results[size][(k, beta)] = v
+        finally:
+            for ev in views.values():
+                if ev is not evaluator:
+                    ev.index.close()
+        return results
     if memory_sizes is None:
         return evaluator.evaluate(val_loader, eval_spatial_resolution=eval_spatial_resolution,
                                   return_knn_details=return_knn_details, ignore_index=effective_ignore, window=window)

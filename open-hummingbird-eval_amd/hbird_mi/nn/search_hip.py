@@ -10,6 +10,8 @@ RCCL all-gather, `idx_shard=False` keeps a full replica per rank (faiss.IndexRep
 from __future__ import annotations
 
 import ctypes
+import math
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import numpy as np
@@ -35,6 +37,59 @@ def check_k(k: int, what: str = "k"):
     """1 <= k <= 2048 or the ValueError faiss-gpu raises for its k-select limit."""
     if not 1 <= k <= MAX_K_SEARCH:
         raise ValueError(f"{what}={k} outside the supported range [1, {MAX_K_SEARCH}] (faiss-gpu's own limit)")
+
+
+GridPlan = namedtuple("GridPlan", "ks betas configs launches")
+
+
+def grid_plan(ks, betas, max_configs: int = _lib.GRID_MAX_CONFIGS) -> GridPlan:
+    """The grid of an aggregation over (k, beta) configurations, validated, ordered and cut into launches.  Pure Python.
+
+    `ks`, `betas`: a number or an iterable of numbers each; duplicates are dropped, both are sorted ascending.  ValueError for an empty list, a k
+    that is not an integer in [1, 2048] and a beta that is not a finite positive number.
+    -> GridPlan(ks, betas, configs, launches):
+       configs   THE configuration order: [(k, beta) for k in ks for beta in betas] -- row i of every [nk * nb, nq, C] result is configs[i]
+       launches  [(ks_part, betas_part, rows)]: rectangles of at most `max_configs` configurations (what one hb_index_aggregate_grid call
+                 takes: ascending ks_part x betas_part over the same neighbour list), rows[ik * len(betas_part) + ib] = the row of that
+                 configuration in `configs`.  Whole k rows go together, as many as fit; a grid with more than `max_configs` betas is cut along
+                 the betas as well.  Concatenating the launches' rows in launch order gives 0 .. len(configs) - 1 when the betas are not cut."""
+    def as_list(v, what):
+        if isinstance(v, (str, bytes)):
+            raise ValueError(f"{what} must be a number or a list of numbers, got {v!r}")
+        try:
+            out = list(v)
+        except TypeError:
+            out = [v]
+        if not out:
+            raise ValueError(f"{what} is empty: the grid needs at least one value")
+        return out
+
+    k_out = []
+    for k in as_list(ks, "ks"):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"k={k!r} is not an integer")
+        check_k(int(k))
+        k_out.append(int(k))
+    b_out = []
+    for b in as_list(betas, "betas"):
+        if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)):
+            raise ValueError(f"beta={b!r} is not a number")
+        b = float(b)
+        if not (math.isfinite(b) and b > 0.0):
+            raise ValueError(f"beta={b!r}: every beta must be finite and positive")
+        b_out.append(b)
+    k_out, b_out = sorted(set(k_out)), sorted(set(b_out))
+    nb = len(b_out)
+    configs = [(k, b) for k in k_out for b in b_out]
+    b_step = min(nb, max_configs)
+    k_step = max(1, max_configs // b_step)
+    launches = []
+    for k0 in range(0, len(k_out), k_step):
+        kp = k_out[k0:k0 + k_step]
+        for b0 in range(0, nb, b_step):
+            bp = b_out[b0:b0 + b_step]
+            launches.append((tuple(kp), tuple(bp), [(k0 + i) * nb + b0 + j for i in range(len(kp)) for j in range(len(bp))]))
+    return GridPlan(tuple(k_out), tuple(b_out), configs, launches)
 
 
 def _ptr(t):
@@ -212,6 +267,71 @@ class HipFlatIndex:
         _lib.check(_lib.lib().hb_bigk_aggregate_partial(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base),
                                                         float(beta), _ptr(norms_all), norms_all.shape[0], _ptr(out)))
         return out
+
+    # evaluation grids (hb_index_aggregate_grid / hb_index_search_aggregate_grid, csrc/hbird_grid.hip): every (k, beta) of a grid from ONE list
+    # per query -- the best k of a query are the first k entries of its best k_max, bit for bit, and beta only enters after the search
+    def _grid_call(self, q, idx, dist, kp, bp, id_base, out):
+        """One launch: configurations kp x bp (at most 16) on the lists idx / dist [nq, k_list], into out [len(kp) * len(bp), nq, C]."""
+        ka, ba = (ctypes.c_int * len(kp))(*kp), (ctypes.c_float * len(bp))(*bp)
+        _lib.check(_lib.lib().hb_index_aggregate_grid(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base),
+                                                       ka, len(kp), ba, len(bp), _ptr(out), 1), ValueError)
+        return out
+
+    def aggregate_grid(self, q, idx, dist, ks, betas, id_base: int = 0):
+        """Label aggregation of every configuration of `grid_plan(ks, betas)` on given neighbours (CUDA tensors; idx / dist [nq, k_list] with
+        k_list >= max(ks)): -> [nk * nb, nq, C], row i the result of `aggregate` on the first k positions of the lists for (k, beta) =
+        grid_plan(ks, betas).configs[i] -- its bits.  Up to k = 256 the configurations go 16 to a launch on the lists as they are; a k beyond 256
+        is served by `aggregate_bigk` on a contiguous prefix copy.  ValueError for a bad grid and for lists shorter than the largest k."""
+        plan = grid_plan(ks, betas)
+        assert q.is_cuda and idx.is_cuda and dist.is_cuda
+        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous()
+        k_list = idx.shape[1]
+        if plan.ks[-1] > k_list:
+            raise ValueError(f"aggregate_grid: the largest k ({plan.ks[-1]}) exceeds k_list ({k_list}), the length of the given lists")
+        nq, nb = q.shape[0], len(plan.betas)
+        out = torch.empty((len(plan.configs), nq, self.num_classes), dtype=torch.float32, device=q.device)
+        small = [k for k in plan.ks if k <= MAX_K]
+        if small:
+            if k_list > MAX_K:            # the list-resident entry takes strides up to 256: the prefix every small k lives in
+                idx_s, dist_s = idx[:, :small[-1]].contiguous(), dist[:, :small[-1]].contiguous()
+            else:
+                idx_s, dist_s = idx, dist
+            launches = grid_plan(small, plan.betas).launches
+            for kp, bp, rows in launches:
+                whole = len(launches) == 1 and len(small) == len(plan.ks)
+                part = out if whole else torch.empty((len(rows), nq, out.shape[2]), dtype=torch.float32, device=q.device)
+                self._grid_call(q, idx_s, dist_s, kp, bp, id_base, part)
+                if not whole:
+                    out[torch.as_tensor(rows, device=q.device)] = part       # (the rows of the small ks come first in the whole grid too)
+        for ik, k in enumerate(plan.ks):
+            if k > MAX_K:
+                idx_k, dist_k = idx[:, :k].contiguous(), dist[:, :k].contiguous()
+                for ib, beta in enumerate(plan.betas):
+                    out[ik * nb + ib] = self.aggregate_bigk(q, idx_k, dist_k, beta=beta, id_base=id_base)
+        return out
+
+    def search_aggregate_grid(self, q, ks, betas, id_base: int = 0, want_neighbours: bool = False):
+        """ONE search at max(ks), then `aggregate_grid`: -> [nk * nb, nq, C] (and the [nq, max(ks)] neighbour lists); numpy in, numpy out.
+        A grid of one launch with max(ks) <= 256 is the fused entry hb_index_search_aggregate_grid."""
+        plan = grid_plan(ks, betas)
+        on_dev, q = self._as_f32(q)
+        nq, kmax, c = q.shape[0], plan.ks[-1], self.num_classes
+        if len(plan.launches) == 1 and kmax <= MAX_K:
+            new = (lambda shape, dt: torch.empty(shape, dtype=dt, device=q.device)) if on_dev else \
+                (lambda shape, dt: np.empty(shape, dtype=np.int64 if dt == torch.int64 else np.float32))
+            out = new((len(plan.configs), nq, c), torch.float32)
+            idx = new((nq, kmax), torch.int64) if want_neighbours else None
+            dist = new((nq, kmax), torch.float32) if want_neighbours else None
+            ka, ba = (ctypes.c_int * len(plan.ks))(*plan.ks), (ctypes.c_float * len(plan.betas))(*plan.betas)
+            _lib.check(_lib.lib().hb_index_search_aggregate_grid(self._h, _ptr(q), nq, int(id_base), ka, len(plan.ks), ba, len(plan.betas),
+                                                                  _ptr(out), _ptr(idx), _ptr(dist), int(on_dev)), ValueError)
+            return (out, idx, dist) if want_neighbours else out
+        qd = q if on_dev else torch.from_numpy(q).cuda(self.device)
+        idx, dist = self.search(qd, kmax, id_base)
+        out = self.aggregate_grid(qd, idx, dist, plan.ks, plan.betas, id_base=id_base)
+        if not on_dev:
+            out, idx, dist = out.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
+        return (out, idx, dist) if want_neighbours else out
 
     @property
     def num_classes(self) -> int:
@@ -855,6 +975,25 @@ class HipMultiIndex:
             q = (q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32))).to(self.home)
         idx, dist = self._search(q, k, id_base, False)
         out = self.aggregate(q.float().contiguous(), idx, dist, beta=beta, id_base=id_base)
+        if host:
+            out, idx, dist = out.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
+        return (out, idx, dist) if want_neighbours else out
+
+    def aggregate_grid(self, q, idx, dist, ks, betas, id_base: int = 0):
+        """HipFlatIndex.aggregate_grid on the aggregation handle (the home device's tables)."""
+        self._tables()
+        with torch.cuda.device(self.home):
+            self.agg.use_current_stream()
+            return self.agg.aggregate_grid(q.to(self.home), idx, dist, ks, betas, id_base=id_base)
+
+    def search_aggregate_grid(self, q, ks, betas, id_base: int = 0, want_neighbours: bool = False):
+        """K4 on every GPU at max(ks), merge on the home device as for `search_aggregate`, the grid's K5 there."""
+        plan = grid_plan(ks, betas)
+        host = not (isinstance(q, torch.Tensor) and q.is_cuda)
+        if host:
+            q = (q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32))).to(self.home)
+        idx, dist = self._search(q, plan.ks[-1], id_base, False)
+        out = self.aggregate_grid(q.float().contiguous(), idx, dist, plan.ks, plan.betas, id_base=id_base)
         if host:
             out, idx, dist = out.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
         return (out, idx, dist) if want_neighbours else out

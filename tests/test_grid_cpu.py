@@ -1,0 +1,144 @@
+"""Evaluation grids without a GPU: the C ABI of include/hbird_hip_grid.h against its bindings and INTEGRATION.md, the pure-Python
+configuration helper (search_hip.grid_plan) and eval.py's --grid-k / --grid-beta."""
+import ctypes
+import importlib.util
+import inspect
+import os
+import re
+
+import pytest
+
+from hbird_mi import _lib
+from hbird_mi.nn.search_hip import MAX_K_SEARCH, GridPlan, HipFlatIndex, HipMultiIndex, grid_plan
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"hb_index_aggregate_grid", "hb_index_search_aggregate_grid"}
+
+C_TYPES = {"hb_index_t*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "float*": ctypes.c_void_p, "const int64_t*": ctypes.c_void_p,
+           "int64_t*": ctypes.c_void_p, "int64_t": ctypes.c_int64, "int": ctypes.c_int}
+HOST_ARRAYS = {"ks": ctypes.POINTER(ctypes.c_int), "betas": ctypes.POINTER(ctypes.c_float)}       # host arrays: typed pointers
+
+
+def _declarations(header):
+    """name -> (return type, [(type, name)]) of every function the header declares."""
+    out = {}
+    body = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for ret, name, args in re.findall(r"^\s*(\w+)\s+(hb_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", body, flags=re.M):
+        params = []
+        for a in args.split(","):
+            typ, arg = a.strip().rsplit(" ", 1)
+            params.append((re.sub(r"\s*\*", "*", typ.strip()), arg))
+        out[name] = (ret, params)
+    return out
+
+
+def test_grid_entries_are_declared_exported_bound_and_documented():
+    header = open(os.path.join(ROOT, "include", "hbird_hip_grid.h")).read()
+    main = open(os.path.join(ROOT, "include", "hbird_hip.h")).read()
+    assert '#include "hbird_hip_grid.h"' in main and main.index('#include "hbird_hip_grid.h"') > main.index('#include "hbird_hip_select.h"')
+    decl = _declarations(header)
+    assert set(decl) == NAMES == set(_lib.SIGNATURES_GRID)
+    L = _lib.lib()
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name, (ret, params) in decl.items():
+        res, argtypes = _lib.SIGNATURES_GRID[name]
+        assert ret == "int" and res is ctypes.c_int
+        want = [HOST_ARRAYS[arg] if arg in HOST_ARRAYS else C_TYPES[typ] for typ, arg in params]
+        assert want == argtypes, (name, params)
+        fn = getattr(L, name)                       # exported ...
+        assert fn.argtypes == argtypes and fn.restype is res and f"`{name}`" in doc       # ... bound and named in the map
+    assert [a for _, a in decl["hb_index_aggregate_grid"][1]] == ["ix", "q", "nq", "idx", "dist", "k_list", "id_base", "ks", "nk", "betas", "nb",
+                                                                  "out", "io_on_device"]
+    assert [a for _, a in decl["hb_index_search_aggregate_grid"][1]] == ["ix", "q", "nq", "id_base", "ks", "nk", "betas", "nb", "out", "out_idx_opt",
+                                                                         "out_dist_opt", "io_on_device"]
+    assert int(re.search(r"#define\s+HB_GRID_MAX_CONFIGS\s+(\d+)", header).group(1)) == _lib.GRID_MAX_CONFIGS == 16
+    # the new unit is built, and stays out of the units whose resource baselines are pinned
+    mk = open(os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc", "Makefile")).read()
+    assert "hbird_grid.hip" in re.search(r"^SRCS\s*=(.*)$", mk, flags=re.M).group(1)
+    assert "hbird_grid" not in re.search(r"^KNN_UNITS\s*=(.*)$", mk, flags=re.M).group(1)
+
+
+def test_grid_entries_refuse_bad_arguments_before_touching_a_gpu():
+    """A NULL handle and a bad grid are errors with a message, never a dereference (no GPU is touched)."""
+    L = _lib.lib()
+    ks, betas = (ctypes.c_int * 2)(10, 30), (ctypes.c_float * 1)(0.02)
+    assert L.hb_index_aggregate_grid(None, None, 1, None, None, 30, 0, ks, 2, betas, 1, None, 1) != 0 and b"NULL" in L.hb_last_error()
+    assert L.hb_index_search_aggregate_grid(None, None, 1, 0, ks, 2, betas, 1, None, None, None, 1) != 0 and b"NULL" in L.hb_last_error()
+    for meth in ("aggregate_grid", "search_aggregate_grid"):
+        assert callable(getattr(HipFlatIndex, meth)) and callable(getattr(HipMultiIndex, meth))
+    assert list(inspect.signature(HipFlatIndex.aggregate_grid).parameters)[1:] == ["q", "idx", "dist", "ks", "betas", "id_base"]
+    assert list(inspect.signature(HipFlatIndex.search_aggregate_grid).parameters)[1:] == ["q", "ks", "betas", "id_base", "want_neighbours"]
+    from hbird_mi.hbird_eval import HbirdEvaluation, hbird_evaluation
+    assert list(inspect.signature(HbirdEvaluation.evaluate_grid).parameters)[1:7] == ["val_loader", "eval_spatial_resolution", "n_neighbours", "betas",
+                                                                                      "views", "ignore_index"]
+    assert inspect.signature(HbirdEvaluation.__init__).parameters["beta"].default == 0.02
+    assert list(inspect.signature(HbirdEvaluation.__init__).parameters)[-1] == "beta"
+    assert inspect.signature(HbirdEvaluation.from_index).parameters["beta"].default == 0.02
+    sig = inspect.signature(hbird_evaluation).parameters
+    assert sig["grid_k"].default is None and sig["grid_beta"].default is None
+
+
+def test_grid_plan_orders_deduplicates_and_names_the_configurations():
+    p = grid_plan([30, 10, 90, 30], (0.05, 0.02, 0.05))
+    assert isinstance(p, GridPlan) and p.ks == (10, 30, 90) and p.betas == (0.02, 0.05)
+    assert p.configs == [(10, 0.02), (10, 0.05), (30, 0.02), (30, 0.05), (90, 0.02), (90, 0.05)]           # cfg = ik * nb + ib
+    assert p.launches == [((10, 30, 90), (0.02, 0.05), [0, 1, 2, 3, 4, 5])]
+    assert all(type(k) is int for k in p.ks) and all(type(b) is float for b in p.betas)
+    one = grid_plan(30, 0.02)                       # scalars are grids of one
+    assert one.configs == [(30, 0.02)] and one.launches == [((30,), (0.02,), [0])]
+    import numpy as np
+    assert grid_plan(np.array([5, 3]), np.array([0.5], dtype=np.float32)).configs == [(3, 0.5), (5, 0.5)]
+    assert grid_plan([1, MAX_K_SEARCH], [1e-3]).ks == (1, 2048)
+
+
+def test_grid_plan_cuts_a_grid_into_launches_of_at_most_16():
+    def check(p):
+        rows = []
+        for ks, betas, r in p.launches:
+            assert 1 <= len(ks) * len(betas) == len(r) <= 16
+            assert list(ks) == sorted(set(ks)) and list(betas) == sorted(set(betas))           # what one C call takes
+            assert [p.configs[i] for i in r] == [(k, b) for k in ks for b in betas]            # launch-local cfg = ik * nb + ib
+            rows += r
+        assert sorted(rows) == list(range(len(p.configs)))                                      # every configuration exactly once
+        return rows
+    # 5 x 5: launches are rectangles ks x betas over the same list, whole k rows together -- 3 x 5 + 2 x 5, in configuration order
+    p = grid_plan(range(1, 6), [0.01, 0.02, 0.05, 0.1, 0.2])
+    assert [(len(k), len(b)) for k, b, _ in p.launches] == [(3, 5), (2, 5)] and check(p) == list(range(25))
+    p = grid_plan(range(1, 9), [0.02, 0.1])
+    assert len(p.launches) == 1 and check(p) == list(range(16))
+    p = grid_plan(range(1, 10), [0.02, 0.1])
+    assert [(len(k), len(b)) for k, b, _ in p.launches] == [(8, 2), (1, 2)] and check(p) == list(range(18))
+    p = grid_plan(range(1, 40), 0.02)
+    assert [len(k) for k, _, _ in p.launches] == [16, 16, 7] and check(p) == list(range(39))
+    # more betas than a launch holds: cut along the betas too
+    p = grid_plan([7, 9], [i / 100 for i in range(1, 21)])
+    assert [(k, len(b)) for k, b, _ in p.launches] == [((7,), 16), ((7,), 4), ((9,), 16), ((9,), 4)] and check(p) == list(range(40))
+    p = grid_plan([3, 5, 7], [0.1, 0.2], max_configs=4)
+    assert [(len(k), len(b)) for k, b, _ in p.launches] == [(2, 2), (1, 2)]
+
+
+@pytest.mark.parametrize("ks,betas,msg", [
+    ([], [0.02], "ks is empty"), ([30], [], "betas is empty"), ([0], [0.02], r"outside the supported range \[1, 2048\]"),
+    ([2049], [0.02], r"outside the supported range \[1, 2048\]"), ([-3], [0.02], "outside the supported range"), ([1.5], [0.02], "not an integer"),
+    ([True], [0.02], "not an integer"), (["30"], [0.02], "not an integer"), ("30", [0.02], "must be a number or a list"),
+    ([30], [0.0], "finite and positive"), ([30], [-0.02], "finite and positive"), ([30], [float("nan")], "finite and positive"),
+    ([30], [float("inf")], "finite and positive"), ([30], ["0.02"], "not a number"), ([30], [None], "not a number")])
+def test_grid_plan_validation_messages(ks, betas, msg):
+    with pytest.raises(ValueError, match=msg):
+        grid_plan(ks, betas)
+
+
+def test_cli_parser_takes_the_grid_flags():
+    spec = importlib.util.spec_from_file_location("hb_cli_grid_cpu", os.path.join(ROOT, "eval.py"))
+    cli = importlib.util.module_from_spec(spec); spec.loader.exec_module(cli)
+    base = ["--dataset-name", "synthetic", "--data-dir", "", "--d-model", "3", "--patch-size", "8"]
+    p = cli.build_parser()
+    a = p.parse_args(base)
+    assert a.grid_k is None and a.grid_beta is None and a.n_neighbours == 30
+    a = p.parse_args(base + ["--grid-k", "10", "30", "90", "--grid-beta", "0.01", "0.02", "--n-neighbours", "7"])
+    assert a.grid_k == [10, 30, 90] and a.grid_beta == [0.01, 0.02] and a.n_neighbours == 7 and isinstance(a.n_neighbours, int)
+    for bad in (["--grid-k", "0"], ["--grid-k", "-3"], ["--grid-k", "2.5"], ["--grid-k"], ["--grid-beta", "0"], ["--grid-beta", "-0.1"],
+                ["--grid-beta", "nan"], ["--grid-beta", "inf"], ["--grid-beta"], ["--n-neighbours", "10", "30"]):
+        with pytest.raises(SystemExit):
+            p.parse_args(base + bad)
+    assert cli.grid_key(30, 0.02) == "k=30,beta=0.02" and cli.grid_key(3, 0.1) == "k=3,beta=0.1"
