@@ -535,7 +535,7 @@ static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta, float* out_lab,
                        int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate, bool bigk = false, const hb_grid_spec* grid = nullptr) {
-    // bigk: the aggregation is hbird_bigk.hip's K5 (hb_bigk_search_aggregate), whose k goes as far as the search's
+    // bigk: the aggregation is aggregate_bigk_kernel's (hb_bigk_search_aggregate), whose k goes as far as the search's
     // grid: the aggregation is hbird_grid.hip's, over the grid's configurations (k is its largest; out_lab holds one [nq, c] slab each)
     if (nq < 0) return hb_fail("hb_index_search: negative query count");
     if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search: k must be in [1, " + std::to_string(HB_MAX_K) + "] (faiss-gpu's own limit)");
@@ -600,13 +600,34 @@ extern "C" int hb_index_search(hb_index_t* ix, const float* q, int64_t nq, int k
     return search_impl(ix, q, nq, k, id_base, 0.f, nullptr, out_idx, out_dist, io_on_device, false);
 }
 
+// neither a borrowed label table nor own label rows for every bank row
+static bool labels_missing(const hb_index* ix) {
+    return !ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal);
+}
+
+// What every aggregation on GIVEN lists does once its own arguments are checked (nq > 0): the labels' conversion check, the query norms,
+// then `launch(qnorm)`.  zero_if_empty: the output of a label-sharded entry, whose partial sums are zero on a shard without rows.
+template <typename Launch>
+static int aggregate_on_lists(hb_index* ix, const char* range_name, const float* q, int64_t nq, float* zero_if_empty, Launch launch) {
+    hb_range range(range_name);
+    HB_HIP(hipSetDevice(ix->device));
+    if (hb_labels_checked(ix)) return -1;
+    if (zero_if_empty && ix->ntotal == 0) {   // an empty shard owns no neighbour
+        HB_HIP(hipMemsetAsync(zero_if_empty, 0, (size_t)nq * ix->c * 4, ix->stream));
+        return 0;
+    }
+    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
+    return launch(ix->q_aux + nq);
+}
+
 extern "C" int hb_index_search_aggregate(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta,
                                          float* out_label_hat, int64_t* out_idx_opt, float* out_dist_opt,
                                          int io_on_device) {
     if (!ix) return hb_fail("hb_index_search_aggregate: NULL index handle");
     if (nq > 0 && !out_label_hat) return hb_fail("hb_index_search_aggregate: out_label_hat is NULL");
     if (!(beta > 0.f)) return hb_fail("hb_index_search_aggregate: beta must be positive");
-    if (!ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal)) return hb_fail("hb_index_search_aggregate: label rows missing (hb_index_add_labels)");
+    if (labels_missing(ix)) return hb_fail("hb_index_search_aggregate: label rows missing (hb_index_add_labels)");
     if (hb_labels_checked(ix)) return -1;
     return search_impl(ix, q, nq, k, id_base, beta, out_label_hat, out_idx_opt, out_dist_opt, io_on_device, true);
 }
@@ -619,36 +640,26 @@ extern "C" int hb_index_aggregate(hb_index_t* ix, const float* q, int64_t nq, co
     if (k < 1) return hb_fail("hb_index_aggregate: k must be positive");
     if (!io_on_device) return hb_fail("hb_index_aggregate: host pointers are not supported, pass device memory");
     if (!(beta > 0.f)) return hb_fail("hb_index_aggregate: beta must be positive");
-    hb_range range("hbird:aggregate");
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
-    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
-    return hb_launch_aggregate(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_label_hat, ix->stream);
+    return aggregate_on_lists(ix, "hbird:aggregate", q, nq, nullptr, [&](const float* qnorm) {
+        return hb_launch_aggregate(ix, qnorm, idx, dist, nq, k, id_base, beta, out_label_hat, ix->stream);
+    });
 }
 
 // ---- evaluation grids (hbird_grid.hip, include/hbird_hip_grid.h): every (k, beta) of a grid from one list per query.  Everything is
 // checked before the first launch: a failing call leaves no half-written output behind.
-static bool grid_labels_missing(const hb_index* ix) {
-    return !ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal);
-}
-
 extern "C" int hb_index_aggregate_grid(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k_list,
                                        int64_t id_base, const int* ks, int nk, const float* betas, int nb, float* out, int io_on_device) {
     if (!ix) return hb_fail("hb_index_aggregate_grid: NULL index handle");
     if (nq < 0) return hb_fail("hb_index_aggregate_grid: nq is negative");
     hb_grid_spec gs;
     if (hb_grid_check("hb_index_aggregate_grid", ks, nk, betas, nb, k_list, &gs)) return -1;
-    if (grid_labels_missing(ix)) return hb_fail("hb_index_aggregate_grid: label rows missing (hb_index_add_labels)");
+    if (labels_missing(ix)) return hb_fail("hb_index_aggregate_grid: label rows missing (hb_index_add_labels)");
     if (nq == 0) return 0;
     if (!q || !idx || !dist || !out) return hb_fail("hb_index_aggregate_grid: NULL pointer");
     if (!io_on_device) return hb_fail("hb_index_aggregate_grid: host pointers are not supported, pass device memory");
-    hb_range range("hbird:aggregate_grid");
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
-    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
-    return hb_launch_aggregate_grid(ix, ix->q_aux + nq, idx, dist, nq, k_list, id_base, gs, out, ix->stream);
+    return aggregate_on_lists(ix, "hbird:aggregate_grid", q, nq, nullptr, [&](const float* qnorm) {
+        return hb_launch_aggregate_grid(ix, qnorm, idx, dist, nq, k_list, id_base, gs, out, ix->stream);
+    });
 }
 
 extern "C" int hb_index_search_aggregate_grid(hb_index_t* ix, const float* q, int64_t nq, int64_t id_base, const int* ks, int nk,
@@ -658,7 +669,7 @@ extern "C" int hb_index_search_aggregate_grid(hb_index_t* ix, const float* q, in
     hb_grid_spec gs;
     if (hb_grid_check("hb_index_search_aggregate_grid", ks, nk, betas, nb, -1, &gs)) return -1;
     if (nq > 0 && !out) return hb_fail("hb_index_search_aggregate_grid: out is NULL");
-    if (grid_labels_missing(ix)) return hb_fail("hb_index_search_aggregate_grid: label rows missing (hb_index_add_labels)");
+    if (labels_missing(ix)) return hb_fail("hb_index_search_aggregate_grid: label rows missing (hb_index_add_labels)");
     if (hb_labels_checked(ix)) return -1;
     // the search of hb_index_search_aggregate at the grid's largest k, then the grid's aggregation on its lists
     return search_impl(ix, q, nq, gs.ks[nk - 1], id_base, 0.f, out, out_idx_opt, out_dist_opt, io_on_device, true, false, &gs);
@@ -672,19 +683,12 @@ extern "C" int hb_index_aggregate_partial(hb_index_t* ix, const float* q, int64_
     if (k < 1) return hb_fail("hb_index_aggregate_partial: k must be positive");
     if (!q || !idx || !dist || !norms_all || !out_partial) return hb_fail("hb_index_aggregate_partial: NULL pointer");
     if (!(beta > 0.f)) return hb_fail("hb_index_aggregate_partial: beta must be positive");
-    hb_range range("hbird:aggregate_partial");
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    if (ix->ntotal == 0) {   // an empty shard owns no neighbour: its partial sums are zero
-        HB_HIP(hipMemsetAsync(out_partial, 0, (size_t)nq * ix->c * 4, ix->stream));
-        return 0;
-    }
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
-    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
-    return hb_launch_aggregate(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_partial, ix->stream, norms_all, n_all);
+    return aggregate_on_lists(ix, "hbird:aggregate_partial", q, nq, out_partial, [&](const float* qnorm) {
+        return hb_launch_aggregate(ix, qnorm, idx, dist, nq, k, id_base, beta, out_partial, ix->stream, norms_all, n_all);
+    });
 }
 
-// ---- k beyond 256: the hb_bigk_* family (hbird_bigk.hip).  Argument lists of their hb_index_* / hb_merge_* counterparts, 1 <= k <= HB_MAX_K.
+// ---- k beyond 256: the hb_bigk_* family (K5: hbird_aggregate.hip, merge: hbird_bigk.hip).  Argument lists of their hb_index_* / hb_merge_* counterparts, 1 <= k <= HB_MAX_K.
 static std::string bigk_range(const char* who) { return std::string(who) + ": k must be in [1, " + std::to_string(HB_MAX_K) + "]"; }
 
 extern "C" int hb_bigk_search_aggregate(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta,
@@ -693,7 +697,7 @@ extern "C" int hb_bigk_search_aggregate(hb_index_t* ix, const float* q, int64_t 
     if (nq > 0 && !out_label_hat) return hb_fail("hb_bigk_search_aggregate: out_label_hat is NULL");
     if (k < 1 || k > HB_MAX_K) return hb_fail(bigk_range("hb_bigk_search_aggregate"));
     if (!(beta > 0.f)) return hb_fail("hb_bigk_search_aggregate: beta must be positive");
-    if (!ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal)) return hb_fail("hb_bigk_search_aggregate: label rows missing (hb_index_add_labels)");
+    if (labels_missing(ix)) return hb_fail("hb_bigk_search_aggregate: label rows missing (hb_index_add_labels)");
     if (hb_labels_checked(ix)) return -1;
     return search_impl(ix, q, nq, k, id_base, beta, out_label_hat, out_idx_opt, out_dist_opt, io_on_device, true, true);
 }
@@ -707,12 +711,9 @@ extern "C" int hb_bigk_aggregate(hb_index_t* ix, const float* q, int64_t nq, con
     if (nq == 0) return 0;
     if (!q || !idx || !dist || !out_label_hat) return hb_fail("hb_bigk_aggregate: NULL pointer");
     if (!io_on_device) return hb_fail("hb_bigk_aggregate: host pointers are not supported, pass device memory");
-    hb_range range("hbird:aggregate_bigk");
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
-    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
-    return hb_launch_aggregate_bigk(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_label_hat, ix->stream);
+    return aggregate_on_lists(ix, "hbird:aggregate_bigk", q, nq, nullptr, [&](const float* qnorm) {
+        return hb_launch_aggregate_bigk(ix, qnorm, idx, dist, nq, k, id_base, beta, out_label_hat, ix->stream);
+    });
 }
 
 extern "C" int hb_bigk_aggregate_partial(hb_index_t* ix, const float* q, int64_t nq, const int64_t* idx, const float* dist, int k,
@@ -723,16 +724,9 @@ extern "C" int hb_bigk_aggregate_partial(hb_index_t* ix, const float* q, int64_t
     if (!(beta > 0.f)) return hb_fail("hb_bigk_aggregate_partial: beta must be positive");
     if (nq == 0) return 0;
     if (!q || !idx || !dist || !norms_all || !out_partial) return hb_fail("hb_bigk_aggregate_partial: NULL pointer");
-    hb_range range("hbird:aggregate_partial_bigk");
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    if (ix->ntotal == 0) {   // an empty shard owns no neighbour: its partial sums are zero
-        HB_HIP(hipMemsetAsync(out_partial, 0, (size_t)nq * ix->c * 4, ix->stream));
-        return 0;
-    }
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
-    if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
-    return hb_launch_aggregate_bigk(ix, ix->q_aux + nq, idx, dist, nq, k, id_base, beta, out_partial, ix->stream, norms_all, n_all);
+    return aggregate_on_lists(ix, "hbird:aggregate_partial_bigk", q, nq, out_partial, [&](const float* qnorm) {
+        return hb_launch_aggregate_bigk(ix, qnorm, idx, dist, nq, k, id_base, beta, out_partial, ix->stream, norms_all, n_all);
+    });
 }
 
 static int bigk_merge_checks(const char* who, int parts, int64_t nq, int k, int metric) {

@@ -2,7 +2,8 @@
 //
 // The engine's lists are the exact top-k under one total order (score descending, id ascending) with deterministic score bits, so the
 // best k of a query are the first k entries of its best k_max: one search at the largest k serves every smaller k, and beta only
-// enters after the search.  aggregate_grid_kernel is aggregate_kernel (hbird_aggregate.hip) applied to the first k POSITIONS of the
+// enters after the search.  aggregate_grid_kernel is aggregate_kernel (hbird_aggregate.hip; k5_body of hbird_k5_dev.h, which also holds
+// the neighbour resolution and the count decode used here) applied to the first k POSITIONS of the
 // list for every configuration (k, beta) of the grid -- whatever those positions hold: -1 entries, ids outside the norm table, repeated
 // ids -- and agrees with it bit for bit.  That fixes the arithmetic order, configuration by configuration:
 //   c_j = ip_j / (max(|q|, 1e-12) max(|b_j|, 1e-12)) once per neighbour (L2: ip = 0.5 (qn2 + bn^2 - dist)), logit = c_j / beta,
@@ -14,16 +15,15 @@
 // configurations -- G configurations cost one launch and one gather, not G.  A position beyond a configuration's k is predicated out
 // of its accumulator (not multiplied by a zero weight: an fp32 table may hold a non-finite value).
 //
-// Shape: aggregate_bigk_kernel's (hbird_bigk.hip) -- a workgroup IS one wave with dynamic LDS: kmax cosines and 32-bit rows plus NC
+// Shape: aggregate_bigk_kernel's (hbird_aggregate.hip) -- a workgroup IS one wave with dynamic LDS: kmax cosines and 32-bit rows plus NC
 // weights per position, 4 (2 + NC) kmax bytes = 18 KiB at 256 x 16.  The weights of one position are contiguous (w[j][cfg]): the gather
 // loop fetches them with 16-byte LDS reads at an address all lanes (wide / generic body) or all lanes of a neighbour group share.
 // The configurations are a template parameter (4 / 8 / 12 / 16 accumulator sets, a smaller grid padded with weights of zero) so that
 // the accumulators are registers: 8 x 16 = 128 VGPRs in the wide body, no scratch (profiles/r12/README.md has the resource report).
 #include "hbird_internal.h"
 #include "../../include/hbird_hip.h"
+#include "hbird_k5_dev.h"
 #include <cmath>
-
-#define GRID_LUT 2048   // uint16 counts: the three-instruction quotient holds for P <= 2048 (hbird_aggregate.hip: AGG_LUT)
 
 template <bool U16, int NC>
 __global__ __launch_bounds__(64) void aggregate_grid_kernel(const void* __restrict__ labels_v, int ls, int wide, int P, int64_t nlabels, int C,
@@ -36,7 +36,6 @@ __global__ __launch_bounds__(64) void aggregate_grid_kernel(const void* __restri
     extern __shared__ __attribute__((aligned(16))) char grid_smem[];
     const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
-    const float* labels = reinterpret_cast<const float*>(labels_v);
     const unsigned short* counts = reinterpret_cast<const unsigned short*>(labels_v);
     const float Pf = (float)P, Pr = 1.0f / Pf;
     if (q >= nq) return;
@@ -47,20 +46,10 @@ __global__ __launch_bounds__(64) void aggregate_grid_kernel(const void* __restri
     int* rows = reinterpret_cast<int*>(cosv + kmax);                 // [kmax]
     // the cosine and the label row of every position, once (lane-strided: lane l owns the positions l, l + 64, ... in every phase below)
     for (int j = lane; j < kmax; j += 64) {
-        float cs = -INFINITY;
-        int row = -1;
-        const int64_t gid = idx[q * (int64_t)k_list + j];
-        const int64_t r = gid - id_base, rn = gid - norm_base;
-        if (gid >= 0 && rn >= 0 && rn < nnorm) {
-            if (r >= 0 && r < nlabels) row = (int)r;
-            const float bn = fmaxf(bnorm[rn], 1e-12f);
-            const float qn = fmaxf(qnorm[q], 1e-12f);
-            float ip = dist[q * (int64_t)k_list + j];
-            if (metric == 1) ip = 0.5f * (qn2[q] + bnorm[rn] * bnorm[rn] - ip);   // squared L2 -> inner product
-            cs = ip / (qn * bn);
-        }
-        cosv[j] = cs;
-        rows[j] = row;
+        int64_t row;
+        cosv[j] = k5_neighbour(idx[q * (int64_t)k_list + j], dist + q * (int64_t)k_list + j, id_base, nlabels, bnorm, norm_base, nnorm,
+                               qnorm + q, metric, qn2 + q, row);
+        rows[j] = (int)row;
     }
     // the softmax of every configuration over its prefix: aggregate_kernel's three passes, lane sums and butterflies
     for (int ik = 0; ik < nk; ++ik) {
@@ -95,15 +84,7 @@ __global__ __launch_bounds__(64) void aggregate_grid_kernel(const void* __restri
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's own LDS writes are visible to all its lanes
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // ... and the compiler keeps the gather's LDS reads behind them (no instruction)
-    auto label_at = [&](int64_t rj, int c) -> float {
-        if (U16) {
-            const float jf = (float)counts[rj * (int64_t)ls + c];
-            if (P > GRID_LUT) return jf / Pf;
-            const float q1 = jf * Pr;
-            return fmaf(fmaf(-q1, Pf, jf), Pr, q1);
-        }
-        return labels[rj * (int64_t)ls + c];
-    };
+    auto label_at = [&](int64_t rj, int c) -> float { return k5_label_at<U16>(labels_v, rj, ls, c, P, Pf, Pr); };
     const size_t slab = (size_t)nq * C;   // out[cfg][nq][C]
     constexpr int UB = 8;                 // label rows in flight per lane
     if (C <= 32) {
@@ -167,14 +148,8 @@ __global__ __launch_bounds__(64) void aggregate_grid_kernel(const void* __restri
                 for (int u = 0; u < UB; ++u) {
                     const int j = j0 + u;
                     const int fj = j < kmax ? __float_as_int(cosv[j]) : NC;
-                    const unsigned wds[4] = {raw[u].x, raw[u].y, raw[u].z, raw[u].w};
                     float lv[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const float jf = (float)((wds[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu);
-                        const float q1 = jf * Pr;
-                        lv[i] = fmaf(fmaf(-q1, Pf, jf), Pr, q1);
-                    }
+                    k5_unpack8(raw[u], Pf, Pr, lv);
                     const float4* w4 = reinterpret_cast<const float4*>(wgt + (j < kmax ? j : 0) * NC);
 #pragma unroll
                     for (int n4 = 0; n4 < NC / 4; ++n4) {
@@ -262,39 +237,31 @@ int hb_grid_check(const char* who, const int* ks, int nk, const float* betas, in
     return 0;
 }
 
-template <bool U16, typename... A>
-static void launch_grid(int ncfg, dim3 grid, int kmax, hipStream_t s, A... a) {
-    const dim3 block(64);
-    if (ncfg <= 4) aggregate_grid_kernel<U16, 4><<<grid, block, (size_t)kmax * 4 * (2 + 4), s>>>(a...);
-    else if (ncfg <= 8) aggregate_grid_kernel<U16, 8><<<grid, block, (size_t)kmax * 4 * (2 + 8), s>>>(a...);
-    else if (ncfg <= 12) aggregate_grid_kernel<U16, 12><<<grid, block, (size_t)kmax * 4 * (2 + 12), s>>>(a...);
-    else aggregate_grid_kernel<U16, 16><<<grid, block, (size_t)kmax * 4 * (2 + 16), s>>>(a...);
+template <int NC, typename... A>
+static void launch_grid_nc(bool u16, dim3 grid, int kmax, hipStream_t s, A... a) {
+    (u16 ? aggregate_grid_kernel<true, NC> : aggregate_grid_kernel<false, NC>)<<<grid, dim3(64), (size_t)kmax * 4 * (2 + NC), s>>>(a...);
 }
 
-// The table is chosen as hb_launch_aggregate's non-partial branch chooses it: the index's own rows (fp32 or counts) or a borrowed table.
+template <typename... A>
+static void launch_grid(int ncfg, A... a) {
+    if (ncfg <= 4) launch_grid_nc<4>(a...);
+    else if (ncfg <= 8) launch_grid_nc<8>(a...);
+    else if (ncfg <= 12) launch_grid_nc<12>(a...);
+    else launch_grid_nc<16>(a...);
+}
+
+// The index's own rows (fp32 or counts) or a borrowed table (hb_k5_table_choose); the grid has no label-sharded form.
 int hb_launch_aggregate_grid(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq, int k_list,
                              int64_t id_base, const hb_grid_spec& gs, float* out, hipStream_t s) {
     if (nq == 0) return 0;
     if (nq > 0x7FFFFFFFLL) return hb_fail("hb_index_aggregate_grid: more than 2^31 - 1 queries in one call");
-    bool u16 = ix->label_P > 0;
-    const void* labels = u16 ? (const void*)ix->labels16 : (const void*)ix->labels;
-    const float* bnorm = ix->bnorm;
-    int64_t nlab = ix->nlabels;
-    int P = ix->label_P, ls = ix->lab_stride();
-    if (ix->ext_labels || ix->ext_labels16) {
-        ls = ix->c;                                  // borrowed tables are dense [n, C]
-        u16 = ix->ext_labels16 != nullptr;
-        labels = u16 ? (const void*)ix->ext_labels16 : (const void*)ix->ext_labels; P = ix->ext_P;
-        bnorm = ix->ext_bnorm; nlab = ix->ext_n; id_base = ix->ext_base;
-    } else if (!labels || ix->nlabels < ix->ntotal) return hb_fail("hb_index_aggregate_grid: label rows missing (hb_index_add_labels)");
-    if (nlab > 0x7FFFFFFFLL) return hb_fail("hb_index_aggregate_grid: label tables of more than 2^31 - 1 rows are not supported");
-    if (!u16) P = 0;
-    // the 16-byte gather's conditions (hb_launch_aggregate: wide_ok)
-    const int wide = u16 && (ls & 7) == 0 && (reinterpret_cast<uintptr_t>(labels) & 15) == 0 && P > 0 && P <= GRID_LUT && ix->c > 32 && ix->c <= 512 ? 1 : 0;
+    hb_k5_table t;
+    if (hb_k5_table_choose(ix, id_base, nullptr, 0, "hb_index_aggregate_grid", &t)) return -1;
+    if (t.nlabels > 0x7FFFFFFFLL) return hb_fail("hb_index_aggregate_grid: label tables of more than 2^31 - 1 rows are not supported");
     const dim3 grid((unsigned)nq);
     const int ncfg = gs.nk * gs.nb, kmax = gs.ks[gs.nk - 1];
-    if (u16) launch_grid<true>(ncfg, grid, kmax, s, labels, ls, wide, P, nlab, ix->c, bnorm, id_base, nlab, qnorm, idx, dist, nq, k_list, id_base, ix->metric, (const float*)ix->q_aux, gs, out);
-    else launch_grid<false>(ncfg, grid, kmax, s, labels, ls, 0, 0, nlab, ix->c, bnorm, id_base, nlab, qnorm, idx, dist, nq, k_list, id_base, ix->metric, (const float*)ix->q_aux, gs, out);
+    launch_grid(ncfg, t.u16, grid, kmax, s, t.labels, t.ls, t.wide, t.P, t.nlabels, ix->c, t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k_list, t.id_base,
+                ix->metric, (const float*)ix->q_aux, gs, out);
     HB_HIP(hipGetLastError());
     return 0;
 }

@@ -164,11 +164,21 @@ int hb_launch_labels_to_counts(const float* src, int64_t rows, int c, int dst_st
 int hb_launch_gather_label_counts(const uint16_t* src, int64_t src_rows, int c, int src_stride, int P, const int64_t* ids, int64_t n, float* out, hipStream_t s);
 int hb_labels_ensure(hb_index* ix, int c, int64_t n);   // the label table for rows of c classes with room for n more rows (sets ix->c)
 int hb_labels_checked(hb_index* ix);   // 0, or fails when a stored label was not a multiple of 1 / label_P
+// K5 (hbird_aggregate.hip, hbird_grid.hip; device code in hbird_k5_dev.h).  The table one launch reads, chosen in ONE place for all three
+// kernels: label rows (fp32: P = 0) of stride ls covering the global ids [id_base, id_base + nlabels), norms covering
+// [norm_base, norm_base + nnorm), and whether the 16-byte gather of count rows applies.  norms_all: the label-sharded form.
+struct hb_k5_table {
+    const void* labels; bool u16; int P, ls; int64_t nlabels;
+    const float* bnorm; int64_t norm_base, nnorm;
+    int64_t id_base;
+    int wide;
+};
+int hb_k5_table_choose(const hb_index* ix, int64_t id_base, const float* norms_all, int64_t n_all, const char* who, hb_k5_table* t);
 int hb_launch_aggregate(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq,
                         int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);
 int hb_launch_merge_parts(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,
                           int64_t dist_stride, int64_t idx_stride, int64_t* out_idx, float* out_dist, hipStream_t s);
-// k beyond 256 (hbird_bigk.hip): K5 for 1 <= k <= HB_MAX_K with hb_launch_aggregate's tables and bits, and the merge of SORTED per-shard lists
+// k beyond 256: K5 for 1 <= k <= HB_MAX_K with hb_launch_aggregate's tables and bits (hbird_aggregate.hip), and the merge of SORTED per-shard lists (hbird_bigk.hip)
 int hb_launch_aggregate_bigk(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq,
                              int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);
 int hb_launch_merge_sorted_parts(const float* dist_parts, const int64_t* idx_parts, int parts, int64_t nq, int k, int metric,

@@ -44,7 +44,7 @@ SIGNATURES = {
     "hb_merge_topk": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "hb_packed_list_bytes": (c_int64, [c_int64, c_int]),
     "hb_merge_topk_packed": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    # k beyond 256 (csrc/hbird_bigk.hip): the argument lists of their hb_index_* / hb_merge_* counterparts
+    # k beyond 256 (K5: csrc/hbird_aggregate.hip, merges: csrc/hbird_bigk.hip): the argument lists of their hb_index_* / hb_merge_* counterparts
     "hb_bigk_search_aggregate": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_void_p, c_void_p,
                                          c_void_p, c_int]),
     "hb_bigk_aggregate": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64, c_float,

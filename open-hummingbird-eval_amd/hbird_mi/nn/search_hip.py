@@ -92,6 +92,13 @@ def grid_plan(ks, betas, max_configs: int = _lib.GRID_MAX_CONFIGS) -> GridPlan:
     return GridPlan(tuple(k_out), tuple(b_out), configs, launches)
 
 
+def _new(like, shape, dtype):
+    """An uninitialised output beside `like`: a tensor on its device for a CUDA tensor, a numpy array otherwise (dtype: a torch dtype)."""
+    if isinstance(like, torch.Tensor) and like.is_cuda:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    return np.empty(shape, dtype=np.int64 if dtype == torch.int64 else np.float32)
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -189,84 +196,61 @@ class HipFlatIndex:
             idx, dist = out
             assert on_dev and idx.is_cuda and dist.is_cuda and idx.is_contiguous() and dist.is_contiguous()
             assert idx.dtype == torch.int64 and dist.dtype == torch.float32 and tuple(idx.shape) == tuple(dist.shape) == (nq, k)
-        elif on_dev:
-            idx = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
         else:
-            idx = np.empty((nq, k), dtype=np.int64)
-            dist = np.empty((nq, k), dtype=np.float32)
+            idx, dist = _new(q, (nq, k), torch.int64), _new(q, (nq, k), torch.float32)
         _lib.check(_lib.lib().hb_index_search(self._h, _ptr(q), nq, int(k), int(id_base), _ptr(idx), _ptr(dist),
                                                int(on_dev)))
         return idx, dist
 
-    def search_aggregate(self, q, k: int, beta: float = 0.02, id_base: int = 0, want_neighbours: bool = False):
+    # K5 on one GPU: each method and its `_bigk` twin (k beyond 256, up to 2048: same arguments, same results, for k <= 256 the same bits)
+    # are one implementation that takes the C entry; `k5()` above routes between the twins.
+    def _search_aggregate(self, entry, q, k, beta, id_base, want_neighbours):
         on_dev, q = self._as_f32(q)
         nq = q.shape[0]
-        c = self.num_classes
-        if on_dev:
-            out = torch.empty((nq, c), dtype=torch.float32, device=q.device)
-            idx = torch.empty((nq, k), dtype=torch.int64, device=q.device) if want_neighbours else None
-            dist = torch.empty((nq, k), dtype=torch.float32, device=q.device) if want_neighbours else None
-        else:
-            out = np.empty((nq, c), dtype=np.float32)
-            idx = np.empty((nq, k), dtype=np.int64) if want_neighbours else None
-            dist = np.empty((nq, k), dtype=np.float32) if want_neighbours else None
-        _lib.check(_lib.lib().hb_index_search_aggregate(self._h, _ptr(q), nq, int(k), int(id_base), float(beta),
-                                                         _ptr(out), _ptr(idx), _ptr(dist), int(on_dev)))
+        out = _new(q, (nq, self.num_classes), torch.float32)
+        idx = _new(q, (nq, k), torch.int64) if want_neighbours else None
+        dist = _new(q, (nq, k), torch.float32) if want_neighbours else None
+        _lib.check(entry(self._h, _ptr(q), nq, int(k), int(id_base), float(beta), _ptr(out), _ptr(idx), _ptr(dist), int(on_dev)))
         return (out, idx, dist) if want_neighbours else out
+
+    def _aggregate(self, entry, q, idx, dist, beta, id_base):
+        assert q.is_cuda and idx.is_cuda and dist.is_cuda
+        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous()
+        out = _new(q, (q.shape[0], self.num_classes), torch.float32)
+        _lib.check(entry(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base), float(beta), _ptr(out), 1))
+        return out
+
+    def _aggregate_partial(self, entry, q, idx, dist, norms_all, beta, id_base):
+        assert q.is_cuda and idx.is_cuda and dist.is_cuda and norms_all.is_cuda
+        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous(); norms_all = norms_all.contiguous().float()
+        if self.ntotal == 0:                 # an empty shard owns no neighbour
+            return torch.zeros((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
+        out = _new(q, (q.shape[0], self.num_classes), torch.float32)
+        _lib.check(entry(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base), float(beta), _ptr(norms_all),
+                         norms_all.shape[0], _ptr(out)))
+        return out
+
+    def search_aggregate(self, q, k: int, beta: float = 0.02, id_base: int = 0, want_neighbours: bool = False):
+        return self._search_aggregate(_lib.lib().hb_index_search_aggregate, q, k, beta, id_base, want_neighbours)
 
     def aggregate(self, q, idx, dist, beta: float = 0.02, id_base: int = 0):
         """Label aggregation on given neighbours (CUDA tensors)."""
-        assert q.is_cuda and idx.is_cuda and dist.is_cuda
-        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous()
-        out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().hb_index_aggregate(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1],
-                                                  int(id_base), float(beta), _ptr(out), 1))
-        return out
+        return self._aggregate(_lib.lib().hb_index_aggregate, q, idx, dist, beta, id_base)
 
     def aggregate_partial(self, q, idx, dist, norms_all: torch.Tensor, beta: float = 0.02, id_base: int = 0):
         """Label-sharded aggregation: the softmax-weighted label sum over the neighbours THIS index owns (global ids id_base ..),
         with the weights of the full neighbour list (norms_all: the bank-row norms of all rows, global ids from 0).  The sum
         over the shards (an all-reduce) is label_hat."""
-        assert q.is_cuda and idx.is_cuda and dist.is_cuda and norms_all.is_cuda
-        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous(); norms_all = norms_all.contiguous().float()
-        if self.ntotal == 0:                 # an empty shard owns no neighbour
-            return torch.zeros((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
-        out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().hb_index_aggregate_partial(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base),
-                                                         float(beta), _ptr(norms_all), norms_all.shape[0], _ptr(out)))
-        return out
+        return self._aggregate_partial(_lib.lib().hb_index_aggregate_partial, q, idx, dist, norms_all, beta, id_base)
 
-    # k beyond 256: the hb_bigk_* twins of the three methods above (same arguments, same results, for k <= 256 the same bits; k <= 2048)
     def search_aggregate_bigk(self, q, k: int, beta: float = 0.02, id_base: int = 0, want_neighbours: bool = False):
-        on_dev, q = self._as_f32(q)
-        nq = q.shape[0]
-        new = (lambda shape, dt: torch.empty(shape, dtype=dt, device=q.device)) if on_dev else \
-            (lambda shape, dt: np.empty(shape, dtype=np.int64 if dt == torch.int64 else np.float32))
-        out = new((nq, self.num_classes), torch.float32)
-        idx = new((nq, k), torch.int64) if want_neighbours else None
-        dist = new((nq, k), torch.float32) if want_neighbours else None
-        _lib.check(_lib.lib().hb_bigk_search_aggregate(self._h, _ptr(q), nq, int(k), int(id_base), float(beta),
-                                                        _ptr(out), _ptr(idx), _ptr(dist), int(on_dev)))
-        return (out, idx, dist) if want_neighbours else out
+        return self._search_aggregate(_lib.lib().hb_bigk_search_aggregate, q, k, beta, id_base, want_neighbours)
 
     def aggregate_bigk(self, q, idx, dist, beta: float = 0.02, id_base: int = 0):
-        assert q.is_cuda and idx.is_cuda and dist.is_cuda
-        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous()
-        out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().hb_bigk_aggregate(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1],
-                                                 int(id_base), float(beta), _ptr(out), 1))
-        return out
+        return self._aggregate(_lib.lib().hb_bigk_aggregate, q, idx, dist, beta, id_base)
 
     def aggregate_partial_bigk(self, q, idx, dist, norms_all: torch.Tensor, beta: float = 0.02, id_base: int = 0):
-        assert q.is_cuda and idx.is_cuda and dist.is_cuda and norms_all.is_cuda
-        q = q.contiguous().float(); idx = idx.contiguous(); dist = dist.contiguous(); norms_all = norms_all.contiguous().float()
-        if self.ntotal == 0:                 # an empty shard owns no neighbour
-            return torch.zeros((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
-        out = torch.empty((q.shape[0], self.num_classes), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().hb_bigk_aggregate_partial(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist), idx.shape[1], int(id_base),
-                                                        float(beta), _ptr(norms_all), norms_all.shape[0], _ptr(out)))
-        return out
+        return self._aggregate_partial(_lib.lib().hb_bigk_aggregate_partial, q, idx, dist, norms_all, beta, id_base)
 
     # evaluation grids (hb_index_aggregate_grid / hb_index_search_aggregate_grid, csrc/hbird_grid.hip): every (k, beta) of a grid from ONE list
     # per query -- the best k of a query are the first k entries of its best k_max, bit for bit, and beta only enters after the search
@@ -317,11 +301,9 @@ class HipFlatIndex:
         on_dev, q = self._as_f32(q)
         nq, kmax, c = q.shape[0], plan.ks[-1], self.num_classes
         if len(plan.launches) == 1 and kmax <= MAX_K:
-            new = (lambda shape, dt: torch.empty(shape, dtype=dt, device=q.device)) if on_dev else \
-                (lambda shape, dt: np.empty(shape, dtype=np.int64 if dt == torch.int64 else np.float32))
-            out = new((len(plan.configs), nq, c), torch.float32)
-            idx = new((nq, kmax), torch.int64) if want_neighbours else None
-            dist = new((nq, kmax), torch.float32) if want_neighbours else None
+            out = _new(q, (len(plan.configs), nq, c), torch.float32)
+            idx = _new(q, (nq, kmax), torch.int64) if want_neighbours else None
+            dist = _new(q, (nq, kmax), torch.float32) if want_neighbours else None
             ka, ba = (ctypes.c_int * len(plan.ks))(*plan.ks), (ctypes.c_float * len(plan.betas))(*plan.betas)
             _lib.check(_lib.lib().hb_index_search_aggregate_grid(self._h, _ptr(q), nq, int(id_base), ka, len(plan.ks), ba, len(plan.betas),
                                                                   _ptr(out), _ptr(idx), _ptr(dist), int(on_dev)), ValueError)
@@ -345,26 +327,18 @@ class HipFlatIndex:
 
     def reconstruct(self, ids, id_base: int = 0):
         on_dev = isinstance(ids, torch.Tensor) and ids.is_cuda
-        if on_dev:
-            ids = ids.contiguous().to(torch.int64)
-            out = torch.empty((ids.numel(), self.d), dtype=torch.float32, device=ids.device)
-        else:
-            ids = np.ascontiguousarray(np.asarray(ids), dtype=np.int64)
-            out = np.empty((ids.size, self.d), dtype=np.float32)
+        ids = ids.contiguous().to(torch.int64) if on_dev else np.ascontiguousarray(np.asarray(ids), dtype=np.int64)
         n = ids.numel() if on_dev else ids.size
+        out = _new(ids, (n, self.d), torch.float32)
         _lib.check(_lib.lib().hb_index_reconstruct(self._h, _ptr(ids), n, int(id_base), _ptr(out), int(on_dev)))
         return out
 
     def gather_labels(self, ids):
         on_dev = isinstance(ids, torch.Tensor) and ids.is_cuda
         c = self.num_classes
-        if on_dev:
-            ids = ids.contiguous().to(torch.int64)
-            out = torch.empty((ids.numel(), c), dtype=torch.float32, device=ids.device)
-        else:
-            ids = np.ascontiguousarray(np.asarray(ids), dtype=np.int64)
-            out = np.empty((ids.size, c), dtype=np.float32)
+        ids = ids.contiguous().to(torch.int64) if on_dev else np.ascontiguousarray(np.asarray(ids), dtype=np.int64)
         n = ids.numel() if on_dev else ids.size
+        out = _new(ids, (n, c), torch.float32)
         _lib.check(_lib.lib().hb_index_gather_labels(self._h, _ptr(ids), n, 0, _ptr(out), int(on_dev)))
         return out
 

@@ -1,6 +1,6 @@
-"""K5 (label aggregation, csrc/hbird_aggregate.hip) on every code path against a float64 restatement of its contract.
+"""K5 (label aggregation, csrc/hbird_aggregate.hip; the body is k5_body of csrc/hbird_k5_dev.h) on every code path against a float64 restatement of its contract.
 
-hb_launch_aggregate picks one of three bodies of aggregate_kernel: the (neighbour group, class) form for C <= 32, the 16-byte gather
+hb_launch_aggregate (its table: hb_k5_table_choose) picks one of three bodies of aggregate_kernel: the (neighbour group, class) form for C <= 32, the 16-byte gather
 of uint16 count rows (32 < C <= 512, P <= 2048, row stride a multiple of 8, 16-byte aligned base) and the generic loop over 64-class
 chunks.  Every case below names the body it is meant to reach; tests/test_post_agg_coverage_cpu.py checks each name against the
 dispatch predicates and that the list reaches every body with every table form.

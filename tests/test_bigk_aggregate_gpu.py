@@ -1,4 +1,4 @@
-"""K5 beyond 256 neighbours (aggregate_bigk_kernel, csrc/hbird_bigk.hip) through HipFlatIndex.aggregate_bigk / aggregate_partial_bigk /
+"""K5 beyond 256 neighbours (aggregate_bigk_kernel, csrc/hbird_aggregate.hip: k5_body of csrc/hbird_k5_dev.h on dynamic LDS) through HipFlatIndex.aggregate_bigk / aggregate_partial_bigk /
 search_aggregate_bigk.
 
 Inputs, the float64 reference and its bound are those of tests/test_aggregate_paths_gpu.py: `_run_case` builds the index of a case in

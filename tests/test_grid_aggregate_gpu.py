@@ -1,4 +1,5 @@
-"""K5 over a grid of (k, beta) configurations from one neighbour list per query (aggregate_grid_kernel, csrc/hbird_grid.hip) through
+"""K5 over a grid of (k, beta) configurations from one neighbour list per query (aggregate_grid_kernel, csrc/hbird_grid.hip; neighbour
+resolution and count decode shared with aggregate_kernel in csrc/hbird_k5_dev.h) through
 HipFlatIndex.aggregate_grid / search_aggregate_grid.
 
 Configuration (k, beta) is `aggregate` applied to the first k POSITIONS of the list, whatever they hold, and must have its bits.  Inputs,

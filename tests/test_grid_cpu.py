@@ -52,7 +52,7 @@ def test_grid_entries_are_declared_exported_bound_and_documented():
     assert [a for _, a in decl["hb_index_search_aggregate_grid"][1]] == ["ix", "q", "nq", "id_base", "ks", "nk", "betas", "nb", "out", "out_idx_opt",
                                                                          "out_dist_opt", "io_on_device"]
     assert int(re.search(r"#define\s+HB_GRID_MAX_CONFIGS\s+(\d+)", header).group(1)) == _lib.GRID_MAX_CONFIGS == 16
-    # the new unit is built, and stays out of the units whose resource baselines are pinned
+    # the unit is built, and stays out of the kNN units (its resource rows are pinned with K5's: K5_UNITS, test_kernel_resources_cpu.py)
     mk = open(os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc", "Makefile")).read()
     assert "hbird_grid.hip" in re.search(r"^SRCS\s*=(.*)$", mk, flags=re.M).group(1)
     assert "hbird_grid" not in re.search(r"^KNN_UNITS\s*=(.*)$", mk, flags=re.M).group(1)

@@ -1,4 +1,4 @@
-"""Spill guard: every shipped kNN kernel instantiation is held to the committed register / spill / scratch baseline.
+"""Spill guard: every shipped kNN and K5 kernel instantiation is held to the committed register / spill / scratch baseline.
 No test fails when a header change for ONE kernel pushes ANOTHER over its scalar registers -- it only gets slower (round 2: +12 % at
 k = 90 from 16 reloads of spilled SGPRs per stage) -- so the build leaves hipcc's per-kernel resource report in lib/build/ (untracked) and this test
 compares it with tests/golden/kernel_resources.json (rewrite it with `python tools/kernel_resources.py --write-baseline` when a
@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 @pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))),
-                    reason="needs hipcc: the resource report is a by-product of compiling the kNN units")
+                    reason="needs hipcc: the resource report is a by-product of compiling the kNN and K5 units")
 def test_no_kernel_spills_more_than_the_baseline():
     subprocess.run(["make", "-C", os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc"), "-j", "8"], check=True,
                    stdout=subprocess.PIPE, stderr=subprocess.STDOUT)          # a no-op when the library is up to date
@@ -40,6 +40,20 @@ def test_no_kernel_spills_more_than_the_baseline():
         for f in ("sgpr_spill", "vgpr_spill", "scratch"):
             if d.get(f, 0) > b.get(f, 0):
                 problems.append(f"{k}: {f} {d.get(f, 0)} > baseline {b.get(f, 0)}")
+    # K5: aggregate_kernel, aggregate_bigk_kernel and the aggregate_grid_kernel instantiations share hbird_k5_dev.h; every one of them is
+    # held to the figures of the hand-copied kernels it replaced -- no more registers, spills or scratch, no fewer waves per SIMD
+    k5 = [k for k in now if k.startswith("aggregate_")]
+    assert len(k5) >= 12, f"resource reports of the K5 units missing or unparsed: {sorted(now)}"
+    for k in k5:
+        if k not in base:
+            problems.append(f"{k}: not in the baseline (python tools/kernel_resources.py --write-baseline)")
+            continue
+        d, b = now[k], base[k]
+        for f in ("vgpr", "agpr", "sgpr_spill", "vgpr_spill", "scratch"):
+            if d.get(f, 0) > b.get(f, 0):
+                problems.append(f"{k}: {f} {d.get(f, 0)} > baseline {b.get(f, 0)}")
+        if d.get("waves_per_simd", 0) < b["waves_per_simd"]:
+            problems.append(f"{k}: occupancy {d.get('waves_per_simd')} < {b['waves_per_simd']} waves per SIMD")
     assert not problems, "\n".join(problems)
     # the two kernels the bench times keep their stage loops free of scratch traffic beyond these few bytes (prologue / segment ends)
     assert now["knn_fused_bd_kernel<false, true, false>"]["scratch"] <= 36 and now["knn_f16v2_kernel<4>"]["scratch"] == 0

@@ -12,15 +12,15 @@ import oracle
 import test_aggregate_paths_gpu as agg
 import test_post_paths_gpu as post
 
-# ---------------------------------------------------------------- K5: hb_launch_aggregate (csrc/hbird_aggregate.hip)
+# ---------------------------------------------------------------- K5: hb_launch_aggregate (csrc/hbird_aggregate.hip, body in csrc/hbird_k5_dev.h)
 
-AGG_LUT = 2048                                     # hbird_aggregate.hip:25
+AGG_LUT = 2048                                     # K5_LUT of hbird_k5_dev.h
 
 
 def agg_table(form, C):
     """(uint16?, row stride in elements, 16-byte aligned base?, P) of a table form.
-    Own rows: hbird_aggregate.hip:173-176 with lab_stride() = counts padded to 8 (hbird_internal.h:49), device allocations aligned.
-    Borrowed rows: hbird_aggregate.hip:192-196 -- dense [n, C], stride C."""
+    Own rows: hb_k5_table_choose (hbird_aggregate.hip) with lab_stride() = counts padded to 8 (hbird_internal.h), device allocations aligned.
+    Borrowed rows: its `ext_labels || ext_labels16` branch -- dense [n, C], stride C."""
     P = agg.FORM_P[form]
     if form == "own_f32":
         return False, C, True, 0
@@ -32,8 +32,8 @@ def agg_table(form, C):
 
 
 def agg_branch(form, C):
-    """aggregate_kernel's body: C <= 32 first (hbird_aggregate.hip:91), then `U16 && wide` (:114) with wide_ok (:180-182) --
-    stride % 8 == 0, 16-byte aligned base, 0 < P <= AGG_LUT, 32 < C <= 512 -- else the generic loop (:150)."""
+    """aggregate_kernel's body (k5_body, hbird_k5_dev.h): C <= 32 first, then `U16 && wide` with hb_k5_table_choose's `wide` --
+    stride % 8 == 0, 16-byte aligned base, 0 < P <= K5_LUT, 32 < C <= 512 -- else the generic loop."""
     u16, stride, aligned, P = agg_table(form, C)
     if C <= 32:
         return "grouped"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Registers / spills / scratch of every kNN kernel, from the resource reports the build leaves in open-hummingbird-eval_amd/lib/
-(untracked lib/build/: csrc/Makefile compiles the kNN units with -Rpass-analysis=kernel-resource-usage).
+"""Registers / spills / scratch of every kNN and K5 kernel, from the resource reports the build leaves in open-hummingbird-eval_amd/lib/
+(untracked lib/build/: csrc/Makefile compiles the kNN units, hbird_aggregate and hbird_grid with -Rpass-analysis=kernel-resource-usage).
 
 usage: kernel_resources.py                  print one line per kernel
        kernel_resources.py --write-baseline  also rewrite tests/golden/kernel_resources.json (the spill guard's baseline:
