@@ -282,6 +282,21 @@ int hb_last_search_path(const hb_index_t* ix, int* path, int* reason);
 int hb_exact_screen_replay(int setting, int pinned, int env_off, int k, int ceiling, int64_t rows, int64_t nq, int d, int64_t stages_per_wg,
                            int overflow, int have_copy, int declined, uint64_t free_bytes, uint64_t total_bytes, uint64_t bank_bytes,
                            uint64_t copy_bytes, int* why);
+/* hb_knn_plan_replay: the launcher's SHAPE PLAN for one imagined search without a GPU (tests; csrc/hbird_calibrate.cpp: hb_knn_plan_shape /
+ * _clusters / _kernel) -- everything hb_index_search derives from the search's sizes and the index's override fields once the path is known.
+ * in[0..22] (n_in >= 23): 0 f16 (the screen's final decision), 1 wide_first (adaptive use: one pass with k' = 256), 2 esc (0 a caller's search,
+ * 1 the second fp16 pass, 2 the fp32 search of what is left), 3 ceil (a later pass of a search with k > 256), 4 k, 5 nq, 6 rows, 7 g8 (fp32
+ * stages per tile = padded D / 8), 8 padded D, 9 padded D of the fp16 copy, 10 CUs, 11 / 12 workgroups and panel of hb_index_set_tuning (0 =
+ * automatic), 13 / 14 cluster_q / cluster_b and 20 sync_lag of hb_index_set_cluster, 15 variant, 16 small_limit_stages and 17 phases of
+ * hb_index_set_search_options, 18 the mode of hb_index_set_xcd_weights, 19 that of hb_index_set_cluster_sharing, 21 / 22 the fp32 family's
+ * measured cluster decision (state 0 measuring with, 1 measuring without, 2 decided; choice 1 kept, 0 dropped); optional in[23]: the workgroups
+ * of a cached work list (0 / absent: those of a list built for this search, at most one per pair).
+ * out[0..18] (n_out >= 19): 0 kc (candidates per query), 1 wide (pools), 2 klw (pool / list capacity), 3 small_pools, 4 / 5 query / bank tiles,
+ * 6 workgroups, 7 kernel family (1 = fp16), 8 balance (uneven XCD shares apply), 9 / 10 cluster shape, 11 auto_cluster (the fp32 kernel's
+ * automatic shape), 12 panel, 13 phased, 14 xs (XCD-level query sharing), 15 lag, 16 the kernel -- 0 fp16 candidate kernel; LDS-staged fp32
+ * kernels: 1 lists, 2 lists cold (small searches), 3 pools, 4 lists clustered, 5 pools clustered, 6 CEIL; register-resident fp32 kernels: 8 + 4
+ * wide + 2 clustered + 1 small --, 17 the work list's workgroups, 18 small.  Negative: bad arguments. */
+int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int n_out);
 /* Number of queries of the last fp16-mode search that needed the exact fp32 re-search. */
 int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n);
 /* What happens to a query whose certificate fails.  mode 0 (default): ESCALATION -- the failing queries, compacted, get a second fp16 pass

@@ -163,6 +163,127 @@ bool hb_screen_choose(const hb_screen_in& in, int* why) {
     return screen;
 }
 
+// ---- the shape plan of one search (hbird_calibrate.h) -----------------------------------------------------------------------------------
+long long hb_stages_per_wg(long long nqt, long long nbt, int workgroups, int stages_per_tile) {
+    return nqt * nbt / std::max(1, workgroups) * stages_per_tile;
+}
+long long hb_stages_per_busy_wg(long long nqt, long long nbt, int workgroups, int stages_per_tile) {
+    const long long pairs = nqt * nbt;
+    return pairs / std::max<long long>(1, std::min<long long>(workgroups, pairs)) * stages_per_tile;
+}
+
+void hb_knn_plan_shape(const hb_knn_plan_in& in, hb_knn_plan& p) {
+    const int k = in.k;
+    const bool f16 = in.f16, ceil = in.ceil;
+    // fp16 mode: the fused kernel collects kc >= 2k candidates, the fp32 chain arithmetic re-ranks them
+    // k' = 2k, at least 64 (rounded up to 8, not to 64 as until round 4: the candidate kernel's time is linear in k' -- 300,000 x 768, 21,904
+    // queries: k' = 64 / 128 / 192 / 256 -> 12.95 / 15.85 / 20.7 / 25.0 ms -- so k = 33 paid for 128 candidates where it needs 66)
+    p.kc = f16 ? (in.esc == 1 || in.wide_first ? 256 : std::min(256, std::max(64, (2 * k + 7) / 8 * 8))) : k;     // (the second pass: the widest list the re-rank takes)
+    // Small searches (few stages per workgroup) on the kernel with register-resident query fragments run on POOLS even for k <= 32:
+    // phased, with the bisection cold start and the scan epilogue (hbird_knn_bd.hip <WIDE, COLD>) a pool takes a tile's survivors in one
+    // drain, a sorted LDS list one wave-cooperative insertion each.  Same box, kernel ms, lists / pools, k = 30: 50,176 x 384 x 12,544
+    // queries 4.61 / 4.13 (k = 32: 4.50 / 3.84), x 21,904 queries 7.04 / 6.52, 50,176 x 768 12.47 / 12.16, 200 k x 384 14.76 / 13.89,
+    // 300 k x 768 40.6 / 39.9, 2,074,072 x 384 140.5 / 137.4, 600 k x 1024 105.8 / 105.3, 1.25 M x 768 286.0 / 286.7, 2.5 M x 768
+    // 573.5 / 571.5, 20 k x 384 x 784 queries 0.59 / 0.26, 100 k x 384 x 196 queries 0.61 / 0.26; k = 5 at 50,176 x 384 3.61 / 3.68 and
+    // k = 1 at 200 k x 384 13.47 / 13.54 (few insertions anyway) -> from k = 8.  (Round 2 measured pools at 8.1 vs 5.0 ms for the first
+    // of these: unphased, radix cold start, LDS walk.)  Variant 6 keeps the lists (A/B, tests).
+    p.small_limit = in.small_limit > 0 ? in.small_limit : 400000;   // stages per workgroup (hb_index_set_search_options)
+    p.G = hb_knn_workgroups(in.force_G, in.num_cu);
+    const long long nqt = (in.nq + HB_QT - 1) / HB_QT, nbt = (in.ntotal + HB_BT - 1) / HB_BT;
+    const bool small_shape = hb_stages_per_busy_wg(nqt, nbt, p.G, in.g8) < std::min<long long>(p.small_limit, 120000);   // no gain beyond (1.25 M x 768: 157 k stages)
+    p.bd_shape = in.g8 % 4 == 0 && in.variant != 4;
+    p.small_pools = !f16 && !ceil && k >= 8 && k <= HB_KL && small_shape && p.bd_shape && (in.variant == 0 || in.variant == 3) && in.force_cq <= 1;
+    p.wide = f16 || k > HB_KL || p.small_pools || ceil;
+    // pools (k > HB_KL): capacity >= 2 kc so that a compaction is paid for by >= kc cheap appends
+    // (smaller / larger pools measure the same on the fp16 candidate kernel: kc + 64, kc + 192)
+    p.klw = p.wide ? std::min(HB_POOL_MAX, (std::max(2 * p.kc, p.kc + 128) + 63) / 64 * 64) : HB_KL;
+    // (tile counts as int from here on, as the work list holds them: the same values for every bank and query set of up to (2^31 - 1) x 256 rows)
+    p.nqt = (int)nqt; p.nbt = (int)nbt;
+    // per-XCD work shares (hb_xcd_calibrate, hbird_knn.hip; read BEFORE the cluster shape is chosen: the calibration also decides whether the fp32 clusters stay): calibrated for fp32 searches from 30,000 stages per workgroup (30-60 ms of kernel; from 150,000 until late in
+    // round 5: cfg-2's 2 M x 384 bank went without, 135.3 -> 134.7 ms with; phased searches gain in their last phase only);
+    // shares given by the caller (mode 2) apply to searches of any size, both kernel families (tests/fuzz_small.py FUZZ_XCD=1)
+    p.fam = f16 ? 1 : 0;
+    p.balance = p.G % 8 == 0 && (in.xcd_balance == 2 || (in.xcd_balance == 0 && hb_stages_per_wg(p.nqt, p.nbt, p.G, in.g8) >= 30000));
+    p.calibrated = p.balance && in.xcd_balance == 0;
+}
+
+void hb_knn_plan_clusters(const hb_knn_plan_in& in, hb_knn_plan& p) {
+    const bool f16 = in.f16;
+    const int nqt = p.nqt, nbt = p.nbt, G = p.G;
+    // L2-sharing clusters (hb_index_set_cluster; automatic shapes below): q x b workgroups of one XCD walk the same bank /
+    // query tiles within `lag` stages of each other, so one L2 fill serves several.  Neither kernel is bound by the fabric
+    // (the fp32 one by the matrix pipe, the fp16 candidate kernel by its LDS-DMA copies and the power the chip grants it:
+    // profiles/LABBOOK.md, profiles/r02), so what they buy is traffic, and time only for the fp16 kernel (-8 %).  The 4-wave variant
+    // does not know strided segments.
+    int cq = 1, cb = 1;
+    p.auto_cluster = false;      // fp32: the cluster shape of this search is the automatic choice (kept only where it measures faster)
+    if (in.ceil) { cq = 1; cb = 1; }
+    else if (in.force_cq > 0 && in.force_cb > 0) { cq = in.force_cq; cb = in.force_cb; }
+    // fp16 candidate kernel: from 70 k stages per workgroup up (round 4: with the lean stage loop and the XCD-level query sharing the
+    // clusters pay much earlier than the 400 k of round 3).  Same box, kernel ms (phased), none vs automatic: 10 M x 768 321 / 284,
+    // 2.5 M x 768 (157 k stages) 83.0 / 77.5, 5 M x 384 (157 k) 85.3 / 80.3, 1.25 M x 768 (79 k) 43.7 / 41.8, 5 M x 768 x 12,544 queries
+    // (179 k; 49 query tiles: 4 x 2) 94.0 / 88.2 -- but 2,074,072 x 384 (37 k) 21.3 / 22.8: more slots, shorter segments
+    // (profiles/r04/f16_cluster_threshold.txt)
+    else if (f16 && in.variant == 0 && in.force_cq == 0) {
+        if (hb_stages_per_wg(nqt, nbt, G, in.dp16 / 16) >= 70000) hb_default_cluster(nqt, nbt, G, false, &cq, &cb);
+    }
+    // fp32: only beside the kernel with register-resident query fragments (its sync is free of spills), and only for the
+    // biggest searches: 2 x 4 clusters cut the fabric reads by 60 % (10 M x 768: 4.79 -> 1.93 TB per search, L2 hit rate
+    // 10 % -> 63 %) but the kernel is bound by the matrix pipe, so all they can do for the time is cost little -- measured
+    // (same box, kernel ms, none vs 2 x 4): 10 M x 768 2280 vs 2298 (+0.8 %), 5 M x 1024 1528 vs 1531 (+0.2 %), but
+    // 1.25 M x 768 289.3 vs 293.9 (+1.6 %), 2 M x 384 142.3 vs 146.4 (+2.9 %): more slots, shorter segments.  Automatic from
+    // one million stages per workgroup up (8 M rows at D = 768); hb_index_set_cluster(ix, 1, 1, 0) turns them off, (ix, 2, 4, -1) forces them.
+    // Round 6: ... and only where they MEASURE faster on this box (hb_xcd_calibrate: two calibrated launches with, two without, the faster
+    // form stays); without the calibration's stamps (equal or given shares) they stay on.
+    else if (!f16 && !p.wide && in.variant == 0 && in.force_cq == 0 && in.g8 % 4 == 0 && hb_stages_per_wg(nqt, nbt, G, in.g8) >= 1000000) {
+        p.auto_cluster = true;
+        const bool measured = in.xcd_balance == 0 && G % 8 == 0;
+        // (a decision, once made, holds whatever the share mode; before it: on while measuring with, off while measuring without)
+        if (in.cl_state == 2 ? in.cl_choice != 0 : (!measured || in.cl_state == 0)) hb_default_cluster(nqt, nbt, G, true, &cq, &cb);
+    }
+    if ((long long)nqt * nbt < G || cq * cb > HB_CLUSTER_MAX || G % (8 * cq * cb) != 0) { cq = 1; cb = 1; }
+    p.cq = cq; p.cb = cb;
+    const size_t tile_bytes = (size_t)HB_BT * in.dp * 4;
+    p.panel = in.force_panel > 0 ? in.force_panel : hb_default_panel(nqt, std::min<long long>(G, (long long)nqt * nbt), tile_bytes, cq, cb);
+    // phased searches (pools only: "Phased searches" above hb_launch_knn); hb_index_set_search_options(ix, 0, ...) turns them off (A/B, tests)
+    // (a nested search of uncertified queries starts from seeded floors: phases would only add boundaries -- and with one query tile over 256
+    // workgroups the floors between them go through the merge kernels: 70 ms for two queries)
+    p.phased = p.wide && in.phases_on && in.esc == 0;
+    // XCD-level sharing of the query tiles (hb_build_clustered): automatic for the fp16 candidate kernel -- same box, 10 M x 768, 8 x 1
+    // clusters: 302.7 -> 291.5 ms and 0.97 -> 0.52 TB of L2-miss traffic per search (L2 hit rate 0.60 -> 0.78); the fp32 kernel's 2 x 4
+    // clusters lose 1.6 % with it (2298 -> 2334 ms: 1600 slots instead of 592, and its 768 KiB query tiles do not stay in L2 beside
+    // sixteen bank streams anyway: 1.95 -> 1.62 TB) -> off there (profiles/r04/xs_*.txt)
+    p.xs = cq * cb > 1 && (in.xcd_share == 2 || (in.xcd_share == 0 && f16));
+    // soft-sync lag in stages: the members stay inside the L2's reach (4 MiB per XCD: tens of fp32 k8 stages); 0 disables
+    // the sync (the members then share only while they happen to run together: 36 % instead of 53 % L2 hits)
+    p.lag = cq * cb > 1 ? (in.sync_lag >= 0 ? in.sync_lag : 16) : 0;
+}
+
+void hb_knn_plan_kernel(const hb_knn_plan_in& in, int sched_G, hb_knn_plan& p) {
+    const bool clustered = p.cq * p.cb > 1;
+    // Few stages per workgroup: a slot sees few rows, so its cold start (the first tile inserts all 256 rows of every
+    // query) and its insertions (k ln(rows / k) per query) are a visible share of the search -> the instantiations with the
+    // cold start, the scan epilogue (register queue + immediate inserts) and the per-tile exchange of
+    // threshold floors (hbird_knn_dev.h: small_floor_*).  Same box, kernel ms, LDS-staged small / B-direct plain / B-direct small:
+    // 50,176 x 384: 4.86 / 6.76 / 4.62 (round 1: 6.3; 0.49 -> 0.665 of the fp32 MFMA peak); 200 k x 384: 15.9 / 17.7 / 15.1;
+    // 300 k x 768: 74.7 / 72.8 / 70.7; 2 M x 384: 149.3 / 143.1 / 142.3; 1.25 M x 768: 305.9 / 291.2 / 289.8; 2.5 M x 768 (315 k
+    // stages per workgroup): 612.7 / 579.1 / 579.6 -> small below 400 k stages.  The big searches keep the plain
+    // instantiations: at 10 M x 768 the extra code costs 0.3 % (same-box A/B).
+    // lists: cold_fn / <false, false, COLD>; pools: <WIDE, false, COLD> -- for k > 32 only below 50 k stages (k = 90: 50,176 x 384 4.78 -> 4.45 ms,
+    // k = 64 at 300 k x 768 41.9 -> 40.3, but 2,074,072 x 384 (74 k stages) 142.0 -> 142.7)
+    const long long stages_per_wg = hb_stages_per_wg(p.nqt, p.nbt, sched_G, in.g8);
+    p.small = !in.f16 && !clustered && stages_per_wg < (in.k > HB_KL ? std::min<long long>(p.small_limit, 50000) : p.small_limit);
+    // The query fragments straight into registers (hbird_knn_bd.hip): -3.8 % kernel time at 10 M x 768 (0.895 -> 0.93 of the
+    // fp32 MFMA peak), same bits.  Default for the big LDS-list searches whose stage count per tile is a multiple of four
+    // (D = 384, 768, 1024, ...); variant 3 forces it wherever it applies (tests), variant 4 keeps the LDS-staged kernel.
+    if (in.f16) p.kernel = HB_KERNEL_F16;
+    else if (in.ceil) p.kernel = HB_KERNEL_CEIL;
+    else if (p.bd_shape && (in.variant == 0 || in.variant == 3 || in.variant == 6)) p.kernel = HB_KERNEL_BD + (p.wide ? 4 : 0) + (clustered ? 2 : 0) + (p.small ? 1 : 0);
+    else if (clustered) p.kernel = p.wide ? HB_KERNEL_POOLS_CL : HB_KERNEL_LISTS_CL;
+    else if (p.small && !p.wide) p.kernel = HB_KERNEL_LISTS_COLD;
+    else p.kernel = p.wide ? HB_KERNEL_POOLS : HB_KERNEL_LISTS;
+}
+
 // ---- test hooks (no GPU): a calibration state fed with synthetic stamp sets -----------------------------------------------------------
 struct hb_calibration { hb_xcd_state st; int fam; };
 extern "C" void* hb_calibration_new(int fp16_kernel) { hb_calibration* h = new hb_calibration(); h->fam = fp16_kernel ? 1 : 0; return h; }
@@ -215,4 +336,26 @@ extern "C" int hb_exact_screen_replay(int setting, int pinned, int env_off, int 
     in.stages_per_wg = stages_per_wg; in.overflow = overflow != 0; in.have_copy = have_copy != 0; in.declined = declined != 0;
     in.mem_known = true; in.free_b = free_bytes; in.total_b = total_bytes; in.bank_b = bank_bytes; in.copy_b = copy_bytes;
     return hb_screen_choose(in, why) ? 1 : 0;
+}
+// the launcher's shape plan for one imagined search (include/hbird_hip.h: the slots)
+extern "C" int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int n_out) {
+    if (!in || !out || n_in < 23 || n_out < 19) return -1;
+    if (in[4] < 1 || in[5] < 0 || in[6] < 0 || in[7] < 1 || in[8] < 1 || in[9] < 16 || in[10] < 1 || (n_in > 23 && in[23] < 0)) return -1;
+    hb_knn_plan_in pin;
+    pin.f16 = in[0] != 0; pin.wide_first = in[1] != 0; pin.esc = (int)in[2]; pin.ceil = in[3] != 0;
+    pin.k = (int)in[4]; pin.nq = in[5]; pin.ntotal = in[6]; pin.g8 = (int)in[7]; pin.dp = (int)in[8]; pin.dp16 = (int)in[9]; pin.num_cu = (int)in[10];
+    pin.force_G = (int)in[11]; pin.force_panel = (int)in[12]; pin.force_cq = (int)in[13]; pin.force_cb = (int)in[14]; pin.variant = (int)in[15];
+    pin.small_limit = in[16]; pin.phases_on = (int)in[17]; pin.xcd_balance = (int)in[18]; pin.xcd_share = (int)in[19]; pin.sync_lag = (int)in[20];
+    pin.cl_state = (int)in[21]; pin.cl_choice = (int)in[22];
+    hb_knn_plan p;
+    hb_knn_plan_shape(pin, p);
+    hb_knn_plan_clusters(pin, p);
+    // the workgroups of a work list built for this search (hb_build_schedule: at most one per pair), or the caller's (a cached list)
+    const long long pairs = (long long)p.nqt * p.nbt;
+    const int sched_G = n_in > 23 && in[23] > 0 ? (int)in[23] : pairs < p.G ? (int)std::max<long long>(1, pairs) : p.G;
+    hb_knn_plan_kernel(pin, sched_G, p);
+    out[0] = p.kc; out[1] = p.wide; out[2] = p.klw; out[3] = p.small_pools; out[4] = p.nqt; out[5] = p.nbt; out[6] = p.G; out[7] = p.fam; out[8] = p.balance;
+    out[9] = p.cq; out[10] = p.cb; out[11] = p.auto_cluster; out[12] = p.panel; out[13] = p.phased; out[14] = p.xs; out[15] = p.lag; out[16] = p.kernel;
+    out[17] = sched_G; out[18] = p.small;
+    return 0;
 }

@@ -5,6 +5,10 @@
 #include <array>
 #include <stdint.h>
 #include "../../include/hbird_hip.h"
+#include "hbird_schedule.h"
+
+#define HB_POOL_MAX 512  // largest candidate pool per (slot, query) in global memory (k > HB_KL)
+#define HB_KL 32         // per-query list capacity kept in LDS (k <= HB_KL on the fused path)
 
 // What one launch's stamps say (wg_stamp, hbird_knn_dev.h: per block, at its start and at its end, {100 MHz real-time counter (low word),
 // XCC id, shader-cycle counter lo, hi}).
@@ -85,3 +89,57 @@ struct hb_screen_in {
     uint64_t free_b = 0, total_b = 0, bank_b = 0, copy_b = 0;
 };
 bool hb_screen_choose(const hb_screen_in& in, int* why);     // -> the screen (true) or the fp32 kernel; *why = HB_WHY_*
+
+// ---- the shape plan of one search (hb_launch_knn, hbird_knn.hip) ------------------------------------------------------------------------
+// Everything the launcher derives from the search's sizes and the index's override fields before it touches the device: which kernel runs,
+// on pools or lists, with which clusters, phased or not.  Plain values in, plain values out (CPU tests: hb_knn_plan_replay, tests/
+// test_knn_plan_cpu.py).  Three steps, because two facts of the launcher sit between them:
+//   hb_knn_plan_shape     what needs only the sizes: kc, pools or lists, the grid, whether the shares are calibrated (balance);
+//   -- the launcher runs hb_xcd_calibrate where `balance` says so: it may flip cl_state / cl_choice, which the caller then copies into `in` --
+//   hb_knn_plan_clusters  the cluster shape from the state the calibration left, and what hangs on it: panel, phased, xs, lag;
+//   -- the launcher builds (or finds cached) the work list: a list has fewer workgroups than G when there are fewer pairs, and a cached list
+//      of the nested searches may date from another hb_index_set_tuning --
+//   hb_knn_plan_kernel    `small` and the kernel, from the work list's own workgroup count.
+struct hb_knn_plan_in {
+    bool f16 = false;             // the final decision of the screen (hb_screen_choose, the adaptive use, the copy's upkeep)
+    bool wide_first = false;      // adaptive use: one pass with k' = 256 serves all queries
+    int esc = 0;                  // 0: a caller's search; 1: the second fp16 pass over its uncertified queries; 2: the fp32 search of what is left
+    bool ceil = false;            // a later pass of a search with k > 256
+    int k = 0;
+    int64_t nq = 0, ntotal = 0;
+    int g8 = 0, dp = 0, dp16 = 0, num_cu = 0;
+    int force_G = 0, force_panel = 0, force_cq = 0, force_cb = 0, variant = 0;
+    long long small_limit = 0;    // hb_index_set_search_options (0 = the built-in 400,000)
+    int phases_on = 1, xcd_balance = 0, xcd_share = 0, sync_lag = -1;
+    int cl_state = 0, cl_choice = 1;      // the fp32 family's measured decision about its automatic clusters (hb_xcd_state)
+};
+// The kernel of the search.  The register-resident forms (hbird_knn_bd.hip) are HB_KERNEL_BD + 4 wide + 2 clustered + 1 small.
+enum hb_knn_kernel {
+    HB_KERNEL_F16 = 0,            // the fp16 candidate kernel (hbird_knn_f16.hip)
+    HB_KERNEL_LISTS = 1, HB_KERNEL_LISTS_COLD = 2, HB_KERNEL_POOLS = 3, HB_KERNEL_LISTS_CL = 4, HB_KERNEL_POOLS_CL = 5, HB_KERNEL_CEIL = 6,      // LDS-staged (hbird_knn.hip)
+    HB_KERNEL_BD = 8
+};
+struct hb_knn_plan {
+    // hb_knn_plan_shape
+    int kc = 0; bool wide = false; int klw = 0; bool small_pools = false;
+    int nqt = 0, nbt = 0, G = 0, fam = 0; bool balance = false;
+    bool calibrated = false;      // ... and the shares are the calibration's own: the search stamps its workgroups and (a caller's) feeds hb_xcd_step
+    long long small_limit = 0; bool bd_shape = false;      // (kept for hb_knn_plan_kernel)
+    // hb_knn_plan_clusters
+    int cq = 1, cb = 1; bool auto_cluster = false; int panel = 0;
+    bool phased = false, xs = false; int lag = 0;
+    // hb_knn_plan_kernel
+    bool small = false; int kernel = HB_KERNEL_LISTS;
+};
+// "Stages per workgroup", the size by which every threshold of the launcher is stated.  Two formulas, and they differ only when there are
+// fewer pairs than workgroups:
+// ... all `workgroups` in the divisor (idle ones included: 0 stages when pairs < workgroups).  Used by the screen's automatic state
+// (hb_screen_in::stages_per_wg), `balance`, both cluster bounds (the fp16 one with dp16 / 16 stages per tile) and, with the work list's own
+// workgroup count, `small`.
+long long hb_stages_per_wg(long long nqt, long long nbt, int workgroups, int stages_per_tile);
+// ... only the workgroups that get a pair in the divisor (one tile's stages when pairs < workgroups).  Used by small_shape (lists or small pools).
+long long hb_stages_per_busy_wg(long long nqt, long long nbt, int workgroups, int stages_per_tile);
+inline int hb_knn_workgroups(int force_G, int num_cu) { return force_G > 0 ? force_G : num_cu; }
+void hb_knn_plan_shape(const hb_knn_plan_in& in, hb_knn_plan& p);
+void hb_knn_plan_clusters(const hb_knn_plan_in& in, hb_knn_plan& p);
+void hb_knn_plan_kernel(const hb_knn_plan_in& in, int sched_G, hb_knn_plan& p);

@@ -11,8 +11,7 @@
 
 // ---- tile geometry of the kNN kernel (see DESIGN.md "Data layout in HBM") -------------------
 #define HB_RT 32         // rows per fragment tile (MFMA 32x32x2)
-#define HB_POOL_MAX 512  // largest candidate pool per (slot, query) in global memory (k > HB_KL)
-#define HB_KL 32         // per-query list capacity kept in LDS (k <= HB_KL on the fused path)
+// (HB_POOL_MAX and HB_KL, the pool and list capacities: hbird_calibrate.h, beside the plan that chooses between them)
 #define HB_THREADS 512
 #define HB_WAVES 8
 #define HB_BLK 256       // floats per fragment block (32 rows x 8 k) = 1 KiB
@@ -104,11 +103,7 @@ struct hb_index {
     int64_t last_fp16_escalated = 0;                     // ... and queries whose first certificate failed (second fp16 pass, k' = 256, seeded floors)
     int fp16_escalation = 0;                             // 0 = on (automatic), 1 = off: uncertified queries go straight to the fp32 kernel (round 5)
     hb_f16_adapt f16_adapt;                              // adaptive use of use_fp16 in mode 2 (hbird_calibrate.h): moving averages of the failing shares
-    int f16_skipped = 0;
-    const float* ceil_s_dev = nullptr; const unsigned* ceil_i_dev = nullptr;    // a later pass of a search with k > 256 (hb_launch_knn_bigk)
-    char* bigk = nullptr; size_t bigk_bytes = 0;         // its workspace: one pass's lists and the ceilings
-    int esc_level = 0;                                   // inside hb_launch_knn: 0 = a caller's search, 1 = the second fp16 pass, 2 = the fp32 search of what is left
-    const float* seed_dev = nullptr;                     // per-query floors (scores) a nested search starts from
+    char* bigk = nullptr; size_t bigk_bytes = 0;         // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
     hb_schedule sched_esc; char* sched_esc_dev = nullptr; size_t sched_esc_bytes = 0;   // the nested searches' work list (the caller's stays cached)
     int score_output = 0;                                // 1: searches return ordering scores instead of distances
     int variant = 0;                                     // kernel selection for A/B runs and tests (hb_index_set_variant)

@@ -611,13 +611,28 @@ __global__ __launch_bounds__(256) void bigk_place_kernel(const int64_t* __restri
     }
 }
 
-int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
-static int hb_launch_knn_bigk(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
+static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }      // every carve-up of a workspace in this unit
+
+// What distinguishes ONE invocation of the launcher from the index's settings.  hb_launch_knn builds the level-0 call from the index; the
+// passes of a search with k > 256 (hb_launch_knn_bigk) and the re-search of uncertified queries (knn_research_failures) build a new one for
+// their nested search.  Nothing here is written to the index, so a nested search that fails leaves no trace in it.
+struct knn_call {
+    int esc = 0;                       // 0: a caller's search; 1: the second fp16 pass over its uncertified queries; 2: the fp32 search of what is left
+    const float* seed = nullptr;       // per-query floors (scores) a nested search starts from
+    const float* ceil_s = nullptr;     // a later pass of a search with k > 256: per query the ordering key of the last neighbour delivered
+    const unsigned* ceil_i = nullptr;
+    int fp16 = 0;                      // the fp16 setting in force for this call (hb_index::fp16 for a caller's search)
+    bool timed = false;                // events around the kernel launches, workgroup stamps, last_knn_ms
+    const float* q_aux = nullptr;      // [nq] chain ||q||^2 and [nq] fp32 norms of THIS call's queries
+    bool score_out = false;            // the ordering score goes out as it is, whatever the metric
+};
+static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
+
+static int hb_launch_knn_bigk(hb_index* ix, const knn_call& c, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
     if (nq == 0) return 0;
     hipStream_t s = ix->stream;
     const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_sc = al((size_t)nq * 256 * 8), o_cs = o_sc + al((size_t)nq * 256 * 4), o_ci = o_cs + al((size_t)nqp * 4), tot = o_ci + al((size_t)nqp * 4);
+    const size_t o_sc = al256((size_t)nq * 256 * 8), o_cs = o_sc + al256((size_t)nq * 256 * 4), o_ci = o_cs + al256((size_t)nqp * 4), tot = o_ci + al256((size_t)nqp * 4);
     if (ensure_bytes(&ix->bigk, &ix->bigk_bytes, tot)) return -1;
     int64_t* tmp_idx = reinterpret_cast<int64_t*>(ix->bigk);
     float* tmp_sc = reinterpret_cast<float*>(ix->bigk + o_sc);
@@ -625,31 +640,43 @@ static int hb_launch_knn_bigk(hb_index* ix, const float* q_dev, int64_t nq, int 
     unsigned* ceil_i = reinterpret_cast<unsigned*>(ix->bigk + o_ci);
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)ceil_s, 0xFF800000u, (size_t)nqp, s));      // (padding queries: nothing behind -inf)
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)ceil_i, 0xFFFFFFFFu, (size_t)nqp, s));
-    const int out_metric = ix->score_output ? 0 : ix->metric;
-    const int saved_so = ix->score_output, saved_t = ix->time_kernels;
+    const int out_metric = c.score_out ? 0 : ix->metric;
     double knn_ms = 0.0;
     int rc = 0;
     for (int col0 = 0; col0 < k && !rc; col0 += 256) {
         const int kp = std::min(256, k - col0);
-        ix->score_output = 1;                                // ordering scores: what the next pass's ceiling compares with
-        ix->ceil_s_dev = col0 ? ceil_s : nullptr; ix->ceil_i_dev = col0 ? ceil_i : nullptr;
-        rc = hb_launch_knn(ix, q_dev, nq, kp, 0, tmp_idx, tmp_sc);
-        ix->score_output = saved_so; ix->ceil_s_dev = nullptr; ix->ceil_i_dev = nullptr;
+        knn_call pass = c;
+        pass.score_out = true;                               // ordering scores: what the next pass's ceiling compares with
+        pass.ceil_s = col0 ? ceil_s : nullptr; pass.ceil_i = col0 ? ceil_i : nullptr;
+        rc = knn_search(ix, pass, q_dev, nq, kp, 0, tmp_idx, tmp_sc);
         if (rc) break;
-        if (saved_t) knn_ms += ix->last_knn_ms;
-        bigk_place_kernel<<<dim3((unsigned)((nq * kp + 255) / 256)), dim3(256), 0, s>>>(tmp_idx, tmp_sc, nq, kp, k, col0, id_base, out_metric, ix->q_aux,
+        if (c.timed) knn_ms += ix->last_knn_ms;
+        bigk_place_kernel<<<dim3((unsigned)((nq * kp + 255) / 256)), dim3(256), 0, s>>>(tmp_idx, tmp_sc, nq, kp, k, col0, id_base, out_metric, c.q_aux,
                                                                                          out_idx, out_dist, ceil_s, ceil_i);
         HB_HIP(hipGetLastError());
     }
-    if (saved_t) ix->last_knn_ms = knn_ms;
+    if (c.timed) ix->last_knn_ms = knn_ms;
     return rc;
 }
 
-// q_tiles / q_aux must already be prepared by the caller (hb_index_search).
-int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
-    if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search: k must be in [1, " + std::to_string(HB_MAX_K) + "] (faiss-gpu's limit, search_faiss.py:84-85)");
-    if (k > 256) return hb_launch_knn_bigk(ix, q_dev, nq, k, id_base, out_idx, out_dist);
-    const bool ceil = ix->ceil_s_dev != nullptr;      // a later pass of a search with k > 256: pools, the LDS-staged kernel's CEIL instantiation
+// the fp16 copy of the bank goes (the bank grew, the copy overflowed, or its allocation is about to be repeated)
+static int knn_drop_tiles16(hb_index* ix) {
+    if (ix->tiles16) HB_HIP(hipFree(ix->tiles16));
+    ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0;
+    return 0;
+}
+
+// ---- stage 1: which path serves the call, and the upkeep of the screen's two optional copies of the bank --------------------------------
+struct knn_path {
+    bool f16 = false;          // the candidate pass (the final decision: the upkeep below may still turn it off)
+    int why = HB_WHY_EXPLICIT_FP32;
+    bool automatic = false, wide_first = false;
+    int how16 = HB_F16_CHAIN;
+    bool centred = false;      // this pass runs on the centred copy
+};
+static int knn_choose_path(hb_index* ix, const knn_call& c, int64_t nq, int k, knn_path* out) {
+    knn_path& p = *out;
+    const bool ceil = c.ceil_s != nullptr;      // a later pass of a search with k > 256: pools, the LDS-staged kernel's CEIL instantiation
     // fp16 mode 2 (what the plugin's use_fp16=True selects): the candidate pass only where it pays.  Its fixed costs are per query
     // (fp16 query tiles, re-rank of k' = 2k candidates, a second merge) and per search (the phases' launches and floor kernels), what it
     // saves is proportional to the matrix work rows x queries x D: the pass runs from rows x queries x D >= 1.5e10 x (k' / 64)^2 on, and
@@ -658,278 +685,201 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     // 384: 8 k 0.41 / 0.45, 16 k 0.65 / 0.47; 1,369 x 768: 4 k 0.30 / 0.23, 16 k 0.59 / 0.48; 12,544 x 384: 4 k 0.61 / 0.52, 50 k 3.9 / 1.5, 1 M
     // 69.3 / 10.6; 21,904 x 768: 4 k 1.43 / 1.09, 1 M 242.7 / 34.3; k = 90, 12,544 x 384: 16 k 1.74 / 2.04, 32 k 3.00 / 2.49, 1 M 70.4 / 13.8.
     // (Until round 4: at least 16,384 rows and rows x queries >= 2^27.)  Same results either way.
-    const int esc = ix->esc_level;      // 0: a caller's search; 1: the second fp16 pass over its uncertified queries; 2: the fp32 search of what is left
+    const int esc = c.esc;
     // Which searches take the candidate pass is hb_screen_choose's decision (hbird_calibrate.cpp, with CPU tests): states 1 / 2 by the rule above;
     // the AUTOMATIC state (what a new index starts in) like state 2, but only for big searches -- from the 30,000 stages per workgroup at which the
     // fp32 kernels stamp and calibrate (below) --, on an index whose fp32 kernel the caller has not steered, and where the fp16 copy fits.
     hb_screen_in sin;
-    sin.setting = ix->fp16; sin.pinned = ix->fp32_pinned != 0; sin.env_off = ix->screen_env_off != 0; sin.k = k; sin.ceiling = ceil;
+    sin.setting = c.fp16; sin.pinned = ix->fp32_pinned != 0; sin.env_off = ix->screen_env_off != 0; sin.k = k; sin.ceiling = ceil;
     sin.rows = ix->ntotal; sin.nq = nq; sin.d = ix->d; sin.overflow = ix->f16_overflow != 0;
-    sin.stages_per_wg = (long long)((nq + HB_QT - 1) / HB_QT) * ((ix->ntotal + HB_BT - 1) / HB_BT) / std::max(1, ix->force_G > 0 ? ix->force_G : ix->num_cu) * ix->g8;
+    sin.stages_per_wg = hb_stages_per_wg((nq + HB_QT - 1) / HB_QT, (ix->ntotal + HB_BT - 1) / HB_BT, hb_knn_workgroups(ix->force_G, ix->num_cu), ix->g8);
     sin.have_copy = ix->tiles16 != nullptr && ix->f16_cap_rows == ix->cap_rows;
     sin.declined = ix->f16_declined_cap == ix->cap_rows;
     sin.bank_b = (uint64_t)ix->cap_rows * ix->dp * 4; sin.copy_b = (uint64_t)ix->cap_rows * ix->dp16 * 2;
-    const bool automatic = ix->fp16 == HB_FP16_AUTO;
-    int why = HB_WHY_EXPLICIT_FP32;
-    bool f16 = hb_screen_choose(sin, &why);
-    if (f16 && automatic && !sin.have_copy && nq > 0 && ix->ntotal > 0) {      // the copy has to be made: only where it leaves the device room
-        if (ix->tiles16) { HB_HIP(hipFree(ix->tiles16)); ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0; }      // (the bank grew: the old copy goes first)
+    p.automatic = c.fp16 == HB_FP16_AUTO;
+    p.f16 = hb_screen_choose(sin, &p.why);
+    if (p.f16 && p.automatic && !sin.have_copy && nq > 0 && ix->ntotal > 0) {      // the copy has to be made: only where it leaves the device room
+        if (knn_drop_tiles16(ix)) return -1;      // (the bank grew: the old copy goes first)
         size_t free_b = 0, total_b = 0;
         HB_HIP(hipMemGetInfo(&free_b, &total_b));
         sin.mem_known = true; sin.free_b = free_b; sin.total_b = total_b;
-        f16 = hb_screen_choose(sin, &why);
-        if (!f16) ix->f16_declined_cap = ix->cap_rows;
+        p.f16 = hb_screen_choose(sin, &p.why);
+        if (!p.f16) ix->f16_declined_cap = ix->cap_rows;
     }
     // ADAPTIVE use (mode 2, round 6): on a bank whose neighbours sit closer together than fp16 can tell apart -- token worlds with little
     // noise: profiles/r06/final/fp16_cliff_*.json -- most certificates fail, and passes that certify nothing are pure overhead.  The index keeps
     // moving averages of the share of queries that failed the first certificate (r1) and of the share that reached the fp32 kernel (r12):
     // r12 > 1/2 -> the fp32 kernel right away; r1 > 1/2 -> the first pass is skipped, ONE pass with k' = 256 serves all queries; every 16th
     // search walks the whole chain again, so a bank (or a query stream) that changes is noticed.  Same bits on every path.
-    bool wide_first = false;
-    int how16 = HB_F16_CHAIN;
-    if (f16 && esc == 0 && (ix->fp16 == 2 || automatic) && ix->fp16_escalation == 0) {       // (the policy itself: hbird_calibrate.cpp, with CPU tests)
-        how16 = hb_f16_choose(ix->f16_adapt);
-        if (how16 == HB_F16_FP32) { f16 = false; ix->f16_skipped = 1; why = HB_WHY_ADAPTIVE; }
-        else if (how16 == HB_F16_WIDE_FIRST) wide_first = true;
+    bool skipped = false;
+    if (p.f16 && esc == 0 && (c.fp16 == 2 || p.automatic) && ix->fp16_escalation == 0) {       // (the policy itself: hbird_calibrate.cpp, with CPU tests)
+        p.how16 = hb_f16_choose(ix->f16_adapt);
+        if (p.how16 == HB_F16_FP32) { p.f16 = false; skipped = true; p.why = HB_WHY_ADAPTIVE; }
+        else if (p.how16 == HB_F16_WIDE_FIRST) p.wide_first = true;
     }
-    if (!f16 && esc == 0) { ix->last_fp16_fallbacks = ix->f16_skipped ? nq : 0; ix->last_fp16_escalated = 0; ix->f16_skipped = 0; }      // a plain fp32 search: nothing fell back (the counters are not left over from an earlier search)
-    if (f16 && nq > 0 && ix->ntotal > 0) {
-        // bring the fp16 copy of the bank fragment tiles up to date.  A finite value beyond the fp16 range (|x| > 65504) turns
-        // into inf there and the scores into inf / NaN, which the exactness certificate cannot bound: such a bank stays on the
-        // fp32 kernel (every query counts as a fallback)
-        hipStream_t s0 = ix->stream;
-        if (!ix->f16_flag) { HB_HIP(hipMalloc((void**)&ix->f16_flag, 4)); HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s0)); }
-        if (ix->f16_cap_rows != ix->cap_rows) {
-            if (ix->tiles16) HB_HIP(hipFree(ix->tiles16));
-            ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0;
-            // states 1 / 2: the caller asked for the copy, no memory for it is the search's error.  Automatic: the copy only buys speed, so an
-            // allocation that fails all the same (the device filled up since hipMemGetInfo) is remembered for this capacity and the fp32 kernel answers
-            if (!automatic) HB_HIP(hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2));
-            else if (hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2) != hipSuccess) {
-                (void)hipGetLastError();
-                ix->tiles16 = nullptr; ix->f16_declined_cap = ix->cap_rows;
-                f16 = false; why = HB_WHY_MEMORY;
-                if (esc == 0) { ix->last_fp16_fallbacks = 0; ix->last_fp16_escalated = 0; }
-            }
-            if (ix->tiles16) {
-                HB_HIP(hipMemsetAsync(ix->tiles16, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0));
-                ix->f16_cap_rows = ix->cap_rows;
-            }
+    if (!p.f16 && esc == 0) { ix->last_fp16_fallbacks = skipped ? nq : 0; ix->last_fp16_escalated = 0; }      // a plain fp32 search: nothing fell back (the counters are not left over from an earlier search)
+    return 0;
+}
+
+// bring the fp16 copy of the bank and the re-rank's row copy up to date; may turn f16 off (with its reason)
+static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, hipStream_t s0, bool& f16, int& why) {
+    // bring the fp16 copy of the bank fragment tiles up to date.  A finite value beyond the fp16 range (|x| > 65504) turns
+    // into inf there and the scores into inf / NaN, which the exactness certificate cannot bound: such a bank stays on the
+    // fp32 kernel (every query counts as a fallback)
+    if (!ix->f16_flag) { HB_HIP(hipMalloc((void**)&ix->f16_flag, 4)); HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s0)); }
+    if (ix->f16_cap_rows != ix->cap_rows) {
+        if (knn_drop_tiles16(ix)) return -1;
+        // states 1 / 2: the caller asked for the copy, no memory for it is the search's error.  Automatic: the copy only buys speed, so an
+        // allocation that fails all the same (the device filled up since hipMemGetInfo) is remembered for this capacity and the fp32 kernel answers
+        if (!automatic) HB_HIP(hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2));
+        else if (hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            ix->tiles16 = nullptr; ix->f16_declined_cap = ix->cap_rows;
+            f16 = false; why = HB_WHY_MEMORY;
+            if (esc == 0) { ix->last_fp16_fallbacks = 0; ix->last_fp16_escalated = 0; }
         }
-        if (f16 && ix->f16_rows < ix->ntotal) {
-            const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
-            // (hb_index_set_fp16_centre: the rows as fl32(b - mu) with their per-row term, hbird_f16_centre.hip; a bank without a usable mean: the plain copy)
-            int centred = 0;
-            if (ix->fp16_centre && hb_centre_convert(ix, s0, &centred)) return -1;
-            if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, (_Float16*)ix->tiles16, ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
-            ix->f16_rows = ix->ntotal;
-            HB_HIP(hipMemcpyAsync(&ix->f16_overflow, ix->f16_flag, 4, hipMemcpyDeviceToHost, s0));
-            HB_HIP(hipStreamSynchronize(s0));
-        }
-        if (f16 && ix->f16_overflow) {
-            f16 = false; why = HB_WHY_OVERFLOW;
-            if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; }
-            if (automatic) {      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
-                HB_HIP(hipFree(ix->tiles16));
-                ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0;
-            }
-        }
-        // ... and the row-major fp32 copy for the re-rank (hbird_knn_f16.hip).  Automatic: by the bank's size (below; a 10 M x 768 bank:
-        // 30.7 GB of tiles + 15.4 GB of fp16 tiles + 30.7 GB of rows, of 288)
-        if (f16 && ix->rerank_copy != 2) {
-            const int rs = (ix->g8 * 8 + 31) / 32 * 32;
-            if (ix->rows32 && (ix->rows32_cap_rows != ix->cap_rows || ix->rows32_rs != rs)) {
-                HB_HIP(hipFree(ix->rows32));
-                ix->rows32 = nullptr; ix->rows32_cap_rows = 0; ix->rows32_rows = 0;
-            }
-            if (!ix->rows32 && (ix->rerank_copy == 1 || ix->rows32_declined_cap != ix->cap_rows)) {
-                const size_t need = (size_t)ix->cap_rows * rs * 4;
-                size_t free_b = 0, total_b = 0;
-                HB_HIP(hipMemGetInfo(&free_b, &total_b));
-                ix->rows32_declined_cap = ix->cap_rows;     // (cleared below when the copy is made)
-                // automatic (round 6, by measurement: profiles/r06/final/fp16_residency.json): what the copy saves is a few ms of re-rank per search
-                // (about 4 ms for 21,904 queries x 64 candidates), whatever the bank's size, and what it costs is the bank once more.  At 300,000
-                // x 768 that is 17 % of a search for 0.9 GB; at 10 M x 768 1.5 % for 30.7 GB, at 20 M x 1024 and 27.7 M x 768 0.4 % for 83-85 GB.
-                // So only banks of up to 4e9 values (16 GB of fp32: 5.2 M x 768) get it -- a use_fp16 index of a bigger bank holds 1.5 x the bank
-                // (fp32 tiles for the exact re-rank and the fp32 searches, fp16 tiles for the candidate pass), not 2.5 x -- and, as before, only
-                // where the three copies stay within 55 % of the device with room to spare: the search's own workspace is allocated after the
-                // copy, and a device shared with a model or another rank must not be filled to the brim by an optional copy.  An allocation that
-                // fails all the same just means no copy.
-                const size_t bank_b = (size_t)ix->cap_rows * ix->dp * 4;
-                if (ix->rerank_copy == 1 || (bank_b <= (size_t)16e9 && bank_b + bank_b / 2 + need <= total_b / 100 * 55 &&
-                                             free_b > need + std::max<size_t>(total_b / 16, (size_t)2 << 30))) {
-                    if (hipMalloc((void**)&ix->rows32, need) == hipSuccess) { ix->rows32_cap_rows = ix->cap_rows; ix->rows32_rs = rs; ix->rows32_rows = 0; ix->rows32_declined_cap = -1; }
-                    else { (void)hipGetLastError(); ix->rows32 = nullptr; if (ix->rerank_copy == 1) return hb_fail("hb_index_search: no memory for the re-rank copy of the bank"); }
-                }
-            }
-            if (ix->rows32 && ix->rows32_rows < ix->ntotal) {
-                const int64_t rt0 = ix->rows32_rows / 32, need_rt = (ix->ntotal + 31) / 32;
-                if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->rows32, rs, need_rt - rt0, rt0, s0)) return -1;
-                ix->rows32_rows = ix->ntotal;
-            }
+        if (ix->tiles16) {
+            HB_HIP(hipMemsetAsync(ix->tiles16, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0));
+            ix->f16_cap_rows = ix->cap_rows;
         }
     }
-    // fp16 mode: the fused kernel collects kc >= 2k candidates, the fp32 chain arithmetic re-ranks them
-    // k' = 2k, at least 64 (rounded up to 8, not to 64 as until round 4: the candidate kernel's time is linear in k' -- 300,000 x 768, 21,904
-    // queries: k' = 64 / 128 / 192 / 256 -> 12.95 / 15.85 / 20.7 / 25.0 ms -- so k = 33 paid for 128 candidates where it needs 66)
-    const bool centred = f16 && ix->fp16_centre && ix->centre.active;      // this pass runs on the centred copy
-    if (esc == 0) { ix->last_path = !f16 ? HB_PATH_FP32 : wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = why; ix->last_centred = centred ? 1 : 0; }
-    const int kc = f16 ? (esc == 1 || wide_first ? 256 : std::min(256, std::max(64, (2 * k + 7) / 8 * 8))) : k;     // (the second pass: the widest list the re-rank takes)
-    // Small searches (few stages per workgroup) on the kernel with register-resident query fragments run on POOLS even for k <= 32:
-    // phased, with the bisection cold start and the scan epilogue (hbird_knn_bd.hip <WIDE, COLD>) a pool takes a tile's survivors in one
-    // drain, a sorted LDS list one wave-cooperative insertion each.  Same box, kernel ms, lists / pools, k = 30: 50,176 x 384 x 12,544
-    // queries 4.61 / 4.13 (k = 32: 4.50 / 3.84), x 21,904 queries 7.04 / 6.52, 50,176 x 768 12.47 / 12.16, 200 k x 384 14.76 / 13.89,
-    // 300 k x 768 40.6 / 39.9, 2,074,072 x 384 140.5 / 137.4, 600 k x 1024 105.8 / 105.3, 1.25 M x 768 286.0 / 286.7, 2.5 M x 768
-    // 573.5 / 571.5, 20 k x 384 x 784 queries 0.59 / 0.26, 100 k x 384 x 196 queries 0.61 / 0.26; k = 5 at 50,176 x 384 3.61 / 3.68 and
-    // k = 1 at 200 k x 384 13.47 / 13.54 (few insertions anyway) -> from k = 8.  (Round 2 measured pools at 8.1 vs 5.0 ms for the first
-    // of these: unphased, radix cold start, LDS walk.)  Variant 6 keeps the lists (A/B, tests).
-    const long long small_limit = ix->small_limit > 0 ? ix->small_limit : 400000;   // stages per workgroup (hb_index_set_search_options)
-    const int G0 = ix->force_G > 0 ? ix->force_G : ix->num_cu;
-    const long long pairs0 = (long long)((nq + HB_QT - 1) / HB_QT) * ((ix->ntotal + HB_BT - 1) / HB_BT);
-    const bool small_shape = pairs0 / std::max<long long>(1, std::min<long long>(G0, pairs0)) * ix->g8 < std::min<long long>(small_limit, 120000);   // no gain beyond (1.25 M x 768: 157 k stages)
-    const bool bd_shape = ix->g8 % 4 == 0 && ix->variant != 4;
-    const bool small_pools = !f16 && !ceil && k >= 8 && k <= HB_KL && small_shape && bd_shape && (ix->variant == 0 || ix->variant == 3) && ix->force_cq <= 1;
-    const bool wide = f16 || k > HB_KL || small_pools || ceil;
-    // pools (k > HB_KL): capacity >= 2 kc so that a compaction is paid for by >= kc cheap appends
-    // (smaller / larger pools measure the same on the fp16 candidate kernel: kc + 64, kc + 192)
-    const int klw = wide ? std::min(HB_POOL_MAX, (std::max(2 * kc, kc + 128) + 63) / 64 * 64) : HB_KL;
-    if (nq == 0) return 0;
-    // score output (sharded searches): the ordering score goes out as it is, whatever the metric
-    const int out_metric = ix->score_output ? 0 : ix->metric;
-    const int nqt = (int)((nq + HB_QT - 1) / HB_QT);
-    const int nbt = (int)((ix->ntotal + HB_BT - 1) / HB_BT);
-    hipStream_t s = ix->stream;
-    if (nbt == 0) {
-        // empty index: every neighbour is missing (faiss returns -1 labels)
-        std::vector<int64_t> hi((size_t)nq * k, -1);
-        std::vector<float> hd((size_t)nq * k, out_metric == 1 ? INFINITY : -INFINITY);
-        HB_HIP(hipMemcpyAsync(out_idx, hi.data(), hi.size() * 8, hipMemcpyHostToDevice, s));
-        HB_HIP(hipMemcpyAsync(out_dist, hd.data(), hd.size() * 4, hipMemcpyHostToDevice, s));
-        HB_HIP(hipStreamSynchronize(s));
-        return 0;
+    if (f16 && ix->f16_rows < ix->ntotal) {
+        const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
+        // (hb_index_set_fp16_centre: the rows as fl32(b - mu) with their per-row term, hbird_f16_centre.hip; a bank without a usable mean: the plain copy)
+        int centred = 0;
+        if (ix->fp16_centre && hb_centre_convert(ix, s0, &centred)) return -1;
+        if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, (_Float16*)ix->tiles16, ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
+        ix->f16_rows = ix->ntotal;
+        HB_HIP(hipMemcpyAsync(&ix->f16_overflow, ix->f16_flag, 4, hipMemcpyDeviceToHost, s0));
+        HB_HIP(hipStreamSynchronize(s0));
     }
-    const int G = ix->force_G > 0 ? ix->force_G : ix->num_cu;
-    const size_t tile_bytes = (size_t)HB_BT * ix->dp * 4;
-    // per-XCD work shares (hb_xcd_calibrate above; read BEFORE the cluster shape is chosen: the calibration also decides whether the fp32 clusters stay): calibrated for fp32 searches from 30,000 stages per workgroup (30-60 ms of kernel; from 150,000 until late in
-    // round 5: cfg-2's 2 M x 384 bank went without, 135.3 -> 134.7 ms with; phased searches gain in their last phase only);
-    // shares given by the caller (mode 2) apply to searches of any size, both kernel families (tests/fuzz_small.py FUZZ_XCD=1)
-    const int fam = f16 ? 1 : 0;
-    const bool balance = G % 8 == 0 &&
-                         (ix->xcd_balance == 2 || (ix->xcd_balance == 0 && (long long)nqt * nbt / std::max(1, G) * ix->g8 >= 30000));
-    if (balance && ix->xcd_balance == 0 && esc == 0) hb_xcd_calibrate(ix, fam);     // (nested searches run on the shares in use and leave the calibration alone)
-    // L2-sharing clusters (hb_index_set_cluster; automatic shapes below): q x b workgroups of one XCD walk the same bank /
-    // query tiles within `lag` stages of each other, so one L2 fill serves several.  Neither kernel is bound by the fabric
-    // (the fp32 one by the matrix pipe, the fp16 candidate kernel by its LDS-DMA copies and the power the chip grants it:
-    // profiles/LABBOOK.md, profiles/r02), so what they buy is traffic, and time only for the fp16 kernel (-8 %).  The 4-wave variant
-    // does not know strided segments.
-    int cq = 1, cb = 1;
-    bool auto_cluster = false;      // fp32: the cluster shape of this search is the automatic choice (kept only where it measures faster)
-    if (ceil) { cq = 1; cb = 1; }
-    else if (ix->force_cq > 0 && ix->force_cb > 0) { cq = ix->force_cq; cb = ix->force_cb; }
-    // fp16 candidate kernel: from 70 k stages per workgroup up (round 4: with the lean stage loop and the XCD-level query sharing the
-    // clusters pay much earlier than the 400 k of round 3).  Same box, kernel ms (phased), none vs automatic: 10 M x 768 321 / 284,
-    // 2.5 M x 768 (157 k stages) 83.0 / 77.5, 5 M x 384 (157 k) 85.3 / 80.3, 1.25 M x 768 (79 k) 43.7 / 41.8, 5 M x 768 x 12,544 queries
-    // (179 k; 49 query tiles: 4 x 2) 94.0 / 88.2 -- but 2,074,072 x 384 (37 k) 21.3 / 22.8: more slots, shorter segments
-    // (profiles/r04/f16_cluster_threshold.txt)
-    else if (f16 && ix->variant == 0 && ix->force_cq == 0) {
-        if ((long long)nqt * nbt / std::max(1, G) * (ix->dp16 / 16) >= 70000) hb_default_cluster(nqt, nbt, G, false, &cq, &cb);
+    if (f16 && ix->f16_overflow) {
+        f16 = false; why = HB_WHY_OVERFLOW;
+        if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; }
+        if (automatic && knn_drop_tiles16(ix)) return -1;      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
     }
-    // fp32: only beside the kernel with register-resident query fragments (its sync is free of spills), and only for the
-    // biggest searches: 2 x 4 clusters cut the fabric reads by 60 % (10 M x 768: 4.79 -> 1.93 TB per search, L2 hit rate
-    // 10 % -> 63 %) but the kernel is bound by the matrix pipe, so all they can do for the time is cost little -- measured
-    // (same box, kernel ms, none vs 2 x 4): 10 M x 768 2280 vs 2298 (+0.8 %), 5 M x 1024 1528 vs 1531 (+0.2 %), but
-    // 1.25 M x 768 289.3 vs 293.9 (+1.6 %), 2 M x 384 142.3 vs 146.4 (+2.9 %): more slots, shorter segments.  Automatic from
-    // one million stages per workgroup up (8 M rows at D = 768); hb_index_set_cluster(ix, 1, 1, 0) turns them off, (ix, 2, 4, -1) forces them.
-    // Round 6: ... and only where they MEASURE faster on this box (hb_xcd_calibrate: two calibrated launches with, two without, the faster
-    // form stays); without the calibration's stamps (equal or given shares) they stay on.
-    else if (!f16 && !wide && ix->variant == 0 && ix->force_cq == 0 && ix->g8 % 4 == 0 &&
-             (long long)nqt * nbt / std::max(1, G) * ix->g8 >= 1000000) {
-        auto_cluster = true;
-        const hb_index::xcd_cal& c0 = ix->xcal[0];
-        const bool measured = ix->xcd_balance == 0 && G % 8 == 0;
-        // (a decision, once made, holds whatever the share mode; before it: on while measuring with, off while measuring without)
-        if (c0.cl_state == 2 ? c0.cl_choice != 0 : (!measured || c0.cl_state == 0)) hb_default_cluster(nqt, nbt, G, true, &cq, &cb);
+    // ... and the row-major fp32 copy for the re-rank (hbird_knn_f16.hip).  Automatic: by the bank's size (below; a 10 M x 768 bank:
+    // 30.7 GB of tiles + 15.4 GB of fp16 tiles + 30.7 GB of rows, of 288)
+    if (f16 && ix->rerank_copy != 2) {
+        const int rs = (ix->g8 * 8 + 31) / 32 * 32;
+        if (ix->rows32 && (ix->rows32_cap_rows != ix->cap_rows || ix->rows32_rs != rs)) {
+            HB_HIP(hipFree(ix->rows32));
+            ix->rows32 = nullptr; ix->rows32_cap_rows = 0; ix->rows32_rows = 0;
+        }
+        if (!ix->rows32 && (ix->rerank_copy == 1 || ix->rows32_declined_cap != ix->cap_rows)) {
+            const size_t need = (size_t)ix->cap_rows * rs * 4;
+            size_t free_b = 0, total_b = 0;
+            HB_HIP(hipMemGetInfo(&free_b, &total_b));
+            ix->rows32_declined_cap = ix->cap_rows;     // (cleared below when the copy is made)
+            // automatic (round 6, by measurement: profiles/r06/final/fp16_residency.json): what the copy saves is a few ms of re-rank per search
+            // (about 4 ms for 21,904 queries x 64 candidates), whatever the bank's size, and what it costs is the bank once more.  At 300,000
+            // x 768 that is 17 % of a search for 0.9 GB; at 10 M x 768 1.5 % for 30.7 GB, at 20 M x 1024 and 27.7 M x 768 0.4 % for 83-85 GB.
+            // So only banks of up to 4e9 values (16 GB of fp32: 5.2 M x 768) get it -- a use_fp16 index of a bigger bank holds 1.5 x the bank
+            // (fp32 tiles for the exact re-rank and the fp32 searches, fp16 tiles for the candidate pass), not 2.5 x -- and, as before, only
+            // where the three copies stay within 55 % of the device with room to spare: the search's own workspace is allocated after the
+            // copy, and a device shared with a model or another rank must not be filled to the brim by an optional copy.  An allocation that
+            // fails all the same just means no copy.
+            const size_t bank_b = (size_t)ix->cap_rows * ix->dp * 4;
+            if (ix->rerank_copy == 1 || (bank_b <= (size_t)16e9 && bank_b + bank_b / 2 + need <= total_b / 100 * 55 &&
+                                         free_b > need + std::max<size_t>(total_b / 16, (size_t)2 << 30))) {
+                if (hipMalloc((void**)&ix->rows32, need) == hipSuccess) { ix->rows32_cap_rows = ix->cap_rows; ix->rows32_rs = rs; ix->rows32_rows = 0; ix->rows32_declined_cap = -1; }
+                else { (void)hipGetLastError(); ix->rows32 = nullptr; if (ix->rerank_copy == 1) return hb_fail("hb_index_search: no memory for the re-rank copy of the bank"); }
+            }
+        }
+        if (ix->rows32 && ix->rows32_rows < ix->ntotal) {
+            const int64_t rt0 = ix->rows32_rows / 32, need_rt = (ix->ntotal + 31) / 32;
+            if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->rows32, rs, need_rt - rt0, rt0, s0)) return -1;
+            ix->rows32_rows = ix->ntotal;
+        }
     }
-    if ((long long)nqt * nbt < G || cq * cb > HB_CLUSTER_MAX || G % (8 * cq * cb) != 0) { cq = 1; cb = 1; }
-    const int panel = ix->force_panel > 0 ? ix->force_panel
-                                          : hb_default_panel(nqt, std::min<long long>(G, (long long)nqt * nbt), tile_bytes, cq, cb);
+    return 0;
+}
+
+// ---- stage 2: the work list of the plan, built where the cached one does not serve, and its device copy ---------------------------------
+struct knn_work_list {
+    const hb_schedule* sc = nullptr;
+    double shares[8] = {1, 1, 1, 1, 1, 1, 1, 1};      // the GROUP shares the list was built with
+    // device copy: [segs][wg_off][qt_off][qt_slots][wg_member][phase_bounds]
+    const hb_seg* segs = nullptr;
+    const int *wg_off = nullptr, *qt_off = nullptr, *qt_slots = nullptr, *wg_member = nullptr, *phase_bounds = nullptr;
+    int n_phases = 1;          // 1: a single launch (lists; pools with too little work per workgroup)
+    // this launch's share of every block's segments: [phase_begin(p)[b], phase_end(p)[b]) of the block's list
+    const int* phase_begin(int p) const { return p == 0 ? wg_off : phase_bounds + (size_t)(p - 1) * sc->G; }
+    const int* phase_end(int p) const { return p == n_phases - 1 ? wg_off + 1 : phase_bounds + (size_t)p * sc->G; }
+};
+static int knn_get_work_list(hb_index* ix, int esc, const hb_knn_plan& p, hipStream_t s, knn_work_list* out) {
+    knn_work_list& wl = *out;
     static const double equal_shares[8] = {1, 1, 1, 1, 1, 1, 1, 1};
     // (shares divided by their mean: eight equal shares of any size are the equal list, which is cached as such)
-    double shares_n[8];
-    const double* shares = equal_shares;
-    if (balance) {
+    if (p.balance) {
+        double shares_n[8];
         double mean = 0.0;
         bool uneven = false;
         // calibrated shares belong to the physical XCDs: group g (blocks equal to g mod 8) gets the share of the XCD it was last seen on
-        const hb_index::xcd_cal& xc = ix->xcal[fam];
+        const hb_index::xcd_cal& xc = ix->xcal[p.fam];
         for (int x = 0; x < 8; ++x) mean += xc.w[x] / 8.0;
         for (int g = 0; g < 8; ++g) { shares_n[g] = xc.w[ix->xcd_balance == 0 ? xc.perm[g] : g] / mean; uneven = uneven || std::fabs(shares_n[g] - 1.0) > 1e-9; }
-        if (uneven) shares = shares_n;
+        if (uneven) std::copy(shares_n, shares_n + 8, wl.shares);
     }
+    const double* shares = wl.shares;
     hb_schedule& sc = esc == 0 ? ix->sched : ix->sched_esc;      // (the nested searches of uncertified queries keep a list of their own: the caller's stays cached)
     char*& sched_dev = esc == 0 ? ix->sched_dev : ix->sched_esc_dev;
     size_t& sched_bytes = esc == 0 ? ix->sched_bytes : ix->sched_esc_bytes;
-    // phased searches (pools only: "Phased searches" above hb_launch_knn); hb_index_set_search_options(ix, 0, ...) turns them off (A/B, tests)
-    // (a nested search of uncertified queries starts from seeded floors: phases would only add boundaries -- and with one query tile over 256
-    // workgroups the floors between them go through the merge kernels: 70 ms for two queries)
-    const bool phased = wide && ix->phases_on && esc == 0;
-    // XCD-level sharing of the query tiles (hb_build_clustered): automatic for the fp16 candidate kernel -- same box, 10 M x 768, 8 x 1
-    // clusters: 302.7 -> 291.5 ms and 0.97 -> 0.52 TB of L2-miss traffic per search (L2 hit rate 0.60 -> 0.78); the fp32 kernel's 2 x 4
-    // clusters lose 1.6 % with it (2298 -> 2334 ms: 1600 slots instead of 592, and its 768 KiB query tiles do not stay in L2 beside
-    // sixteen bank streams anyway: 1.95 -> 1.62 TB) -> off there (profiles/r04/xs_*.txt)
-    const bool xs = cq * cb > 1 && (ix->xcd_share == 2 || (ix->xcd_share == 0 && f16));
-    const bool rebuilt = !(sc.nqt == nqt && sc.nbt == nbt && sc.panel == panel && sc.cq == cq && sc.cb == cb && sc.phased == phased &&
-                           sc.xcd_share == xs && (sc.G == G || (long long)nqt * nbt < G) &&
+    const int nqt = p.nqt, nbt = p.nbt, G = p.G;
+    const bool rebuilt = !(sc.nqt == nqt && sc.nbt == nbt && sc.panel == p.panel && sc.cq == p.cq && sc.cb == p.cb && sc.phased == p.phased &&
+                           sc.xcd_share == p.xs && (sc.G == G || (long long)nqt * nbt < G) &&
                            (sc.xcd_w.empty() ? std::equal(shares, shares + 8, equal_shares) : std::equal(shares, shares + 8, sc.xcd_w.begin())));
-    if (rebuilt) { hb_build_schedule(nqt, nbt, G, panel, sc, cq, cb, phased, xs, shares); ++ix->sched_builds; }
-    // device copy of the work list: [segs][wg_off][qt_off][qt_slots][wg_member]
-    const size_t b_segs = sc.segs.size() * sizeof(hb_seg), b_wg = sc.wg_off.size() * 4, b_qo = sc.qt_off.size() * 4,
-                 b_qs = sc.qt_slots.size() * 4, b_wm = sc.wg_member.size() * 4;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t b_pb = sc.phase_bounds.size() * 4;
-    const size_t o_wg = al(b_segs), o_qo = o_wg + al(b_wg), o_qs = o_qo + al(b_qo), o_wm = o_qs + al(b_qs), o_pb = o_wm + al(b_wm),
-                 tot = o_pb + al(b_pb);
-    const bool need_upload = rebuilt || sched_bytes < tot;
-    if (ensure_bytes(&sched_dev, &sched_bytes, tot)) return -1;
+    if (rebuilt) { hb_build_schedule(nqt, nbt, G, p.panel, sc, p.cq, p.cb, p.phased, p.xs, shares); ++ix->sched_builds; }
+    const struct { const void* data; size_t bytes; } part[6] = {{sc.segs.data(), sc.segs.size() * sizeof(hb_seg)}, {sc.wg_off.data(), sc.wg_off.size() * 4},
+        {sc.qt_off.data(), sc.qt_off.size() * 4}, {sc.qt_slots.data(), sc.qt_slots.size() * 4}, {sc.wg_member.data(), sc.wg_member.size() * 4},
+        {sc.phase_bounds.data(), sc.phase_bounds.size() * 4}};
+    size_t off[7] = {0};
+    for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + al256(part[i].bytes);
+    const bool need_upload = rebuilt || sched_bytes < off[6];
+    if (ensure_bytes(&sched_dev, &sched_bytes, off[6])) return -1;
     if (need_upload) {
-        HB_HIP(hipMemcpyAsync(sched_dev, sc.segs.data(), b_segs, hipMemcpyHostToDevice, s));
-        HB_HIP(hipMemcpyAsync(sched_dev + o_wg, sc.wg_off.data(), b_wg, hipMemcpyHostToDevice, s));
-        HB_HIP(hipMemcpyAsync(sched_dev + o_qo, sc.qt_off.data(), b_qo, hipMemcpyHostToDevice, s));
-        HB_HIP(hipMemcpyAsync(sched_dev + o_qs, sc.qt_slots.data(), b_qs, hipMemcpyHostToDevice, s));
-        HB_HIP(hipMemcpyAsync(sched_dev + o_wm, sc.wg_member.data(), b_wm, hipMemcpyHostToDevice, s));
-        HB_HIP(hipMemcpyAsync(sched_dev + o_pb, sc.phase_bounds.data(), b_pb, hipMemcpyHostToDevice, s));
+        for (int i = 0; i < 6; ++i) HB_HIP(hipMemcpyAsync(sched_dev + off[i], part[i].data, part[i].bytes, hipMemcpyHostToDevice, s));
         HB_HIP(hipStreamSynchronize(s));   // host vectors may be rebuilt by the next call
     }
+    auto ints = [&](int i) { return reinterpret_cast<const int*>(sched_dev + off[i]); };
+    wl.sc = &sc; wl.segs = reinterpret_cast<const hb_seg*>(sched_dev);
+    wl.wg_off = ints(1); wl.qt_off = ints(2); wl.qt_slots = ints(3); wl.wg_member = ints(4); wl.phase_bounds = ints(5);
+    wl.n_phases = (int)sc.phase_clock.size() + 1;
+    return 0;
+}
+
+// ---- stage 3: `state` carved into the kernels' arguments: lists / pools, floors, progress words, stamps ---------------------------------
+struct knn_workspace {
+    knn_args a;                // (wg_off / wg_end: set per phase by the runner's launch)
+    size_t state_aux = 0;      // bytes of the pools' fill counts (and of their thresholds)
+    size_t prog_bytes = 0, stamp_bytes = 0;
+};
+static int knn_carve_workspace(hb_index* ix, const knn_call& c, const hb_knn_plan& p, const knn_work_list& wl, int64_t nq, int k, hipStream_t s,
+                               knn_workspace* out) {
+    const hb_schedule& sc = *wl.sc;
+    const int nqt = p.nqt, klw = p.klw, esc = c.esc;
     const size_t state_half = (size_t)sc.n_slots * HB_QT * klw * 4;
-    const size_t state_aux = wide ? (size_t)sc.n_slots * HB_QT * 4 : 0;   // pools: fill counts + thresholds
+    const size_t state_aux = p.wide ? (size_t)sc.n_slots * HB_QT * 4 : 0;   // pools: fill counts + thresholds
     const size_t floor_bytes = (size_t)nqt * HB_QT * 4 * 17;              // shared threshold floors, one per query, + 16 quota-floor keys per query
     const size_t prog_bytes = ((size_t)std::max(1, sc.n_clusters) * HB_CLUSTER_MAX + 1) * HB_CLUSTER_LINE * 4;   // progress words, a line each, + statistics
     const size_t stamp_bytes = (size_t)sc.G * 32;                       // per-block {start, end, XCC id} stamps of the last kNN launch with its shader-cycle counts (wg_stamp, hbird_knn_dev.h)
     if (ensure_bytes(&ix->state, &ix->state_bytes, 2 * state_half + 2 * state_aux + floor_bytes + prog_bytes + stamp_bytes)) return -1;
-
-    knn_args a;
+    out->state_aux = state_aux; out->prog_bytes = prog_bytes; out->stamp_bytes = stamp_bytes;
+    char* const floors = ix->state + 2 * state_half + 2 * state_aux;
+    knn_args& a = out->a;
     // (a nested search of uncertified queries neither stamps nor counts as "the last launch": hb_index_kernel_clock / hb_index_wg_stamps describe the
     // caller's search, as hb_index_schedule_info does)
-    a.wg_stamp = esc == 0 && (ix->time_kernels || (balance && ix->xcd_balance == 0)) ? reinterpret_cast<unsigned*>(ix->state + 2 * state_half + 2 * state_aux + floor_bytes + prog_bytes) : nullptr;
+    a.wg_stamp = esc == 0 && (c.timed || p.calibrated) ? reinterpret_cast<unsigned*>(floors + floor_bytes + prog_bytes) : nullptr;
     if (esc == 0) { ix->wg_stamp_dev = a.wg_stamp; ix->wg_stamp_blocks = sc.G; }
     if (a.wg_stamp) HB_HIP(hipMemsetAsync(a.wg_stamp, 0, stamp_bytes, s));   // a block that never stamps reads 0 / 0 (hb_stamps_summarise)
     a.bank_tiles = ix->tiles; a.binit = ix->binit; a.q_tiles = ix->q_tiles;
-    a.ceil_s = ix->ceil_s_dev; a.ceil_i = ix->ceil_i_dev;
-    a.segs = reinterpret_cast<const hb_seg*>(sched_dev);
-    a.wg_off = reinterpret_cast<const int*>(sched_dev + o_wg);
-    a.wg_end = a.wg_off + 1;
-    // this launch's share of every block's segments: [phase_begin(p)[b], phase_end(p)[b]) of the block's list
-    const int n_phases = (int)sc.phase_clock.size() + 1;   // 1: a single launch (lists; pools with too little work per workgroup)
-    const int* pb = reinterpret_cast<const int*>(sched_dev + o_pb);
-    auto phase_begin = [&](int p) { return p == 0 ? reinterpret_cast<const int*>(sched_dev + o_wg) : pb + (size_t)(p - 1) * sc.G; };
-    auto phase_end = [&](int p) { return p == n_phases - 1 ? reinterpret_cast<const int*>(sched_dev + o_wg) + 1 : pb + (size_t)p * sc.G; };
+    a.ceil_s = c.ceil_s; a.ceil_i = c.ceil_i; a.segs = wl.segs; a.wg_off = wl.wg_off; a.wg_end = a.wg_off + 1;
     a.state_s = reinterpret_cast<float*>(ix->state);
     a.state_i = reinterpret_cast<unsigned*>(ix->state + state_half);
     a.g8 = ix->g8; a.k = k; a.klw = klw;
     a.state_cnt = reinterpret_cast<int*>(ix->state + 2 * state_half);
     a.state_thr = reinterpret_cast<float*>(ix->state + 2 * state_half + state_aux);
-    const int* pool_cnt = wide ? a.state_cnt : nullptr;
-    a.gthr = reinterpret_cast<unsigned*>(ix->state + 2 * state_half + 2 * state_aux);
+    a.gthr = reinterpret_cast<unsigned*>(floors);
     a.qfl = a.gthr + (size_t)nqt * HB_QT;
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)a.gthr, 0x007FFFFF, (size_t)nqt * HB_QT * 17, s));   // key(-inf)
     // the padding queries of the last query tile (zero vectors: every row scores the same) start from key(+inf): nothing ever passes
@@ -938,217 +888,291 @@ int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t i
     if (nq < (int64_t)nqt * HB_QT) HB_HIP(hipMemsetD32Async((hipDeviceptr_t)(a.gthr + nq), 0xFF800000u, (size_t)((int64_t)nqt * HB_QT - nq), s));
     // a nested search of uncertified queries starts from what the pass before it found out (hb_rerank_seeds): per query a score that the
     // rows which can still matter reach
-    if (esc != 0 && ix->seed_dev) {
-        seed_from_scores_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(ix->seed_dev, nq, a.gthr);
+    if (esc != 0 && c.seed) {
+        seed_from_scores_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(c.seed, nq, a.gthr);
         HB_HIP(hipGetLastError());
     }
-    a.wg_member = reinterpret_cast<const int*>(sched_dev + o_wm);
-    a.prog = reinterpret_cast<int*>(ix->state + 2 * state_half + 2 * state_aux + floor_bytes);
-    a.cl = sc.cq * sc.cb;
-    // soft-sync lag in stages: the members stay inside the L2's reach (4 MiB per XCD: tens of fp32 k8 stages); 0 disables
-    // the sync (the members then share only while they happen to run together: 36 % instead of 53 % L2 hits)
-    a.lag = a.cl > 1 ? (ix->sync_lag >= 0 ? ix->sync_lag : 16) : 0;
+    a.wg_member = wl.wg_member; a.prog = reinterpret_cast<int*>(floors + floor_bytes);
+    a.cl = sc.cq * sc.cb; a.lag = p.lag;      // (soft-sync lag in stages: hb_knn_plan_clusters)
     a.cl_stats = a.prog + (size_t)std::max(1, sc.n_clusters) * HB_CLUSTER_MAX * HB_CLUSTER_LINE;
     ix->cl_stats_dev = a.cl > 1 ? a.cl_stats : nullptr;
     if (a.cl > 1) HB_HIP(hipMemsetAsync(a.prog, 0, prog_bytes, s));
-    // between two phases of a pool search: the kk-th best of all rows seen so far becomes every slot's floor -- straight from the pools
-    // where a query tile's pools fit the floor kernel's LDS, else through the merge (few queries against a big bank: many slots)
-    auto seed_floors = [&](int kk, int64_t* scratch_idx, float* scratch_dist) -> int {
-        const int* qo = reinterpret_cast<const int*>(sched_dev + o_qo);
-        const int* qs = reinterpret_cast<const int*>(sched_dev + o_qs);
-        const size_t per_wave = (size_t)sc.max_slots_per_qt * klw;
-        // (up to 144 KiB of the CU's 160: 32 slots per query tile x pools of 256, 16 x 512 -- the merge path below costs a phase boundary
-        // ten times as much: 10 M x 768, k = 90 with 16 slots per query tile: 2.9 -> 44.7 ms per search, profiles/r04/cluster_tail_rows_ab.txt)
-        if (per_wave * 16 <= 144 * 1024) {
-            if (per_wave * 16 > 48 * 1024 && hb_ensure_dyn_lds((const void*)pool_floor_kernel, 144 * 1024)) return -1;
-            pool_floor_kernel<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), per_wave * 16, s>>>(a.state_s, a.state_cnt, a.state_thr, qo, qs, nq, kk,
-                                                                                               klw, (int)per_wave, a.gthr);
-            HB_HIP(hipGetLastError());
-            return 0;
-        }
-        if (launch_merge(ix, a.state_s, a.state_i, a.state_cnt, a.state_thr, qo, qs, sc.max_slots_per_qt, nqt, nq, kk, klw, 0, 0, nullptr,
-                         scratch_idx, scratch_dist, s)) return -1;
-        seed_floors_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(scratch_idx, scratch_dist, nq, kk, a.gthr);
+    return 0;
+}
+
+// ---- stage 4: the phases of one search, for both kernel families ------------------------------------------------------------------------
+// between two phases of a pool search: the kk-th best of all rows seen so far becomes every slot's floor -- straight from the pools
+// where a query tile's pools fit the floor kernel's LDS, else through the merge (few queries against a big bank: many slots)
+static int knn_seed_floors(hb_index* ix, const knn_args& a, const knn_work_list& wl, int nqt, int klw, int64_t nq, int kk, int64_t* scratch_idx,
+                           float* scratch_dist, hipStream_t s) {
+    const hb_schedule& sc = *wl.sc;
+    const size_t per_wave = (size_t)sc.max_slots_per_qt * klw;
+    // (up to 144 KiB of the CU's 160: 32 slots per query tile x pools of 256, 16 x 512 -- the merge path below costs a phase boundary
+    // ten times as much: 10 M x 768, k = 90 with 16 slots per query tile: 2.9 -> 44.7 ms per search, profiles/r04/cluster_tail_rows_ab.txt)
+    if (per_wave * 16 <= 144 * 1024) {
+        if (per_wave * 16 > 48 * 1024 && hb_ensure_dyn_lds((const void*)pool_floor_kernel, 144 * 1024)) return -1;
+        pool_floor_kernel<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), per_wave * 16, s>>>(a.state_s, a.state_cnt, a.state_thr, wl.qt_off, wl.qt_slots, nq, kk,
+                                                                                           klw, (int)per_wave, a.gthr);
         HB_HIP(hipGetLastError());
         return 0;
-    };
-    if (f16) {
-        // fp16 copy of the query fragment tiles (the bank's is up to date: top of this function)
-        const int64_t nqp = (int64_t)nqt * HB_QT;
-        if (ensure_bytes((char**)&ix->q16, &ix->q16_bytes, (size_t)nqp * ix->dp16 * 2)) return -1;
-        // centred: fp16 tiles of q - t mu, c_q and ||q - t mu|| per query; a caller's search also derives t and, from it, the rows' init values
-        hb_centre_view cview{nullptr, nullptr, nullptr};
-        if (centred) { if (hb_centre_queries(ix, nq, esc == 0, (_Float16*)ix->q16, &cview, s)) return -1; }
-        else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, (_Float16*)ix->q16, ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
-        const hb_centre_view* cv = centred ? &cview : nullptr;
-        if (ensure_bytes(&ix->cand, &ix->cand_bytes, (size_t)nq * kc * 12)) return -1;
-        int64_t* cand_idx = reinterpret_cast<int64_t*>(ix->cand);
-        float* cand_dist = reinterpret_cast<float*>(ix->cand + (size_t)nq * kc * 8);
-        knn16_args h;
-        h.wg_stamp = a.wg_stamp;
-        h.bank16 = reinterpret_cast<const _Float16*>(ix->tiles16); h.binit = centred ? ix->centre.init16 : ix->binit; h.q16 = reinterpret_cast<const _Float16*>(ix->q16); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
-        h.state_s = a.state_s; h.state_i = a.state_i; h.g16 = ix->dp16 / 16; h.k = kc; h.klw = klw;
-        h.state_cnt = a.state_cnt; h.state_thr = a.state_thr; h.gthr = a.gthr;
-        h.wg_member = a.wg_member; h.prog = a.prog; h.cl = a.cl; h.lag = a.lag; h.cl_stats = a.cl_stats;
-        if (ix->time_kernels) HB_HIP(hipEventRecord(ix->ev0, s));
-        if (n_phases > 1) {   // slots that start in a later phase must read as empty pools in the merges between the phases
-            HB_HIP(hipMemsetAsync(a.state_cnt, 0, state_aux, s));
-            HB_HIP(hipMemsetD32Async((hipDeviceptr_t)a.state_thr, 0xFF800000u, state_aux / 4, s));
-        }
-        for (int ph = 0; ph < n_phases; ++ph) {
-            h.wg_off = phase_begin(ph); h.wg_end = phase_end(ph);
-            if (hb_knn_f16_launch(h, sc.G, s)) return -1;
-            if (ph + 1 < n_phases) {   // the k'-th best of all rows seen so far -> every slot's floor
-                if (seed_floors(kc, cand_idx, cand_dist)) return -1;
-                if (a.cl > 1) HB_HIP(hipMemsetAsync(a.prog, 0, prog_bytes - HB_CLUSTER_LINE * 4, s));   // progress words (not the statistics)
-            }
-        }
-        if (ix->time_kernels) HB_HIP(hipEventRecord(ix->ev1, s));
-        if (balance && ix->xcd_balance == 0 && esc == 0 && hb_xcd_collect(ix, 1, a.wg_stamp, sc, shares, n_phases, nqt, nbt, kc, s)) return -1;
-        if (launch_merge(ix, a.state_s, a.state_i, pool_cnt, pool_cnt ? a.state_thr : nullptr, reinterpret_cast<const int*>(sched_dev + o_qo),
-                         reinterpret_cast<const int*>(sched_dev + o_qs), sc.max_slots_per_qt, nqt, nq, kc, klw, 0, 0, nullptr,
-                         cand_idx, cand_dist, s)) return -1;
-        // workspace of this level: [certificates nq + 64][exact k-th scores nq][floors for a second pass nq] and, once the failures are
-        // known, [their rows][queries][aux][floors][ids][distances]
-        char*& fbuf = esc == 0 ? ix->fb : ix->fb1;
-        size_t& fbuf_bytes = esc == 0 ? ix->fb_bytes : ix->fb1_bytes;
-        auto al2 = [](size_t x) { return (x + 255) / 256 * 256; };
-        const size_t o_kth = al2((size_t)nq + 64), o_flo = o_kth + al2((size_t)nq * 4), o_rows = o_flo + al2((size_t)nq * 4);
-        if (ensure_bytes(&fbuf, &fbuf_bytes, o_rows)) return -1;
-        unsigned char* cert = reinterpret_cast<unsigned char*>(fbuf);
-        float* kth = reinterpret_cast<float*>(fbuf + o_kth);
-        float* flo = reinterpret_cast<float*>(fbuf + o_flo);
-        HB_HIP(hipMemsetD32Async((hipDeviceptr_t)kth, 0xFF800000u, (o_rows - o_kth) / 4, s));    // -inf: no seed (a query with fewer than k candidates)
-        const float* seed_in = esc == 1 ? ix->seed_dev : nullptr;
-        if (ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal) {
-            if (hb_launch_rerank_rows(ix->rows32, ix->rows32_rs, ix->binit, ix->d, q_dev, ix->q_aux, cand_idx, cand_dist, ix->q_aux + nq, ix->bmax,
-                                      cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
-        } else if (hb_launch_rerank(ix->tiles, ix->binit, ix->g8, ix->d, q_dev, ix->q_aux, cand_idx, cand_dist, ix->q_aux + nq, ix->bmax,
-                                    cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
-        if (ix->time_kernels) {
-            HB_HIP(hipEventSynchronize(ix->ev1));
-            float ms = 0.f;
-            HB_HIP(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-            ix->last_knn_ms = ms;
-        }
-        // Queries whose certificate failed are searched again.  ESCALATION (round 6): first by a second fp16 pass with k' = 256 candidates
-        // (the certificate compares the exact k-th best with the fp16 score of rank k': four times the ranks apart) whose pools start from
-        // the floor `kth - 1.001 E` -- every row that can still matter scores above it in fp16, few others do, so the pass appends little and
-        // a list that does not fill up is complete by construction; only what fails again goes to the exact fp32 kernel, which starts from
-        // the exact k-th best found so far as its floor.  A failing query used to cost a share of a whole-bank fp32 search (10 M x 768: 27 ms
-        // per started tile of 256 queries; 5 % failing queries = +45 % on the step): the second pass costs a twentieth of that per query.
-        std::vector<unsigned char> hc((size_t)nq);
-        HB_HIP(hipMemcpyAsync(hc.data(), cert, (size_t)nq, hipMemcpyDeviceToHost, s));
-        HB_HIP(hipStreamSynchronize(s));
-        std::vector<int64_t> bad;
-        for (int64_t i = 0; i < nq; ++i) if (!hc[i]) bad.push_back(i);
-        const int64_t nf = (int64_t)bad.size();
-        if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
-        if (esc == 0 && nf == 0) hb_f16_observe(ix->f16_adapt, how16, nq, 0, 0);
-        if (nf > 0) {
-            // the second pass needs k' = 256 > the first one's, a bank worth a candidate pass, and is not repeated
-            const bool again16 = esc == 0 && ix->fp16_escalation == 0 && kc < 256 && ix->ntotal >= 4096;
-            const size_t o_q = o_rows + al2((size_t)nf * 8), o_aux = o_q + al2((size_t)nf * ix->d * 4), o_seed = o_aux + al2((size_t)nf * 8),
-                         o_idx = o_seed + al2((size_t)nf * 4), o_dist = o_idx + al2((size_t)nf * k * 8), tot2 = o_dist + al2((size_t)nf * k * 4);
-            if (fbuf_bytes < tot2) {
-                char* nb = nullptr;
-                HB_HIP(hipMalloc((void**)&nb, tot2 + tot2 / 4));
-                HB_HIP(hipMemcpyAsync(nb, fbuf, o_rows, hipMemcpyDeviceToDevice, s));      // (the seeds of this level)
-                HB_HIP(hipStreamSynchronize(s));
-                HB_HIP(hipFree(fbuf));
-                fbuf = nb; fbuf_bytes = tot2 + tot2 / 4;
-                kth = reinterpret_cast<float*>(fbuf + o_kth); flo = reinterpret_cast<float*>(fbuf + o_flo);
-            }
-            int64_t* d_rows = reinterpret_cast<int64_t*>(fbuf + o_rows);
-            float* d_q = reinterpret_cast<float*>(fbuf + o_q);
-            float* d_aux = reinterpret_cast<float*>(fbuf + o_aux);
-            float* d_seed = reinterpret_cast<float*>(fbuf + o_seed);
-            int64_t* d_fi = reinterpret_cast<int64_t*>(fbuf + o_idx);
-            float* d_fd = reinterpret_cast<float*>(fbuf + o_dist);
-            HB_HIP(hipMemcpyAsync(d_rows, bad.data(), (size_t)nf * 8, hipMemcpyHostToDevice, s));
-            if (hb_launch_gather_rows(q_dev, nq, ix->d, d_rows, nf, d_q, s)) return -1;
-            if (hb_launch_gather_rows(again16 ? flo : kth, nq, 1, d_rows, nf, d_seed, s)) return -1;
-            if (hb_launch_rows_to_tiles(d_q, nf, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, s)) return -1;
-            // the nested search takes `state` for its own pools (and may move it): the candidate launch's stamps go aside first
-            if (esc == 0 && a.wg_stamp) {
-                if (ix->stamp_keep_blocks < sc.G) {
-                    if (ix->stamp_keep) HB_HIP(hipFree(ix->stamp_keep));
-                    ix->stamp_keep = nullptr; ix->stamp_keep_blocks = 0;
-                    HB_HIP(hipMalloc((void**)&ix->stamp_keep, stamp_bytes));
-                    ix->stamp_keep_blocks = sc.G;
-                }
-                HB_HIP(hipMemcpyAsync(ix->stamp_keep, a.wg_stamp, stamp_bytes, hipMemcpyDeviceToDevice, s));
-                ix->wg_stamp_dev = ix->stamp_keep;
-            }
-            float* saved_aux = ix->q_aux;
-            ix->q_aux = d_aux;                       // chain ||q||^2 of the re-searched queries (L2 distances)
-            int rc = hb_launch_query_aux(d_q, nf, ix->d, d_aux, d_aux + nf, s);
-            const int saved = ix->fp16, saved_t = ix->time_kernels, saved_esc = ix->esc_level;
-            const float* saved_seed = ix->seed_dev;
-            ix->fp16 = again16 ? 1 : 0; ix->time_kernels = 0; ix->esc_level = again16 ? 1 : 2; ix->seed_dev = d_seed;
-            if (!again16) ix->last_fp16_fallbacks = nf;
-            if (!rc) rc = hb_launch_knn(ix, d_q, nf, k, id_base, d_fi, d_fd);
-            ix->fp16 = saved; ix->time_kernels = saved_t; ix->q_aux = saved_aux; ix->esc_level = saved_esc; ix->seed_dev = saved_seed;
-            if (esc == 0) { ix->last_fp16_escalated = nf; hb_f16_observe(ix->f16_adapt, how16, nq, nf, ix->last_fp16_fallbacks); }
-            if (rc) return -1;
-            if (hb_launch_scatter_rows(d_rows, nf, k, d_fi, d_fd, out_idx, out_dist, s)) return -1;
-            HB_HIP(hipStreamSynchronize(s));         // `bad` and the workspace are reused by the next call
-        }
-        return 0;
     }
+    if (launch_merge(ix, a.state_s, a.state_i, a.state_cnt, a.state_thr, wl.qt_off, wl.qt_slots, sc.max_slots_per_qt, nqt, nq, kk, klw, 0, 0, nullptr,
+                     scratch_idx, scratch_dist, s)) return -1;
+    seed_floors_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(scratch_idx, scratch_dist, nq, kk, a.gthr);
+    HB_HIP(hipGetLastError());
+    return 0;
+}
+
+// launch(begin, end) starts one phase: begin[b] .. end[b] of block b's segments.  kk and the scratch lists are what the floors between two
+// phases are taken from (the kk-th best of all rows seen so far); kk is also the k of the calibration's shape key.
+template <class Launch>
+static int knn_run_phases(hb_index* ix, const knn_call& c, const hb_knn_plan& p, const knn_work_list& wl, const knn_workspace& ws, int64_t nq, int kk,
+                          int64_t* scratch_idx, float* scratch_dist, hipStream_t s, Launch launch) {
+    const knn_args& a = ws.a;
+    if (c.timed) HB_HIP(hipEventRecord(ix->ev0, s));
+    if (wl.n_phases > 1) {   // (pools only) slots that start in a later phase must read as empty pools in the merges between the phases
+        HB_HIP(hipMemsetAsync(a.state_cnt, 0, ws.state_aux, s));
+        HB_HIP(hipMemsetD32Async((hipDeviceptr_t)a.state_thr, 0xFF800000u, ws.state_aux / 4, s));
+    }
+    for (int ph = 0; ph < wl.n_phases; ++ph) {
+        if (launch(wl.phase_begin(ph), wl.phase_end(ph))) return -1;
+        if (ph + 1 < wl.n_phases) {   // the kk-th best ORDERING score of all rows seen so far -> every slot's floor
+            if (knn_seed_floors(ix, a, wl, p.nqt, p.klw, nq, kk, scratch_idx, scratch_dist, s)) return -1;
+            if (a.cl > 1) HB_HIP(hipMemsetAsync(a.prog, 0, ws.prog_bytes - HB_CLUSTER_LINE * 4, s));   // progress words (not the statistics)
+        }
+    }
+    if (c.timed) HB_HIP(hipEventRecord(ix->ev1, s));
+    if (p.calibrated && c.esc == 0 && hb_xcd_collect(ix, p.fam, a.wg_stamp, *wl.sc, wl.shares, wl.n_phases, p.nqt, p.nbt, kk, s, p.auto_cluster)) return -1;
+    return 0;
+}
+// ... and, once whatever follows the kernels has been launched behind them, their time
+static int knn_read_time(hb_index* ix, const knn_call& c) {
+    if (!c.timed) return 0;
+    HB_HIP(hipEventSynchronize(ix->ev1));
+    float ms = 0.f;
+    HB_HIP(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+    ix->last_knn_ms = ms;
+    return 0;
+}
+
+// ---- stage 5: the fp16 path: candidate pass, exact re-rank, certificates, re-search of what failed -------------------------------------
+// workspace of one level: [certificates nq + 64][exact k-th scores nq][floors for a second pass nq] and, once the failures are
+// known, [their rows][queries][aux][floors][ids][distances]
+// -- a caller's search keeps it in fb, the second fp16 pass in fb1 (the fp32 search of what is left has no failures of its own)
+struct knn_level_buf {
+    char*& buf; size_t& bytes;
+    size_t o_kth, o_flo, o_rows;
+    knn_level_buf(hb_index* ix, int esc, int64_t nq) : buf(esc == 0 ? ix->fb : ix->fb1), bytes(esc == 0 ? ix->fb_bytes : ix->fb1_bytes), o_kth(al256((size_t)nq + 64)),
+                                                       o_flo(o_kth + al256((size_t)nq * 4)), o_rows(o_flo + al256((size_t)nq * 4)) {}
+    float* kth() const { return reinterpret_cast<float*>(buf + o_kth); }
+    float* flo() const { return reinterpret_cast<float*>(buf + o_flo); }
+};
+
+// The queries `bad` of this level are searched again: gathered, re-tiled, searched by a nested call, scattered into the outputs.
+static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path& path, const hb_knn_plan& p, const knn_work_list& wl, const knn_workspace& ws,
+                                 const std::vector<int64_t>& bad, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist,
+                                 hipStream_t s) {
+    const int esc = c.esc;
+    const int64_t nf = (int64_t)bad.size();
+    const knn_level_buf lv(ix, esc, nq);
+    char*& fbuf = lv.buf;
+    size_t& fbuf_bytes = lv.bytes;
+    const size_t o_rows = lv.o_rows;
+    // the second pass needs k' = 256 > the first one's, a bank worth a candidate pass, and is not repeated
+    const bool again16 = esc == 0 && ix->fp16_escalation == 0 && p.kc < 256 && ix->ntotal >= 4096;
+    const size_t o_q = o_rows + al256((size_t)nf * 8), o_aux = o_q + al256((size_t)nf * ix->d * 4), o_seed = o_aux + al256((size_t)nf * 8),
+                 o_idx = o_seed + al256((size_t)nf * 4), o_dist = o_idx + al256((size_t)nf * k * 8), tot2 = o_dist + al256((size_t)nf * k * 4);
+    if (fbuf_bytes < tot2) {
+        char* nb = nullptr;
+        HB_HIP(hipMalloc((void**)&nb, tot2 + tot2 / 4));
+        HB_HIP(hipMemcpyAsync(nb, fbuf, o_rows, hipMemcpyDeviceToDevice, s));      // (the seeds of this level)
+        HB_HIP(hipStreamSynchronize(s));
+        HB_HIP(hipFree(fbuf));
+        fbuf = nb; fbuf_bytes = tot2 + tot2 / 4;
+    }
+    const float *kth = lv.kth(), *flo = lv.flo();      // (after the move)
+    int64_t* d_rows = reinterpret_cast<int64_t*>(fbuf + o_rows);
+    float* d_q = reinterpret_cast<float*>(fbuf + o_q);
+    float* d_aux = reinterpret_cast<float*>(fbuf + o_aux);
+    float* d_seed = reinterpret_cast<float*>(fbuf + o_seed);
+    int64_t* d_fi = reinterpret_cast<int64_t*>(fbuf + o_idx);
+    float* d_fd = reinterpret_cast<float*>(fbuf + o_dist);
+    HB_HIP(hipMemcpyAsync(d_rows, bad.data(), (size_t)nf * 8, hipMemcpyHostToDevice, s));
+    if (hb_launch_gather_rows(q_dev, nq, ix->d, d_rows, nf, d_q, s)) return -1;
+    if (hb_launch_gather_rows(again16 ? flo : kth, nq, 1, d_rows, nf, d_seed, s)) return -1;
+    if (hb_launch_rows_to_tiles(d_q, nf, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, s)) return -1;
+    // What the nested search shares with this one THROUGH THE INDEX (everything else it is told by its knn_call):
+    //   q_tiles  overwritten just above with the re-searched queries' tiles (this level has no further use for its own);
+    //   state    taken for the nested search's own pools, and it may move: the candidate launch's stamps go aside first (stamp_keep);
+    //   sched    the nested levels keep ONE work list of their own (sched_esc), so the caller's stays cached;
+    //   fb       this level's workspace, the second fp16 pass's is fb1 (knn_level_buf).
+    if (esc == 0 && ws.a.wg_stamp) {
+        const hb_schedule& sc = *wl.sc;
+        const size_t stamp_bytes = ws.stamp_bytes;
+        if (ix->stamp_keep_blocks < sc.G) {
+            if (ix->stamp_keep) HB_HIP(hipFree(ix->stamp_keep));
+            ix->stamp_keep = nullptr; ix->stamp_keep_blocks = 0;
+            HB_HIP(hipMalloc((void**)&ix->stamp_keep, stamp_bytes));
+            ix->stamp_keep_blocks = sc.G;
+        }
+        HB_HIP(hipMemcpyAsync(ix->stamp_keep, ws.a.wg_stamp, ws.stamp_bytes, hipMemcpyDeviceToDevice, s));
+        ix->wg_stamp_dev = ix->stamp_keep;
+    }
+    int rc = hb_launch_query_aux(d_q, nf, ix->d, d_aux, d_aux + nf, s);      // chain ||q||^2 of the re-searched queries (L2 distances)
+    knn_call nested;
+    nested.esc = again16 ? 1 : 2; nested.seed = d_seed;
+    nested.fp16 = again16 ? 1 : 0; nested.timed = false; nested.q_aux = d_aux; nested.score_out = c.score_out;
+    if (!again16) ix->last_fp16_fallbacks = nf;
+    if (!rc) rc = knn_search(ix, nested, d_q, nf, k, id_base, d_fi, d_fd);
+    if (esc == 0) { ix->last_fp16_escalated = nf; hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks); }
+    if (rc) return -1;
+    if (hb_launch_scatter_rows(d_rows, nf, k, d_fi, d_fd, out_idx, out_dist, s)) return -1;
+    HB_HIP(hipStreamSynchronize(s));         // `bad` and the workspace are reused by the next call
+    return 0;
+}
+
+static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path, const hb_knn_plan& p, const knn_work_list& wl, const knn_workspace& ws,
+                          const float* q_dev, int64_t nq, int k, int64_t id_base, int out_metric, int64_t* out_idx, float* out_dist,
+                          hipStream_t s) {
+    const knn_args& a = ws.a;
+    const hb_schedule& sc = *wl.sc;
+    const int esc = c.esc, kc = p.kc, klw = p.klw, nqt = p.nqt;
+    const bool centred = path.centred;
+    // fp16 copy of the query fragment tiles (the bank's is up to date: top of this function)
+    const int64_t nqp = (int64_t)nqt * HB_QT;
+    if (ensure_bytes((char**)&ix->q16, &ix->q16_bytes, (size_t)nqp * ix->dp16 * 2)) return -1;
+    // centred: fp16 tiles of q - t mu, c_q and ||q - t mu|| per query; a caller's search also derives t and, from it, the rows' init values
+    hb_centre_view cview{nullptr, nullptr, nullptr};
+    if (centred) { if (hb_centre_queries(ix, nq, esc == 0, (_Float16*)ix->q16, &cview, s)) return -1; }
+    else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, (_Float16*)ix->q16, ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
+    const hb_centre_view* cv = centred ? &cview : nullptr;
+    if (ensure_bytes(&ix->cand, &ix->cand_bytes, (size_t)nq * kc * 12)) return -1;
+    int64_t* cand_idx = reinterpret_cast<int64_t*>(ix->cand);
+    float* cand_dist = reinterpret_cast<float*>(ix->cand + (size_t)nq * kc * 8);
+    knn16_args h;
+    h.wg_stamp = a.wg_stamp;
+    h.bank16 = reinterpret_cast<const _Float16*>(ix->tiles16); h.binit = centred ? ix->centre.init16 : ix->binit; h.q16 = reinterpret_cast<const _Float16*>(ix->q16); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
+    h.state_s = a.state_s; h.state_i = a.state_i; h.g16 = ix->dp16 / 16; h.k = kc; h.klw = klw;
+    h.state_cnt = a.state_cnt; h.state_thr = a.state_thr; h.gthr = a.gthr;
+    h.wg_member = a.wg_member; h.prog = a.prog; h.cl = a.cl; h.lag = a.lag; h.cl_stats = a.cl_stats;
+    if (knn_run_phases(ix, c, p, wl, ws, nq, kc, cand_idx, cand_dist, s, [&](const int* begin, const int* end) {
+            h.wg_off = begin; h.wg_end = end;
+            return hb_knn_f16_launch(h, sc.G, s);
+        })) return -1;
+    // the tail: merge to candidates, exact re-rank with the certificates, and the certificates back on the host
+    if (launch_merge(ix, a.state_s, a.state_i, a.state_cnt, a.state_thr, wl.qt_off, wl.qt_slots, sc.max_slots_per_qt, nqt, nq, kc, klw, 0, 0, nullptr,
+                     cand_idx, cand_dist, s)) return -1;
+    const knn_level_buf lv(ix, esc, nq);
+    if (ensure_bytes(&lv.buf, &lv.bytes, lv.o_rows)) return -1;
+    unsigned char* cert = reinterpret_cast<unsigned char*>(lv.buf);
+    float *kth = lv.kth(), *flo = lv.flo();
+    HB_HIP(hipMemsetD32Async((hipDeviceptr_t)kth, 0xFF800000u, (lv.o_rows - lv.o_kth) / 4, s));    // -inf: no seed (a query with fewer than k candidates)
+    const float* seed_in = esc == 1 ? c.seed : nullptr;
+    const float* q_aux = c.q_aux;
+    if (ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal) {
+        if (hb_launch_rerank_rows(ix->rows32, ix->rows32_rs, ix->binit, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax,
+                                  cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
+    } else if (hb_launch_rerank(ix->tiles, ix->binit, ix->g8, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax,
+                                cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
+    if (knn_read_time(ix, c)) return -1;
+    // Queries whose certificate failed are searched again.  ESCALATION (round 6): first by a second fp16 pass with k' = 256 candidates
+    // (the certificate compares the exact k-th best with the fp16 score of rank k': four times the ranks apart) whose pools start from
+    // the floor `kth - 1.001 E` -- every row that can still matter scores above it in fp16, few others do, so the pass appends little and
+    // a list that does not fill up is complete by construction; only what fails again goes to the exact fp32 kernel, which starts from
+    // the exact k-th best found so far as its floor.  A failing query used to cost a share of a whole-bank fp32 search (10 M x 768: 27 ms
+    // per started tile of 256 queries; 5 % failing queries = +45 % on the step): the second pass costs a twentieth of that per query.
+    std::vector<unsigned char> hc((size_t)nq);
+    HB_HIP(hipMemcpyAsync(hc.data(), cert, (size_t)nq, hipMemcpyDeviceToHost, s));
+    HB_HIP(hipStreamSynchronize(s));
+    std::vector<int64_t> bad;
+    for (int64_t i = 0; i < nq; ++i) if (!hc[i]) bad.push_back(i);
+    const int64_t nf = (int64_t)bad.size();
+    if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
+    if (esc == 0 && nf == 0) hb_f16_observe(ix->f16_adapt, path.how16, nq, 0, 0);
+    if (nf > 0 && knn_research_failures(ix, c, path, p, wl, ws, bad, q_dev, nq, k, id_base, out_idx, out_dist, s)) return -1;
+    return 0;
+}
+
+// ---- ... and the fp32 path: the plan's kernel, the merge into the outputs -------------------------------------------------------------
+static int knn_search_f32(hb_index* ix, const knn_call& c, const hb_knn_plan& p, const knn_work_list& wl, const knn_workspace& ws, int64_t nq, int k,
+                          int64_t id_base, int out_metric, int64_t* out_idx, float* out_dist, hipStream_t s) {
+    const hb_schedule& sc = *wl.sc;
     typedef void (*knn_fn)(knn_args);
-    knn_fn fn = wide ? (knn_fn)knn_fused_kernel<false, true> : (knn_fn)knn_fused_kernel<false, false>;
-    if (a.cl > 1) fn = wide ? (knn_fn)knn_fused_kernel<false, true, true> : (knn_fn)knn_fused_kernel<false, false, true>;
-    // Few stages per workgroup: a slot sees few rows, so its cold start (the first tile inserts all 256 rows of every
-    // query) and its insertions (k ln(rows / k) per query) are a visible share of the search -> the instantiations with the
-    // cold start, the scan epilogue (register queue + immediate inserts) and the per-tile exchange of
-    // threshold floors (hbird_knn_dev.h: small_floor_*).  Same box, kernel ms, LDS-staged small / B-direct plain / B-direct small:
-    // 50,176 x 384: 4.86 / 6.76 / 4.62 (round 1: 6.3; 0.49 -> 0.665 of the fp32 MFMA peak); 200 k x 384: 15.9 / 17.7 / 15.1;
-    // 300 k x 768: 74.7 / 72.8 / 70.7; 2 M x 384: 149.3 / 143.1 / 142.3; 1.25 M x 768: 305.9 / 291.2 / 289.8; 2.5 M x 768 (315 k
-    // stages per workgroup): 612.7 / 579.1 / 579.6 -> small below 400 k stages.  The big searches keep the plain
-    // instantiations: at 10 M x 768 the extra code costs 0.3 % (same-box A/B).
-    static const knn_fn cold_fn = knn_fused_kernel<true, false>;
-    // lists: cold_fn / <false, false, COLD>; pools: <WIDE, false, COLD> -- for k > 32 only below 50 k stages (k = 90: 50,176 x 384 4.78 -> 4.45 ms,
-    // k = 64 at 300 k x 768 41.9 -> 40.3, but 2,074,072 x 384 (74 k stages) 142.0 -> 142.7)
-    const long long stages_per_wg = (long long)nqt * nbt / std::max(1, sc.G) * ix->g8;
-    const bool small = !f16 && a.cl == 1 && stages_per_wg < (k > HB_KL ? std::min<long long>(small_limit, 50000) : small_limit);
-    if (small && !wide) fn = cold_fn;
-    const int threads = HB_THREADS;
-    int lds_bytes = fn == cold_fn ? KN_LDS_TOTAL_COLD : KN_LDS_TOTAL;
-    // The query fragments straight into registers (hbird_knn_bd.hip): -3.8 % kernel time at 10 M x 768 (0.895 -> 0.93 of the
-    // fp32 MFMA peak), same bits.  Default for the big LDS-list searches whose stage count per tile is a multiple of four
-    // (D = 384, 768, 1024, ...); variant 3 forces it wherever it applies (tests), variant 4 keeps the LDS-staged kernel.
-    if (ceil) { fn = (knn_fn)knn_fused_kernel<false, true, false, true>; lds_bytes = KN_LDS_TOTAL; }
-    else if (bd_shape && (ix->variant == 0 || ix->variant == 3 || ix->variant == 6)) {
-        fn = hb_knn_bd_kernel(wide, a.cl > 1, small);
-        lds_bytes = hb_knn_bd_lds_bytes(small && !wide);
+    knn_fn fn = nullptr;
+    int lds_bytes = KN_LDS_TOTAL;
+    switch (p.kernel) {      // (which one and why: hb_knn_plan_kernel)
+        case HB_KERNEL_LISTS: fn = knn_fused_kernel<false, false>; break;
+        case HB_KERNEL_LISTS_COLD: fn = knn_fused_kernel<true, false>; lds_bytes = KN_LDS_TOTAL_COLD; break;
+        case HB_KERNEL_POOLS: fn = knn_fused_kernel<false, true>; break;
+        case HB_KERNEL_LISTS_CL: fn = knn_fused_kernel<false, false, true>; break;
+        case HB_KERNEL_POOLS_CL: fn = knn_fused_kernel<false, true, true>; break;
+        case HB_KERNEL_CEIL: fn = knn_fused_kernel<false, true, false, true>; break;
+        default:      // HB_KERNEL_BD + ...: query fragments straight into registers (hbird_knn_bd.hip)
+            fn = hb_knn_bd_kernel(p.wide, ws.a.cl > 1, p.small);
+            lds_bytes = hb_knn_bd_lds_bytes(p.small && !p.wide);
     }
     if (hb_ensure_dyn_lds((const void*)fn, lds_bytes)) return -1;   // per (kernel, device)
-    if (ix->time_kernels) HB_HIP(hipEventRecord(ix->ev0, s));
-    if (n_phases > 1) {   // (pools only) slots that start in a later phase must read as empty pools in the merges between the phases
-        HB_HIP(hipMemsetAsync(a.state_cnt, 0, state_aux, s));
-        HB_HIP(hipMemsetD32Async((hipDeviceptr_t)a.state_thr, 0xFF800000u, state_aux / 4, s));
+    knn_args a = ws.a;
+    // (between two phases the outputs serve as scratch)
+    if (knn_run_phases(ix, c, p, wl, ws, nq, k, out_idx, out_dist, s, [&](const int* begin, const int* end) {
+            a.wg_off = begin; a.wg_end = end;
+            fn<<<dim3((unsigned)sc.G), dim3(HB_THREADS), lds_bytes, s>>>(a);
+            HB_HIP(hipGetLastError());
+            return 0;
+        })) return -1;
+    const float* qn2 = c.q_aux;   // [nq] chain ||q||^2 (valid for L2)
+    const int* pool_cnt = p.wide ? a.state_cnt : nullptr;
+    if (launch_merge(ix, a.state_s, a.state_i, pool_cnt, pool_cnt ? a.state_thr : nullptr, wl.qt_off, wl.qt_slots, sc.max_slots_per_qt, p.nqt, nq, k, p.klw,
+                     id_base, out_metric, qn2, out_idx, out_dist, s)) return -1;
+    return knn_read_time(ix, c);
+}
+
+// One search of at most 256 neighbours as a sequence of stages: path -> screen upkeep -> plan -> work list -> workspace -> the path's kernels.
+static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
+    if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search: k must be in [1, " + std::to_string(HB_MAX_K) + "] (faiss-gpu's limit, search_faiss.py:84-85)");
+    if (k > 256) return hb_launch_knn_bigk(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
+    hipStream_t s = ix->stream;
+    const int esc = c.esc;
+    knn_path path;
+    if (knn_choose_path(ix, c, nq, k, &path)) return -1;
+    if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_screen_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;
+    path.centred = path.f16 && ix->fp16_centre && ix->centre.active;
+    if (esc == 0) { ix->last_path = !path.f16 ? HB_PATH_FP32 : path.wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = path.why; ix->last_centred = path.centred ? 1 : 0; }
+    if (nq == 0) return 0;
+    // score output (sharded searches): the ordering score goes out as it is, whatever the metric
+    const int out_metric = c.score_out ? 0 : ix->metric;
+    if (ix->ntotal == 0) {
+        // empty index: every neighbour is missing (faiss returns -1 labels)
+        std::vector<int64_t> hi((size_t)nq * k, -1);
+        std::vector<float> hd((size_t)nq * k, out_metric == 1 ? INFINITY : -INFINITY);
+        HB_HIP(hipMemcpyAsync(out_idx, hi.data(), hi.size() * 8, hipMemcpyHostToDevice, s));
+        HB_HIP(hipMemcpyAsync(out_dist, hd.data(), hd.size() * 4, hipMemcpyHostToDevice, s));
+        HB_HIP(hipStreamSynchronize(s));
+        return 0;
     }
-    for (int ph = 0; ph < n_phases; ++ph) {
-        a.wg_off = phase_begin(ph); a.wg_end = phase_end(ph);
-        fn<<<dim3((unsigned)sc.G), dim3(threads), lds_bytes, s>>>(a);
-        HB_HIP(hipGetLastError());
-        if (ph + 1 < n_phases) {   // the k-th best ORDERING score of all rows seen so far -> every slot's floor (the outputs serve as scratch)
-            if (seed_floors(k, out_idx, out_dist)) return -1;   // (the outputs serve as scratch)
-            if (a.cl > 1) HB_HIP(hipMemsetAsync(a.prog, 0, prog_bytes - HB_CLUSTER_LINE * 4, s));
-        }
-    }
-    if (ix->time_kernels) HB_HIP(hipEventRecord(ix->ev1, s));
-    if (balance && ix->xcd_balance == 0 && esc == 0 && hb_xcd_collect(ix, 0, a.wg_stamp, sc, shares, n_phases, nqt, nbt, k, s, auto_cluster)) return -1;
-    const float* qn2 = ix->q_aux;   // [nq] chain ||q||^2 (valid for L2)
-    if (launch_merge(ix, a.state_s, a.state_i, pool_cnt, pool_cnt ? a.state_thr : nullptr, reinterpret_cast<const int*>(sched_dev + o_qo),
-                     reinterpret_cast<const int*>(sched_dev + o_qs), sc.max_slots_per_qt, nqt, nq, k, klw, id_base, out_metric,
-                     qn2, out_idx, out_dist, s)) return -1;
-    if (ix->time_kernels) {
-        HB_HIP(hipEventSynchronize(ix->ev1));
-        float ms = 0.f;
-        HB_HIP(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-        ix->last_knn_ms = ms;
-    }
-    return 0;
+    // the plan (hbird_calibrate.cpp).  hb_xcd_calibrate runs BEFORE the cluster shape is chosen: it also decides whether the fp32 clusters stay
+    hb_knn_plan_in pin;
+    pin.f16 = path.f16; pin.wide_first = path.wide_first; pin.esc = esc; pin.ceil = c.ceil_s != nullptr;
+    pin.k = k; pin.nq = nq; pin.ntotal = ix->ntotal; pin.g8 = ix->g8; pin.dp = ix->dp; pin.dp16 = ix->dp16; pin.num_cu = ix->num_cu;
+    pin.force_G = ix->force_G; pin.force_panel = ix->force_panel; pin.force_cq = ix->force_cq; pin.force_cb = ix->force_cb; pin.variant = ix->variant;
+    pin.small_limit = ix->small_limit; pin.phases_on = ix->phases_on; pin.xcd_balance = ix->xcd_balance; pin.xcd_share = ix->xcd_share; pin.sync_lag = ix->sync_lag;
+    hb_knn_plan p;
+    hb_knn_plan_shape(pin, p);
+    if (p.calibrated && esc == 0) hb_xcd_calibrate(ix, p.fam);     // (nested searches run on the shares in use and leave the calibration alone)
+    pin.cl_state = ix->xcal[0].cl_state; pin.cl_choice = ix->xcal[0].cl_choice;
+    hb_knn_plan_clusters(pin, p);
+    knn_work_list wl;
+    if (knn_get_work_list(ix, esc, p, s, &wl)) return -1;
+    hb_knn_plan_kernel(pin, wl.sc->G, p);
+    knn_workspace ws;
+    if (knn_carve_workspace(ix, c, p, wl, nq, k, s, &ws)) return -1;
+    if (path.f16) return knn_search_f16(ix, c, path, p, wl, ws, q_dev, nq, k, id_base, out_metric, out_idx, out_dist, s);
+    return knn_search_f32(ix, c, p, wl, ws, nq, k, id_base, out_metric, out_idx, out_dist, s);
+}
+
+// q_tiles / q_aux must already be prepared by the caller (hb_index_search).
+int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
+    knn_call c;
+    c.fp16 = ix->fp16; c.timed = ix->time_kernels != 0; c.q_aux = ix->q_aux; c.score_out = ix->score_output != 0;
+    return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
 }
