@@ -297,6 +297,11 @@ int hb_exact_screen_replay(int setting, int pinned, int env_off, int k, int ceil
  * kernels: 1 lists, 2 lists cold (small searches), 3 pools, 4 lists clustered, 5 pools clustered, 6 CEIL; register-resident fp32 kernels: 8 + 4
  * wide + 2 clustered + 1 small --, 17 the work list's workgroups, 18 small.  Negative: bad arguments. */
 int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int n_out);
+/* hb_certificate_bound_replay: the bounds of the fp16 screen's certificate without a GPU (tests), evaluated in float by the code the re-rank
+ * kernels compile (csrc/hbird_certificate.h).  in[0..7] (n_in >= 8): 0 D, 1 metric, 2 ||q||, 3 bmax = max ||b||, and of the mean-centred
+ * form 4 ||q - t mu||, 5 cmax = max ||b - mu||, 6 ||mu||, 7 t.  out[0..1] (n_out >= 2): 0 E of the plain pass, 1 E' of the centred pass.
+ * Negative: bad arguments. */
+int hb_certificate_bound_replay(const double* in, int n_in, double* out, int n_out);
 /* Number of queries of the last fp16-mode search that needed the exact fp32 re-search. */
 int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n);
 /* What happens to a query whose certificate fails.  mode 0 (default): ESCALATION -- the failing queries, compacted, get a second fp16 pass

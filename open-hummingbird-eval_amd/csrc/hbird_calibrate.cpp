@@ -1,6 +1,7 @@
 // The calibration decisions of the kNN launcher as plain host code (see hbird_calibrate.h): compiled by hipcc into libhbird_hip.so and,
 // host-only under sanitizers, into lib/build/libhbird_plan_asan.so beside the planner.
 #include "hbird_calibrate.h"
+#include "hbird_certificate.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -357,5 +358,14 @@ extern "C" int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int
     out[0] = p.kc; out[1] = p.wide; out[2] = p.klw; out[3] = p.small_pools; out[4] = p.nqt; out[5] = p.nbt; out[6] = p.G; out[7] = p.fam; out[8] = p.balance;
     out[9] = p.cq; out[10] = p.cb; out[11] = p.auto_cluster; out[12] = p.panel; out[13] = p.phased; out[14] = p.xs; out[15] = p.lag; out[16] = p.kernel;
     out[17] = sched_G; out[18] = p.small;
+    return 0;
+}
+// the fp16 screen's bounds as the re-rank kernels compile them (hbird_certificate.h), in float (include/hbird_hip.h: the slots)
+extern "C" int hb_certificate_bound_replay(const double* in, int n_in, double* out, int n_out) {
+    if (!in || !out || n_in < 8 || n_out < 2 || !(in[0] >= 1.0 && in[0] <= 1048576.0)) return -1;
+    const int d = (int)in[0], metric = in[1] != 0.0 ? 1 : 0;
+    const float qn = (float)in[2], bmax = (float)in[3], qc = (float)in[4], cmax = (float)in[5], mun = (float)in[6], at = fabsf((float)in[7]);
+    out[0] = (double)hb_certificate_bound(qn, bmax, d, metric);
+    out[1] = (double)hb_certificate_bound_centred(qc, cmax, mun, at, qn, bmax, d, metric);
     return 0;
 }

@@ -16,11 +16,6 @@
 #define HB_WAVES 8
 #define HB_BLK 256       // floats per fragment block (32 rows x 8 k) = 1 KiB
 
-#define HB_STAGE_BYTES (16384 + 16384 + 1024)   // A fragments, B fragments, bank-row init values
-#define HB_LDS_LISTS (2 * HB_STAGE_BYTES)
-#define HB_LDS_SCRATCH (HB_LDS_LISTS + 2 * HB_QT * HB_KL * 4)
-#define HB_LDS_TOTAL (HB_LDS_SCRATCH + HB_WAVES * 8 * 64 * 4)
-
 #define HB_ID_NONE 0xFFFFFFFFu
 
 // Optional ROCTx range around a host-side phase (shows up under `rocprofv3 --marker-trace`).  The marker library
@@ -138,17 +133,10 @@ int hb_launch_tiles_to_rows(const float* tiles, int g8, int d, const int64_t* id
 int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
 int hb_launch_tiles_to_f16(const float* t32, int g8, _Float16* t16, int g16, int64_t n_row_tiles, int64_t rt0, int* overflow,
                            hipStream_t s);
-int hb_launch_tiles_to_rows(const float* t32, int g8, float* rows, int rs, int64_t n_row_tiles, int64_t rt0, hipStream_t s);
-int hb_launch_rerank_rows(const float* rows, int rs, const float* binit, int d, const float* q, const float* qn2,
-                          const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
-                          unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric,
-                          int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in = nullptr, float* kth_out = nullptr,
-                          float* floor_out = nullptr, const hb_centre_view* cv = nullptr);
-int hb_launch_rerank(const float* tiles, const float* binit, int g8, int d, const float* q, const float* qn2,
-                     const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
-                     unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric, int64_t ntotal, int64_t* out_idx,
-                     float* out_dist, hipStream_t s, const float* seed_in = nullptr, float* kth_out = nullptr, float* floor_out = nullptr,
-                     const hb_centre_view* cv = nullptr);
+int hb_launch_tiles_to_row_copy(const float* t32, int g8, float* rows, int rs, int64_t n_row_tiles, int64_t rt0, hipStream_t s);
+// the exact re-rank of a pass' candidates (hbird_rerank_dev.h: the argument block); rows != nullptr: from the row-major copy [row][rs], else from the tiles
+struct hb_rerank_args;
+int hb_launch_rerank(const hb_rerank_args& a, const float* tiles, int g8, const float* rows, int rs, hipStream_t s);
 int hb_launch_bnorm_max(const float* bnorm, int64_t n, float* bmax, hipStream_t s);
 int hb_launch_scatter_rows(const int64_t* rows, int64_t n, int k, const int64_t* src_idx, const float* src_dist,
                            int64_t* out_idx, float* out_dist, hipStream_t s);

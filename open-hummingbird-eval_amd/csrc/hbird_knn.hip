@@ -24,6 +24,7 @@
 #include <map>
 
 #include "hbird_knn_dev.h"
+#include "hbird_rerank_dev.h"
 
 // One stage = one k8 fragment group of the pair tile: 32 MFMAs per wave, in two halves of 16 (bank row tiles
 // 0-3 = "X", 4-7 = "Y").  Fragments of the next half are fetched from LDS while the current half is in the
@@ -788,7 +789,7 @@ static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, 
         }
         if (ix->rows32 && ix->rows32_rows < ix->ntotal) {
             const int64_t rt0 = ix->rows32_rows / 32, need_rt = (ix->ntotal + 31) / 32;
-            if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->rows32, rs, need_rt - rt0, rt0, s0)) return -1;
+            if (hb_launch_tiles_to_row_copy(ix->tiles, ix->g8, ix->rows32, rs, need_rt - rt0, rt0, s0)) return -1;
             ix->rows32_rows = ix->ntotal;
         }
     }
@@ -1045,7 +1046,6 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     hb_centre_view cview{nullptr, nullptr, nullptr};
     if (centred) { if (hb_centre_queries(ix, nq, esc == 0, (_Float16*)ix->q16, &cview, s)) return -1; }
     else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, (_Float16*)ix->q16, ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
-    const hb_centre_view* cv = centred ? &cview : nullptr;
     if (ensure_bytes(&ix->cand, &ix->cand_bytes, (size_t)nq * kc * 12)) return -1;
     int64_t* cand_idx = reinterpret_cast<int64_t*>(ix->cand);
     float* cand_dist = reinterpret_cast<float*>(ix->cand + (size_t)nq * kc * 8);
@@ -1067,13 +1067,11 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     unsigned char* cert = reinterpret_cast<unsigned char*>(lv.buf);
     float *kth = lv.kth(), *flo = lv.flo();
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)kth, 0xFF800000u, (lv.o_rows - lv.o_kth) / 4, s));    // -inf: no seed (a query with fewer than k candidates)
-    const float* seed_in = esc == 1 ? c.seed : nullptr;
     const float* q_aux = c.q_aux;
-    if (ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal) {
-        if (hb_launch_rerank_rows(ix->rows32, ix->rows32_rs, ix->binit, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax,
-                                  cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
-    } else if (hb_launch_rerank(ix->tiles, ix->binit, ix->g8, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax,
-                                cert, kc, nq, k, id_base, ix->metric, out_metric, ix->ntotal, out_idx, out_dist, s, seed_in, kth, flo, cv)) return -1;
+    const hb_rerank_args ra{ix->binit, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax, cert, kc, nq, k, id_base, ix->metric, out_metric,
+                            ix->ntotal, out_idx, out_dist, hb_rerank_seeds{esc == 1 ? c.seed : nullptr, kth, flo}, cview};
+    const bool row_copy = ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal;
+    if (hb_launch_rerank(ra, ix->tiles, ix->g8, row_copy ? ix->rows32 : nullptr, ix->rows32_rs, s)) return -1;
     if (knn_read_time(ix, c)) return -1;
     // Queries whose certificate failed are searched again.  ESCALATION (round 6): first by a second fp16 pass with k' = 256 candidates
     // (the certificate compares the exact k-th best with the fp16 score of rank k': four times the ranks apart) whose pools start from

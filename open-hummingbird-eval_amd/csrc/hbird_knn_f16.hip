@@ -10,6 +10,7 @@
 //
 // The per-query candidate pools live in HBM (the WIDE path of the fp32 kernels), only the thresholds stay in registers.
 #include "hbird_knn_dev.h"
+#include "hbird_rerank_dev.h"
 #include <algorithm>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -265,76 +266,31 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
     wg_stamp<knn16_args>(1);
 }
 
-// What the re-rank leaves for an ESCALATION of the queries whose certificate fails (hb_launch_knn), and what it takes from the pass before:
-//   seed_in  [query] (second pass only): the fp16-score floor this pass ran under -- every row with an fp16 score >= it was offered to the
-//            pools, so a candidate list that is NOT full holds every such row: the rows outside score below the floor in fp16, hence below
-//            floor + E exactly, and the answer is exact when its k-th best exceeds that;
-//   kth_out  [query]: the exact k-th best score among this pass's candidates -- a lower bound of the true k-th best: the floor of an fp32
-//            search of this query (ties pass: floor_from_key);
-//   floor_out[query]: kth - 1.001 E, a hair lower: every row that can still enter the top k has an exact score >= kth, hence an fp16 score
-//            above this -- the floor of a second, wider fp16 pass (0.001 E is twenty times the rounding of these few operations).
-// CENTRED (hbird_f16_centre.hip): the pass ran on q - t mu and b - mu and its scores lack the query's constant c_q = q.mu -- every comparison of
-// an exact score with a pass score adds it to the latter; floor_out seeds the second PASS and is written in the pass' units (kth - c_q - 1.001 E'),
-// kth_out seeds the fp32 kernel and stays exact.
-struct hb_rerank_seeds { const float* seed_in; float* kth_out; float* floor_out; };
-template <bool CENTRED>
-__device__ __forceinline__ bool hb_rerank_finish(const hb_rerank_seeds& sd, int64_t qi, bool ok, bool list_not_full, bool have_kth, float s, float E, float cq) {
-    if (sd.seed_in && list_not_full && have_kth && !ok) ok = CENTRED ? s > sd.seed_in[qi] + cq + E : s > sd.seed_in[qi] + E;
-    if (sd.kth_out) {
-        const bool fin = have_kth && E < INFINITY && fabsf(s) < INFINITY && (!CENTRED || fabsf(cq) < INFINITY);      // (false for NaN as well)
-        float f = CENTRED ? s - cq - 1.001f * E : s - 1.001f * E;
-        f = f - fabsf(f) * 2.4e-7f - 1e-37f;
-        sd.kth_out[qi] = fin ? s : -INFINITY;
-        sd.floor_out[qi] = fin ? f : -INFINITY;
-    }
-    return ok;
-}
-
-// The centred pass' bound E' >= |pass score + c_q - exact score| (derivation: DESIGN.md 4).  qc = ||fl(q - t mu)||, cmax = max ||fl(b - mu)||,
-// qn = ||q||, bmax = max ||b||, mun = ||mu||; D' = D + 4 pays for the fmaf of init16 and the additions of the comparison itself.
-__device__ __forceinline__ float hb_centred_E(const hb_centre_view& cv, int64_t qi, float qn, float bmax, int d, int metric) {
-    const float cmax = cv.sc[0], mun = cv.sc[1], at = fabsf(cv.sc[3]), qc = cv.qcn[qi];
-    const float du = (float)(d + 4) * 1.2e-7f;
-    return qc * cmax * (1.05f / 1024.0f + du)                                                      // fp16 images of both centred operands; the pass' fp32 sums
-           + du * (qn * bmax + qn * mun + 2.0f * at * mun * cmax + (metric == 1 ? bmax * bmax : 0.0f))   // exact chain; chain of c_q; chain of g, init16 and its share of the sums; |row init|
-           + (qc + cmax) * sqrtf((float)d) * 6e-8f                                                 // fp16 subnormal inputs
-           + 1e-30f;
-}
+// what both re-rank kernels take after their row source and its stride: the fields of hb_rerank_args, in their order (plain parameters, not
+// the block by value: hbird_rerank_dev.h)
+#define HB_RERANK_PARAMS                                                                                                     \
+    const float* __restrict__ binit, int d, const float* __restrict__ q, const float* __restrict__ qn2,                      \
+    const int64_t* __restrict__ cand, const float* __restrict__ cand_score, const float* __restrict__ qnorm,                \
+    const float* __restrict__ bmax, unsigned char* __restrict__ certified, int kc, int64_t nq, int k, int64_t id_base,      \
+    int metric, int out_metric, int64_t ntotal, int64_t* __restrict__ out_idx, float* __restrict__ out_dist,                \
+    hb_rerank_seeds sd, hb_centre_view cv
 
 // Exact re-rank: one wave per query; lane j scores candidates j, j+64, ... with the fp32 chain arithmetic of the fp32
 // kernel (acc = row init; acc = fmaf(q_k, b_k, acc) for k ascending over the fp32 fragment tiles), then the wave
-// ranks them by (score desc, id asc) and writes the best k.
+// ranks them by (score desc, id asc) and writes the best k (hb_rerank_tail, with the certificate).
 template <bool CENTRED>
-__global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ tiles, const float* __restrict__ binit, int g8,
-                                                     int d, const float* __restrict__ q, const float* __restrict__ qn2,
-                                                     const int64_t* __restrict__ cand, const float* __restrict__ cand_score,
-                                                     const float* __restrict__ qnorm, const float* __restrict__ bmax,
-                                                     unsigned char* __restrict__ certified, int kc, int64_t nq, int k,
-                                                     int64_t id_base, int metric, int out_metric, int64_t ntotal,
-                                                     int64_t* __restrict__ out_idx, float* __restrict__ out_dist, hb_rerank_seeds sd, hb_centre_view cv) {
+__global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ tiles, int g8, HB_RERANK_PARAMS) {
     __shared__ float s_sc[4][256];
-    __shared__ int64_t s_id[4][256];
+    __shared__ int64_t s_id[4][256];                     // (the list's 8 bytes: on rerank_rows_kernel's 4-byte form the ranking loop takes 24 more VGPRs here)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t qi = (int64_t)blockIdx.x * 4 + wv;
     if (qi >= nq) return;   // wave-uniform
     const float* qr = q + qi * (int64_t)d;
-    // E >= |fp16 score - exact score| of any row of this query (both inputs rounded to fp16: relative 2^-10 per product,
-    // Cauchy-Schwarz over the row; fp32 accumulation: D * 2^-23) -- the certificate below, and which candidates need an exact score at
-    // all: the list comes sorted by fp16 score, its first k have exact scores >= (k-th fp16 score) - E, so a candidate whose fp16
-    // score is more than 2E below the k-th's is exactly below k of them and cannot be in the answer.  Its row is not read (a row
-    // is 2 x D/8 sixteen-byte pieces 512 B apart: the re-rank is bound by the sectors it touches; 50,176 x 384, 12,544 queries:
-    // 0.96 ms of a 2.4 ms search).  A non-finite E (query norm) skips nothing, and fails the certificate.
-    const float E = CENTRED ? hb_centred_E(cv, qi, qnorm[qi], bmax[0], d, metric)
-                            : qnorm[qi] * bmax[0] * (1.05f / 1024.0f + (float)d * 2.4e-7f)
-                              + (qnorm[qi] + bmax[0]) * sqrtf((float)d) * 6e-8f                 // fp16 subnormal inputs
-                              + (metric == 1 ? (float)d * 1.2e-7f * 0.5f * bmax[0] * bmax[0] : 0.0f)  // |row init| in the sums
-                              + 1e-30f;
-    const float cq = CENTRED ? cv.cq[qi] : 0.0f;
-    const float cut = (k <= kc && cand[qi * (int64_t)kc + (k - 1)] >= 0) ? cand_score[qi * (int64_t)kc + (k - 1)] - 2.0f * E : -INFINITY;
+    const hb_rerank_query qc = hb_rerank_query_of<CENTRED>(qi, qnorm, bmax, d, metric, cv, cand, cand_score, kc, k);
     for (int c = lane; c < kc; c += 64) {
         const int64_t row = cand[qi * (int64_t)kc + c];
         float acc = -INFINITY;
-        if (row >= 0 && !(c >= k && cand_score[qi * (int64_t)kc + c] < cut)) {
+        if (hb_rerank_needs_score(row, c, k, cand_score + qi * (int64_t)kc, qc.cut)) {
             acc = binit[row];
             const float* base = tiles + ((row >> 5) * (int64_t)g8) * HB_BLK + (int)(row & 31) * 4;
             for (int g = 0; g < g8; ++g) {
@@ -352,59 +308,7 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ t
         s_id[wv][c] = row;
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's own LDS writes are visible to its lanes
-    for (int c = lane; c < kc; c += 64) {
-        const float s = s_sc[wv][c];
-        const int64_t id = s_id[wv][c];
-        int rank = 0;
-        for (int j = 0; j < kc; ++j) {
-            const float sj = s_sc[wv][j];
-            const int64_t ij = s_id[wv][j];
-            bool better;
-            if (ij < 0 || id < 0) better = (ij >= 0 && id < 0) || (ij < 0 && id < 0 && j < c);
-            else better = (sj > s) || (sj == s && (ij < id || (ij == id && j < c)));
-            rank += better;
-        }
-        if (rank == k - 1) {
-            // Certificate: every row outside the candidate list has an fp16 score <= the kc-th candidate's, hence an
-            // exact score <= that + E.  If the exact k-th best is strictly above that bound, no outside row can enter the
-            // top k: the answer IS the fp32 answer.
-            // The argument needs finite fp16 operands: a query with |q_i| > 65504 becomes inf in fp16 and its scores inf / NaN
-            // (||q|| <= 65504 rules that out; a NaN / inf norm fails the test too), and a candidate list that is not full
-            // although the bank has kc rows has lost rows to NaN / -inf fp16 scores that nothing bounds.
-            const int64_t last = cand[qi * (int64_t)kc + kc - 1];
-            const bool finite_q = CENTRED ? (cv.qcn[qi] <= 65504.0f && qnorm[qi] < INFINITY && fabsf(cq) < INFINITY) : qnorm[qi] <= 65504.0f;   // (centred: the operands of the pass are q - t mu)
-            bool ok = last < 0 && ntotal < kc && finite_q;   // fewer than kc rows exist: every row was a candidate
-            if (last >= 0 && id >= 0 && finite_q) {
-                ok = CENTRED ? s > cand_score[qi * (int64_t)kc + kc - 1] + cq + E : s > cand_score[qi * (int64_t)kc + kc - 1] + E;
-            }
-            ok = hb_rerank_finish<CENTRED>(sd, qi, ok, last < 0, id >= 0 && finite_q, s, E, cq);
-            certified[qi] = ok ? 1 : 0;
-        }
-        if (rank < k) {
-            const int64_t o = qi * (int64_t)k + rank;
-            if (id < 0) { out_idx[o] = -1; out_dist[o] = out_metric == 1 ? INFINITY : -INFINITY; }
-            else {
-                out_idx[o] = id + id_base;
-                if (out_metric == 1) { const float d2 = fmaf(-2.0f, s, qn2[qi]); out_dist[o] = d2 > 0.0f ? d2 : 0.0f; }
-                else out_dist[o] = s;
-            }
-        }
-    }
-}
-
-int hb_launch_rerank(const float* tiles, const float* binit, int g8, int d, const float* q, const float* qn2,
-                     const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
-                     unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric,
-                     int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in, float* kth_out, float* floor_out,
-                     const hb_centre_view* cv) {
-    if (nq == 0) return 0;
-    if (kc > 256) return hb_fail("hb_index_search: too many candidates for the re-rank kernel");
-    auto fn = cv ? rerank_kernel<true> : rerank_kernel<false>;
-    fn<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s>>>(tiles, binit, g8, d, q, qn2, cand, cand_score, qnorm, bmax,
-                                                          certified, kc, nq, k, id_base, metric, out_metric, ntotal, out_idx, out_dist,
-                                                          hb_rerank_seeds{seed_in, kth_out, floor_out}, cv ? *cv : hb_centre_view{nullptr, nullptr, nullptr});
-    HB_HIP(hipGetLastError());
-    return 0;
+    hb_rerank_tail<CENTRED>(s_sc[wv], s_id[wv], lane, qi, qc.E, qc.cq, cand, cand_score, qnorm, qn2, certified, kc, k, id_base, out_metric, ntotal, out_idx, out_dist, sd, cv);
 }
 
 // ---- the re-rank on a row-major copy of the bank ---------------------------------------------------------------------
@@ -433,39 +337,25 @@ __global__ __launch_bounds__(256) void tiles_to_rows_kernel(const float* __restr
     if (8 * g0 + 4 * c < rs) *reinterpret_cast<f32x4*>(rows + (rt * 32 + i) * (int64_t)rs + 8 * g0 + 4 * c) = out;
 }
 
-int hb_launch_tiles_to_rows(const float* t32, int g8, float* rows, int rs, int64_t n_row_tiles, int64_t rt0, hipStream_t s) {
+int hb_launch_tiles_to_row_copy(const float* t32, int g8, float* rows, int rs, int64_t n_row_tiles, int64_t rt0, hipStream_t s) {
     if (n_row_tiles <= 0) return 0;
     tiles_to_rows_kernel<<<dim3((unsigned)n_row_tiles, (unsigned)((rs / 8 + 3) / 4)), dim3(256), 0, s>>>(t32, g8, rows, rs, rt0);
     HB_HIP(hipGetLastError());
     return 0;
 }
 
-#define RRW_NONE 0xFFFFFFFFu
 #define RRW_STRIDE 36      // dwords per row of the LDS image: 128 B of values + 16 B (lane t's b128 reads of row t: no bank conflicts)
 template <bool CENTRED>
-__global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restrict__ rows, int rs, const float* __restrict__ binit,
-                                                          int d, const float* __restrict__ q, const float* __restrict__ qn2,
-                                                          const int64_t* __restrict__ cand, const float* __restrict__ cand_score,
-                                                          const float* __restrict__ qnorm, const float* __restrict__ bmax,
-                                                          unsigned char* __restrict__ certified, int kc, int64_t nq, int k,
-                                                          int64_t id_base, int metric, int out_metric, int64_t ntotal,
-                                                          int64_t* __restrict__ out_idx, float* __restrict__ out_dist, hb_rerank_seeds sd, hb_centre_view cv) {
+__global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restrict__ rows, int rs, HB_RERANK_PARAMS) {
     __shared__ float s_sc[4][256];
-    __shared__ unsigned s_id[4][256];                    // bank rows (below 2^32); RRW_NONE: no candidate
+    __shared__ unsigned s_id[4][256];                    // bank rows; HB_ID_NONE: no candidate
     __shared__ int s_act[4][256];
     __shared__ __attribute__((aligned(16))) float s_img[4][66 * RRW_STRIDE];   // 64 rows + the query's + one of padding: 50 KB per workgroup, three per CU
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t qi = (int64_t)blockIdx.x * 4 + wv;
     if (qi >= nq) return;   // wave-uniform
     const float* qr = q + qi * (int64_t)d;
-    // (E and the skip rule: rerank_kernel)
-    const float E = CENTRED ? hb_centred_E(cv, qi, qnorm[qi], bmax[0], d, metric)
-                            : qnorm[qi] * bmax[0] * (1.05f / 1024.0f + (float)d * 2.4e-7f)
-                              + (qnorm[qi] + bmax[0]) * sqrtf((float)d) * 6e-8f
-                              + (metric == 1 ? (float)d * 1.2e-7f * 0.5f * bmax[0] * bmax[0] : 0.0f)
-                              + 1e-30f;
-    const float cq = CENTRED ? cv.cq[qi] : 0.0f;
-    const float cut = (k <= kc && cand[qi * (int64_t)kc + (k - 1)] >= 0) ? cand_score[qi * (int64_t)kc + (k - 1)] - 2.0f * E : -INFINITY;
+    const hb_rerank_query qc = hb_rerank_query_of<CENTRED>(qi, qnorm, bmax, d, metric, cv, cand, cand_score, kc, k);
     // the candidates that need an exact score, compacted: s_act[0 .. n_act)
     int n_act = 0;
     for (int c0 = 0; c0 < kc; c0 += 64) {
@@ -474,9 +364,9 @@ __global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restric
         bool act = false;
         if (c < kc) {
             row = cand[qi * (int64_t)kc + c];
-            act = row >= 0 && !(c >= k && cand_score[qi * (int64_t)kc + c] < cut);
+            act = hb_rerank_needs_score(row, c, k, cand_score + qi * (int64_t)kc, qc.cut);
             s_sc[wv][c] = -INFINITY;
-            s_id[wv][c] = row >= 0 ? (unsigned)row : RRW_NONE;
+            s_id[wv][c] = row >= 0 ? (unsigned)row : HB_ID_NONE;
         }
         const unsigned long long m = __ballot(act);
         if (act) s_act[wv][n_act + __popcll(m & ((1ull << lane) - 1ull))] = c;
@@ -539,49 +429,18 @@ __global__ __launch_bounds__(256) void rerank_rows_kernel(const float* __restric
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's own LDS writes are visible to its lanes
     __builtin_amdgcn_wave_barrier();
-    for (int c = lane; c < kc; c += 64) {
-        const float s = s_sc[wv][c];
-        const int64_t id = s_id[wv][c] == RRW_NONE ? -1 : (int64_t)s_id[wv][c];
-        int rank = 0;
-        for (int j = 0; j < kc; ++j) {
-            const float sj = s_sc[wv][j];
-            const int64_t ij = s_id[wv][j] == RRW_NONE ? -1 : (int64_t)s_id[wv][j];
-            bool better;
-            if (ij < 0 || id < 0) better = (ij >= 0 && id < 0) || (ij < 0 && id < 0 && j < c);
-            else better = (sj > s) || (sj == s && (ij < id || (ij == id && j < c)));
-            rank += better;
-        }
-        if (rank == k - 1) {   // the certificate: rerank_kernel
-            const int64_t last = cand[qi * (int64_t)kc + kc - 1];
-            const bool finite_q = CENTRED ? (cv.qcn[qi] <= 65504.0f && qnorm[qi] < INFINITY && fabsf(cq) < INFINITY) : qnorm[qi] <= 65504.0f;   // (centred: the operands of the pass are q - t mu)
-            bool ok = last < 0 && ntotal < kc && finite_q;
-            if (last >= 0 && id >= 0 && finite_q) ok = CENTRED ? s > cand_score[qi * (int64_t)kc + kc - 1] + cq + E : s > cand_score[qi * (int64_t)kc + kc - 1] + E;
-            ok = hb_rerank_finish<CENTRED>(sd, qi, ok, last < 0, id >= 0 && finite_q, s, E, cq);
-            certified[qi] = ok ? 1 : 0;
-        }
-        if (rank < k) {
-            const int64_t o = qi * (int64_t)k + rank;
-            if (id < 0) { out_idx[o] = -1; out_dist[o] = out_metric == 1 ? INFINITY : -INFINITY; }
-            else {
-                out_idx[o] = id + id_base;
-                if (out_metric == 1) { const float d2 = fmaf(-2.0f, s, qn2[qi]); out_dist[o] = d2 > 0.0f ? d2 : 0.0f; }
-                else out_dist[o] = s;
-            }
-        }
-    }
+    hb_rerank_tail<CENTRED>(s_sc[wv], s_id[wv], lane, qi, qc.E, qc.cq, cand, cand_score, qnorm, qn2, certified, kc, k, id_base, out_metric, ntotal, out_idx, out_dist, sd, cv);
 }
+#undef HB_RERANK_PARAMS
 
-int hb_launch_rerank_rows(const float* rows, int rs, const float* binit, int d, const float* q, const float* qn2,
-                          const int64_t* cand, const float* cand_score, const float* qnorm, const float* bmax,
-                          unsigned char* certified, int kc, int64_t nq, int k, int64_t id_base, int metric, int out_metric,
-                          int64_t ntotal, int64_t* out_idx, float* out_dist, hipStream_t s, const float* seed_in, float* kth_out, float* floor_out,
-                          const hb_centre_view* cv) {
-    if (nq == 0) return 0;
-    if (kc > 256) return hb_fail("hb_index_search: too many candidates for the re-rank kernel");
-    auto fn = cv ? rerank_rows_kernel<true> : rerank_rows_kernel<false>;
-    fn<<<dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s>>>(rows, rs, binit, d, q, qn2, cand, cand_score, qnorm, bmax,
-                                                          certified, kc, nq, k, id_base, metric, out_metric, ntotal, out_idx, out_dist,
-                                                          hb_rerank_seeds{seed_in, kth_out, floor_out}, cv ? *cv : hb_centre_view{nullptr, nullptr, nullptr});
+// rows != nullptr: the row-major copy [row][rs]; else the fragment tiles.  a.cv.cq != nullptr: a centred pass
+int hb_launch_rerank(const hb_rerank_args& a, const float* tiles, int g8, const float* rows, int rs, hipStream_t s) {
+    if (a.nq == 0) return 0;
+    if (a.kc > 256) return hb_fail("hb_index_search: too many candidates for the re-rank kernel");
+    const bool centred = a.cv.cq != nullptr;
+    auto fn = rows ? (centred ? rerank_rows_kernel<true> : rerank_rows_kernel<false>) : (centred ? rerank_kernel<true> : rerank_kernel<false>);
+    fn<<<dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, s>>>(rows ? rows : tiles, rows ? rs : g8, a.binit, a.d, a.q, a.qn2, a.cand, a.cand_score, a.qnorm, a.bmax,
+                                                            a.certified, a.kc, a.nq, a.k, a.id_base, a.metric, a.out_metric, a.ntotal, a.out_idx, a.out_dist, a.sd, a.cv);
     HB_HIP(hipGetLastError());
     return 0;
 }

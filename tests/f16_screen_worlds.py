@@ -45,10 +45,10 @@ NNZ = N_ADV + 2
 _N_LO, _N_HI = 16, 2047                                # integer range of a tuning component (n u: exact in fp16, never subnormal)
 
 
-def bound_E(qn, bmax, D, metric):
-    """The documented bound, restated (float64)."""
+def bound_E(qn, bmax, D, metric, c16=1.05):
+    """The documented bound, restated (float64).  c16: the factor on 2^-10 (1.05 as shipped)."""
     qn = np.asarray(qn, dtype=np.float64)
-    return (qn * bmax * (1.05 / 1024.0 + D * 2.4e-7) + (qn + bmax) * np.sqrt(float(D)) * 6e-8
+    return (qn * bmax * (c16 / 1024.0 + D * 2.4e-7) + (qn + bmax) * np.sqrt(float(D)) * 6e-8
             + (D * 1.2e-7 * 0.5 * bmax * bmax if metric == 1 else 0.0) + 1e-30)
 
 

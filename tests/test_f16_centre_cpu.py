@@ -42,7 +42,7 @@ GAPS = (0.5, 0.7, 0.8, 0.9, 0.95)
 
 
 def bound_E_centred(qn, qcn, bmax, cmax, mun, t, D, metric, c16=1.05):
-    """E' of csrc/hbird_knn_f16.hip (hb_centred_E), restated in float64.  c16: the factor on 2^-10 (1.05 as shipped)."""
+    """E' of csrc/hbird_certificate.h (hb_certificate_bound_centred), restated in float64.  c16: the factor on 2^-10 (1.05 as shipped)."""
     qn, qcn = np.asarray(qn, np.float64), np.asarray(qcn, np.float64)
     du = (D + 4) * 1.2e-7
     return (qcn * cmax * (c16 / 1024.0 + du)

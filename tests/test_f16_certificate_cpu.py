@@ -15,11 +15,15 @@ Model mutation (a single pass whose certificate uses f E; groups at g = 0.5 / 0.
     f = 0.75  D = 64: certifies 3 groups, D = 384: 3 (L2: 2) -- every one of them with a true neighbour missing;  D = 768: none
     f = 0.65  D = 768: certifies 3 groups, all wrong
 """
+import ctypes
+import itertools
+
 import numpy as np
 import pytest
 
 import f16_screen_worlds as fw
 import oracle
+from test_f16_centre_cpu import bound_E_centred
 
 GAPS = (0.5, 0.7, 0.8, 0.9, 0.95)
 FLOOR = {64: 0.83, 384: 0.77, 768: 0.71}
@@ -122,3 +126,49 @@ def test_subnormal_world_needs_the_subnormals(metric):
     print(f"subnormal_world metric={metric}: err/E kept {kept['err_over_E'].max():.3f}, flushed {flushed['err_over_E'].max():.1f}")
     assert flushed["err_over_E"].max() > 1.0
     assert not flushed["contained"].all()
+
+
+# ---- the restated bounds against the constants the kernels compile ----------------------------------------------------------------------------
+NORMS = [float(np.float32(v)) for v in (2.0 ** -14, 1e-3, 1.0, 30.0, 6e4)]      # fp32 numbers: what the replay computes with
+
+
+def _shipped_bounds(D, metric, qn, bmax, qcn, cmax, mun, t):
+    """hb_certificate_bound_replay: (E, E') in float, by the code of csrc/hbird_certificate.h that the re-rank kernels call."""
+    from hbird_mi import _lib
+    a = (ctypes.c_double * 8)(D, metric, qn, bmax, qcn, cmax, mun, t)
+    o = (ctypes.c_double * 2)()
+    assert _lib.lib().hb_certificate_bound_replay(a, 8, o, 2) == 0
+    return o[0], o[1]
+
+
+@pytest.mark.parametrize("metric", [0, 1])
+@pytest.mark.parametrize("D", [24, 33, 384, 768])
+def test_restated_bounds_are_the_shipped_constants(D, metric):
+    """bound_E (this folder's worlds) and bound_E_centred (test_f16_centre_cpu.py) restate E and E' in float64; the CPU proofs that "E is a bound"
+    hold for the kernels only while the restatements ARE the kernels' expressions.  Norms from the smallest normal fp16 number to the end of its
+    range.  Tolerance 1e-5 relative: a bound is about ten fp32 operations on positive terms, each within 6e-8.  With 0.75 for 1.05 on the
+    Python side the comparison fails: it can tell a changed constant."""
+    worst = worst_c = mut = mut_c = 0.0
+    for qn, bmax in itertools.product(NORMS, NORMS):
+        E, _ = _shipped_bounds(D, metric, qn, bmax, 0.0, 0.0, 0.0, 0.0)
+        ref = float(fw.bound_E(qn, bmax, D, metric))
+        worst = max(worst, abs(E - ref) / ref)
+        mut = max(mut, abs(E - float(fw.bound_E(qn, bmax, D, metric, c16=0.75))) / ref)
+        for qcn, cmax, mun, t in itertools.product(NORMS[::2], NORMS[::2], (0.0, NORMS[0], 1.0, NORMS[-1]), (0.0, -0.5, 3.0)):
+            _, Ec = _shipped_bounds(D, metric, qn, bmax, qcn, cmax, mun, t)
+            ref = float(bound_E_centred(qn, qcn, bmax, cmax, mun, t, D, metric))
+            worst_c = max(worst_c, abs(Ec - ref) / ref)
+            mut_c = max(mut_c, abs(Ec - float(bound_E_centred(qn, qcn, bmax, cmax, mun, t, D, metric, c16=0.75))) / ref)
+    print(f"D={D} metric={metric}: worst relative difference E {worst:.2e}, E' {worst_c:.2e}; with 0.75 for 1.05: {mut:.3f}, {mut_c:.3f}")
+    assert worst <= 1e-5 and worst_c <= 1e-5
+    assert mut > 1e-5 and mut_c > 1e-5, "a mutated constant went unnoticed"
+
+
+def test_bound_replay_rejects_bad_arguments():
+    from hbird_mi import _lib
+    L = _lib.lib()
+    a, o = (ctypes.c_double * 8)(64, 0, 1, 1, 1, 1, 1, 1), (ctypes.c_double * 2)()
+    assert L.hb_certificate_bound_replay(None, 8, o, 2) < 0 and L.hb_certificate_bound_replay(a, 7, o, 2) < 0
+    assert L.hb_certificate_bound_replay(a, 8, o, 1) < 0 and L.hb_certificate_bound_replay(a, 8, None, 2) < 0
+    a[0] = 0
+    assert L.hb_certificate_bound_replay(a, 8, o, 2) < 0

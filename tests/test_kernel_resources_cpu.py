@@ -1,4 +1,4 @@
-"""Spill guard: every shipped kNN and K5 kernel instantiation is held to the committed register / spill / scratch baseline.
+"""Spill guard: every shipped kNN, re-rank and K5 kernel instantiation is held to the committed register / spill / scratch baseline.
 No test fails when a header change for ONE kernel pushes ANOTHER over its scalar registers -- it only gets slower (round 2: +12 % at
 k = 90 from 16 reloads of spilled SGPRs per stage) -- so the build leaves hipcc's per-kernel resource report in lib/build/ (untracked) and this test
 compares it with tests/golden/kernel_resources.json (rewrite it with `python tools/kernel_resources.py --write-baseline` when a
@@ -44,7 +44,11 @@ def test_no_kernel_spills_more_than_the_baseline():
     # held to the figures of the hand-copied kernels it replaced -- no more registers, spills or scratch, no fewer waves per SIMD
     k5 = [k for k in now if k.startswith("aggregate_")]
     assert len(k5) >= 12, f"resource reports of the K5 units missing or unparsed: {sorted(now)}"
-    for k in k5:
+    # ... and so are the exact re-rank's kernels, which share hbird_rerank_dev.h (the certificate): the baseline rows are those of the kernels
+    # that carried a copy each (rerank_rows_kernel: 123 / 129 VGPRs, one step from losing a wave, and 39 spilled SGPRs)
+    rerank = [k for k in now if k.startswith("rerank_")]
+    assert sorted(rerank) == ["rerank_kernel<false>", "rerank_kernel<true>", "rerank_rows_kernel<false>", "rerank_rows_kernel<true>"], sorted(now)
+    for k in k5 + rerank:
         if k not in base:
             problems.append(f"{k}: not in the baseline (python tools/kernel_resources.py --write-baseline)")
             continue

@@ -570,6 +570,46 @@ def test_use_fp16_rerank_on_the_row_major_copy(cuda_device, M, D, nq, k, metric)
     _check_exact(i4, d4, q, more, k, metric)
 
 
+@pytest.mark.parametrize("centre", [False, True])
+@pytest.mark.parametrize("metric", ["dot_product", "l2"])
+@pytest.mark.parametrize("D", [33, 50])            # the last 32-value chunk holds 1 and 18 values; 33 is no multiple of 4
+def test_use_fp16_rerank_forms_agree_in_certificate_outcomes(cuda_device, D, metric, centre):
+    """The two row sources of the exact re-rank (fragment tiles, row-major copy) share one certificate: beyond the fp32 search's bits they
+    fail and pass the SAME queries, at ragged shapes -- 131 queries (the last workgroup holds three), a planted cluster of 150 near-duplicate
+    rows (wider than k' = 64, inside the second pass's 256: the seeds path runs), with and without the centred copy.  (With one copy of the
+    certificate per kernel, before they shared it: 31 queries escalate at D = 33 and 32 at D = 50 in all eight cases, none reaches the fp32 kernel.)"""
+    M, nq, k = 6000, 131, 30
+    rng = np.random.default_rng(17 + D)
+    bank = gi.unit_bank(M, D, seed=M + D)
+    c = bank[10].copy()
+    for r in range(200, 350):                      # 150 rows within 1e-4 of one direction
+        v = c + 1e-4 * rng.standard_normal(D).astype(np.float32)
+        bank[r] = v / np.linalg.norm(v)
+    q = gi.vit_like_queries(nq, D, seed=nq + D)
+    q[:30] = 4.0 * c + 1e-3 * rng.standard_normal((30, D)).astype(np.float32)   # queries aimed at the cluster
+    qd = torch.from_numpy(q).cuda()
+    m = 0 if metric == "dot_product" else 1
+    ref = HipFlatIndex(D, m, 0)
+    ref.add(torch.from_numpy(bank).cuda())
+    ref.set_fp16(0)
+    ref_i, ref_d = ref.search(qd, k)
+    ix = HipFlatIndex(D, m, 0)
+    ix.add(torch.from_numpy(bank).cuda())
+    ix.set_fp16(True)
+    ix.set_fp16_centre(centre)
+    ix.set_fp16_escalation(True)
+    counters = []
+    for rerank_copy in (1, 2):
+        ix.set_rerank_copy(rerank_copy)
+        i1, d1 = ix.search(qd, k)
+        assert (ix.rerank_copy_bytes() > 0) == (rerank_copy == 1)
+        assert torch.equal(i1, ref_i) and torch.equal(d1.view(torch.int32), ref_d.view(torch.int32))
+        counters.append((ix.last_fp16_escalated(), ix.last_fp16_fallbacks()))
+    print(f"D={D} {metric} centre={centre}: (escalated, fallbacks) rows {counters[0]} tiles {counters[1]}")
+    assert counters[0] == counters[1], counters
+    assert counters[0][0] >= 1, counters           # the seeds path ran
+
+
 def test_use_fp16_certificate_and_exact_fallback(cuda_device):
     """Near-duplicate bank rows cannot be ranked by fp16 scores: the per-query certificate must fail for them and the
     exact fp32 re-search must deliver the fp32 answer anyway; well-separated queries stay on the fast path."""

@@ -5,7 +5,7 @@ library, seeded inputs generated once).  For changes to the kNN launcher that mu
 usage: ab_knn.py bits lib1.so lib2.so ...   per case ids and distances as uint32 words, hb_index_schedule_info, hb_last_search_path and the two
                                             fp16 counters of every library against the first library's; one case per branch of the launcher's
                                             plan, at the smallest shape that reaches it
-       ab_knn.py time lib1.so lib2.so ...   whole searches at three of the project's measured sizes: HIP events around 20 back-to-back
+       ab_knn.py time lib1.so lib2.so ...   whole searches at the project's measured sizes: HIP events around 20 back-to-back
                                             hb_index_search calls, median of 9 repetitions after 3 warm-ups, the libraries alternating inside
                                             every repetition (name the first library twice, as two files, for the A/A spread: the resolution)
 One JSON line per case; AB_KNN_OUT=file collects them.  `bits` exits with status 1 on any difference."""
@@ -91,6 +91,7 @@ def bits(libs):
         ("fp16 state 2 below its bound", wide, 30, f16(2, 1)), ("fp16 state 2, rerank copy", (66_000, 384, 700), 30, f16(2, 1)),
         ("fp16 state 2, no rerank copy", (66_000, 384, 700), 30, f16(2, 2)), ("fp16 state 1 k=90", wide, 90, f16(1, 0)),
         ("fp16 centred", wide, 30, f16(1, 1) + [L("hb_index_set_fp16_centre", 1)]),
+        ("fp16 centred, no rerank copy", wide, 30, f16(1, 2) + [L("hb_index_set_fp16_centre", 1)]),
         ("k=300", small, 300, []), ("k=600", small, 600, []), ("k=300 on a use_fp16 index", wide, 300, f16(1, 0)),
         ("a bank of one tile", (200, 64, 300), 30, []), ("a bank of one tile k=5", (200, 64, 300), 5, []), ("an empty bank", (0, 64, 300), 30, []),
     ]
@@ -130,12 +131,16 @@ def time_legs(libs, warm=3, reps=9, inner=20):
     names = [os.path.basename(l.path) for l in libs]
     # (the last leg once more with equal XCD shares: every library calibrates shares of its own from its own launches' stamps, so at that size
     # the libraries otherwise run on different work lists)
-    for M, D, nq, k, fp16, equal in ((20_000, 384, 784, 30, 0, 0), (50_176, 384, 12_544, 30, 0, 0), (300_000, 768, 21_904, 30, 1, 0), (300_000, 768, 21_904, 30, 1, 1)):
+    # copy: hb_index_set_rerank_copy (0: automatic -- the fp16 legs re-rank from the row-major copy; 2: from the fragment tiles)
+    for M, D, nq, k, fp16, equal, copy in ((20_000, 384, 784, 30, 0, 0, 0), (50_176, 384, 12_544, 30, 0, 0, 0), (300_000, 768, 21_904, 30, 1, 0, 0),
+                                           (300_000, 768, 21_904, 30, 1, 1, 0), (300_000, 768, 21_904, 30, 1, 0, 2)):
         g = torch.Generator(device=dev); g.manual_seed(11)
         rows, q = torch.randn((M, D), generator=g, device=dev), torch.randn((nq, D), generator=g, device=dev)
         hs = [l.bank(D, 0, rows) for l in libs]
         for l, h in zip(libs, hs):
             l.ok(l.L.hb_index_set_fp16(h, fp16))
+            if copy:
+                l.ok(l.L.hb_index_set_rerank_copy(h, copy))
             if equal:
                 l.ok(l.L.hb_index_set_xcd_weights(h, 1, None))
         idx, dist = torch.empty((nq, k), dtype=torch.int64, device=dev), torch.empty((nq, k), device=dev)
@@ -150,7 +155,7 @@ def time_legs(libs, warm=3, reps=9, inner=20):
                 if it >= warm:
                     t[i].append(e0.elapsed_time(e1) / inner)
         med = [float(np.median(v)) for v in t]
-        emit({"mode": "time", "leg": f"{M} x {D}, {nq} queries, k={k}, set_fp16({fp16})" + (", equal shares" if equal else ""), "median_ms": dict(zip(names, (round(m, 4) for m in med))),
+        emit({"mode": "time", "leg": f"{M} x {D}, {nq} queries, k={k}, set_fp16({fp16})" + (", equal shares" if equal else "") + (f", set_rerank_copy({copy})" if copy else ""), "median_ms": dict(zip(names, (round(m, 4) for m in med))),
               "over_first": dict(zip(names, (round(m / med[0], 4) for m in med))),
               "min_max_ms": dict(zip(names, ([round(min(v), 4), round(max(v), 4)] for v in t))), "reports": [l.reports(h) for l, h in zip(libs, hs)]})
         for l, h in zip(libs, hs):
