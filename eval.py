@@ -70,6 +70,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "then carries miou_grid, keyed 'k=30,beta=0.02' (with --memory-sizes: miou_grid_by_memory_size)")
     p.add_argument("--grid-beta", type=_positive_float, nargs="+", default=None, metavar="B",
                    help="sweep over the softmax temperature of the label aggregation (0.02 in the reference), see --grid-k")
+    p.add_argument("--leave-one-out", action="store_true",
+                   help="score on the TRAINING images instead of the validation split (not in the reference): every training image queries the "
+                        "bank with its own rows excluded, so --grid-k / --grid-beta / --memory-sizes can be chosen without tuning on validation data")
+    p.add_argument("--leave-one-out-images", type=_positive_int, default=None, metavar="N", help="stop the leave-one-out pass after N images")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -179,6 +183,7 @@ def main(argv: Optional[List[str]] = None) -> None:
                               frame_size=tuple(args.frame_size) if args.frame_size else None,
                               window_stride=args.window_stride, f_mem_p=args.f_mem_p, l_mem_p=args.l_mem_p,
                               **({"memory_sizes": args.memory_sizes} if args.memory_sizes else {}),
+                              **({"leave_one_out": True, "leave_one_out_images": args.leave_one_out_images} if args.leave_one_out else {}),
                               **({"grid_k": args.grid_k, "grid_beta": args.grid_beta} if args.grid_k or args.grid_beta else {}))
     from hbird_mi import hbird_eval as _he
     by_size = grid = grid_by_size = None
@@ -197,6 +202,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         result = result[args.memory_size] if args.memory_size in result else result[max(result)] if result else float("nan")
     summary = {"miou": float(result), "seconds": round(time.time() - t0, 3), "nn_method": args.nn_method,
                "dataset": args.dataset_name, "n_neighbours": args.n_neighbours, **_he.last_run_info}
+    if args.leave_one_out:
+        summary["leave_one_out"] = True
     if by_size is not None:
         summary["miou_by_memory_size"] = by_size
     if grid is not None:

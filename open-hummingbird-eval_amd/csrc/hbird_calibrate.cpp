@@ -369,3 +369,26 @@ extern "C" int hb_certificate_bound_replay(const double* in, int n_in, double* o
     out[1] = (double)hb_certificate_bound_centred(qc, cmax, mun, at, qn, bmax, d, metric);
     return 0;
 }
+// the rungs of an excluding search (hbird_calibrate.h)
+int hb_exclude_plan(int k, int64_t gmax, int rungs[2]) {
+    if (k < 1 || k > HB_MAX_K || gmax < 0) return -1;
+    const int64_t need = (int64_t)k + gmax;
+    if (need > HB_MAX_K) return -2;
+    const int64_t r0 = 256 * (((int64_t)k + std::min<int64_t>(k, gmax) + 255) / 256);
+    if (r0 >= need) { rungs[0] = (int)need; return 1; }
+    rungs[0] = (int)r0; rungs[1] = (int)need;
+    return 2;
+}
+extern "C" int hb_exclude_plan_replay(int k, int64_t gmax, int* rungs, int max_rungs) {
+    int r[2] = {0, 0};
+    const int n = hb_exclude_plan(k, gmax, r);
+    if (n == -1) return hb_fail("hb_exclude_plan_replay: k must be in [1, " + std::to_string(HB_MAX_K) + "] and gmax >= 0");
+    if (n == -2) {
+        hb_fail("excluding search: k = " + std::to_string(k) + " plus the largest row group (gmax = " + std::to_string(gmax) + " rows) exceeds the limit of " +
+                       std::to_string(HB_MAX_K) + " neighbours per search: use a smaller memory_size or fewer epochs per group");
+        return -2;
+    }
+    if (!rungs || max_rungs < n) return hb_fail("hb_exclude_plan_replay: rungs is NULL or holds fewer than " + std::to_string(n) + " entries");
+    for (int i = 0; i < n; ++i) rungs[i] = r[i];
+    return n;
+}

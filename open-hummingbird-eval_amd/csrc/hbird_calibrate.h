@@ -143,3 +143,11 @@ inline int hb_knn_workgroups(int force_G, int num_cu) { return force_G > 0 ? for
 void hb_knn_plan_shape(const hb_knn_plan_in& in, hb_knn_plan& p);
 void hb_knn_plan_clusters(const hb_knn_plan_in& in, hb_knn_plan& p);
 void hb_knn_plan_kernel(const hb_knn_plan_in& in, int sched_G, hb_knn_plan& p);
+
+// ---- the rungs of an excluding search (hb_index_search_excluding, hbird_exclude.hip) -----------------------------------------------------
+// The best k rows outside a group of at most gmax rows are the first k non-excluded entries of the best need = k + gmax rows.  Few queries
+// lose a whole group from the top of their list: rung 0 fetches r0 = 256 * ceil((k + min(k, gmax)) / 256) entries -- room for as many excluded
+// entries as kept ones, rounded up to whole pool passes of 256, which cost the same -- and only the queries it leaves incomplete are searched
+// at need.  r0 >= need: ONE rung at need, complete by construction.
+// -> the rung count (1 or 2), rungs[0 .. count) ascending; -1: k outside [1, HB_MAX_K] or gmax < 0; -2: need > HB_MAX_K.
+int hb_exclude_plan(int k, int64_t gmax, int rungs[2]);

@@ -88,7 +88,7 @@ extern "C" int hb_index_free(hb_index_t* ix) {
     (void)hipSetDevice(ix->device);
     (void)hipStreamSynchronize(ix->stream);
     void* ptrs[] = {ix->tiles, ix->binit, ix->bnorm, ix->labels, ix->q_tiles, ix->q_aux, ix->state, ix->sched_dev, ix->tmp,
-                    ix->tiles16, ix->stamp_keep, ix->q16, ix->cand, ix->bmax, ix->fb, ix->fb1, ix->sched_esc_dev, ix->bigk, ix->mtmp, ix->f16_flag, ix->labels16, ix->lab_flag, ix->rows32};
+                    ix->tiles16, ix->stamp_keep, ix->q16, ix->cand, ix->bmax, ix->fb, ix->fb1, ix->sched_esc_dev, ix->bigk, ix->mtmp, ix->f16_flag, ix->labels16, ix->lab_flag, ix->rows32, ix->row_groups, ix->excl, ix->excl1};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     hb_centre_drop(ix);
     for (auto& c : ix->xcal) { if (c.stamp_host) (void)hipHostFree(c.stamp_host); if (c.stamp_ev) (void)hipEventDestroy(c.stamp_ev); }
@@ -379,6 +379,7 @@ extern "C" int hb_index_reset(hb_index_t* ix) {
     }
     HB_HIP(hipMemsetAsync(ix->bmax, 0, 4, s));
     ix->ntotal = 0; ix->nlabels = 0; ix->lab_checked = 0; ix->f16_rows = 0; ix->f16_overflow = 0; ix->rows32_rows = 0;
+    ix->row_groups_n = 0; ix->n_groups = 0; ix->gmax = 0;      // the row-group table goes with the rows
     ix->centre.rows = 0;      // (f16_rows = 0: a centred copy derives its mean anew from the rows of the next search)
     if (ix->lab_flag) HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, s));
     if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s));

@@ -108,6 +108,12 @@ struct hb_index {
     double last_knn_ms = 0.0;                            // HIP-event time of the last knn kernel launch
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int time_kernels = 0;
+    // searches that exclude one row group per query (hb_index_set_row_groups / hb_index_search_excluding, hbird_exclude.hip)
+    int32_t* row_groups = nullptr; int64_t row_groups_n = 0, row_groups_cap = 0;   // device copy of groups[n]; n == 0: no table
+    int n_groups = 0; int64_t gmax = 0;                  // ... its group count and the largest group's rows
+    char* excl = nullptr; size_t excl_bytes = 0;         // workspace of an excluding search: staging, rung 0's lists, flags ...
+    char* excl1 = nullptr; size_t excl1_bytes = 0;       // ... and of its rung 1 (sized once the incomplete queries are counted)
+    int64_t last_excl[4] = {0, 0, 0, 0};                 // {rungs run, queries sent to rung 1, kf of the last rung run, gmax}
 };
 
 void hb_set_error(const std::string& msg);
@@ -172,6 +178,10 @@ struct hb_grid_spec { int ks[16]; float betas[16]; int nk, nb; };
 int hb_grid_check(const char* who, const int* ks, int nk, const float* betas, int nb, int k_list, hb_grid_spec* gs);
 int hb_launch_aggregate_grid(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq, int k_list,
                              int64_t id_base, const hb_grid_spec& gs, float* out, hipStream_t s);
+// the filter of an excluding search (hbird_exclude.hip); incomplete_opt: a device counter the launch adds its incomplete queries to
+int hb_launch_exclude_filter(const int64_t* idx, const float* dist, int64_t nq, int k_list, int64_t id_base, const int32_t* groups, int64_t n_rows,
+                             const int32_t* qgroups, int k, float pad, int64_t* out_idx, float* out_dist, int32_t* complete_opt, int32_t* incomplete_opt,
+                             hipStream_t s);
 int hb_launch_patch_label_hist(const int64_t* y, int64_t B, int H, int W, int ps, int C, int map255, float* out,
                                hipStream_t s);
 int hb_launch_normalize_rows(const float* x, int64_t n, int d, float* out, hipStream_t s);

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("HBIRD_HIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libhbird_hip.so")   # override: A/B builds
@@ -139,6 +139,16 @@ SIGNATURES_GRID = {
                                                c_void_p, c_void_p, c_void_p, c_int]),
 }
 
+# ... and include/hbird_hip_exclude.h (searches that exclude one row group per query, csrc/hbird_exclude.hip: leave-one-image-out evaluation)
+SIGNATURES_EXCLUDE = {
+    "hb_index_set_row_groups": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int]),
+    "hb_index_search_excluding": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int]),
+    "hb_exclude_filter": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+    "hb_index_last_exclusion": (c_int, [c_void_p, POINTER(c_int64)]),
+    "hb_exclude_plan_replay": (c_int, [c_int, c_int64, POINTER(c_int), c_int]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -160,8 +170,8 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()):
-            if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay") or name == "hb_last_error"):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()):
+            if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree
             fn.restype = res

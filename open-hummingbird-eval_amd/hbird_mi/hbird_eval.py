@@ -627,6 +627,11 @@ class HbirdEvaluation:
             ids, starts_new, images_new, k_new, dataset_size_new = self._view_geometry(memory_size, images, rows_per_image)
         with torch.cuda.device(self.gpu_device):
             self.index.use_current_stream()
+            try:
+                self._groups_to_index()            # the view's rows keep their images (leave-one-out): select_rows hands groups[ids] over
+                carried = self.row_groups()
+            except ValueError:
+                carried = None                     # (no geometry and no table given: the view has none either)
             index = self.index.select_rows(ids)
             index.use_current_stream()
         view = HbirdEvaluation.from_index(self.feature_extractor, index, self.num_classes,
@@ -646,7 +651,128 @@ class HbirdEvaluation:
         view._bank_block_starts, view._dataset_images = starts_new, images_new
         view._dataset_size = dataset_size_new
         view.bank_loaded = False
+        if carried is not None:
+            view._row_groups = carried[torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu()]
+            view._row_groups_on_index = index.row_groups is not None
+            view._loo_images = self._leave_one_out_images()
         return view
+
+    # ------------------------------------------------------------------------------------------------
+    # leave-one-image-out: the bank evaluated on its own training images, every query excluding the rows of the image it came from
+    # (HipFlatIndex.search_excluding, csrc/hbird_exclude.hip; DESIGN.md section 4, "Leave-one-image-out searches")
+    # ------------------------------------------------------------------------------------------------
+    def set_row_groups(self, groups) -> None:
+        """The dataset image of every bank row, given by the caller (int tensor [ntotal], -1 = no image): for a loaded or `from_index` bank,
+        which has no build geometry to derive it from."""
+        g = torch.as_tensor(groups).detach().reshape(-1).cpu()
+        if g.numel() and (g.dtype.is_floating_point or g.dtype == torch.bool):
+            raise ValueError(f"set_row_groups: groups must be integers, got {g.dtype}")
+        if g.numel() != self.index.ntotal:
+            raise ValueError(f"set_row_groups: {g.numel()} groups for a bank of {self.index.ntotal} rows")
+        self._row_groups, self._row_groups_on_index = g.to(torch.int32), False
+        self._loo_images = None
+
+    def row_groups(self) -> torch.Tensor:
+        """int32 [ntotal] (CPU): the dataset image of every bank row.  Bank blocks are appended in (epoch, image) order, block b belongs to
+        image b % images -- with augmentation_epoch > 1 an image's rows are not one range.  ValueError on a loaded or `from_index` bank
+        (no build geometry) unless `set_row_groups` gave the table; a `memory_view` carries its rows' images."""
+        given = getattr(self, "_row_groups", None)
+        if given is not None:
+            return given
+        starts, n_img = self._bank_block_starts, self._dataset_images
+        if starts is None or not n_img:
+            raise ValueError("row_groups: this bank was not built here (loaded, or from_index): it has no geometry -- call set_row_groups(tensor)")
+        st = torch.as_tensor(starts, dtype=torch.int64)
+        g = torch.repeat_interleave(torch.arange(st.numel() - 1, dtype=torch.int64) % int(n_img), st[1:] - st[:-1]).to(torch.int32)
+        if g.numel() != self.index.ntotal:
+            raise ValueError(f"row_groups: the build geometry covers {g.numel()} rows, the bank holds {self.index.ntotal}")
+        return g
+
+    def _leave_one_out_images(self) -> int:
+        """How many images a leave-one-out pass may see: the images of the build (a view: of the bank it was cut from)."""
+        n = getattr(self, "_loo_images", None)
+        if n is None:
+            g = self.row_groups()             # (ValueError: a bank without geometry and without a given table)
+            n = self._dataset_images if getattr(self, "_row_groups", None) is None else int(g.max().item()) + 1 if g.numel() else 0
+        return int(n)
+
+    def _groups_to_index(self) -> None:
+        """The row-group table onto the index (once; again after set_row_groups or when the bank has grown)."""
+        if self.world > 1 or self.sharded or len(self.local_gpus) > 1 or not isinstance(self.index, HipFlatIndex):
+            raise ValueError("leave-one-out searches are single-index -- not available under torch.distributed or with several GPUs in one process")
+        g = self.row_groups()
+        have = self.index.row_groups
+        if have is None or have.numel() != g.numel() or not getattr(self, "_row_groups_on_index", False):
+            self.index.set_row_groups(g, max(self._leave_one_out_images(), int(g.max().item()) + 1 if g.numel() else 0))
+            self._row_groups_on_index = True
+
+    def evaluate_leave_one_out(self, loader, eval_spatial_resolution: int, n_neighbours=None, betas=None, views=None, ignore_index: int = 255,
+                               max_images: Optional[int] = None, window=None) -> Dict[tuple, float]:
+        """`evaluate_grid` of the bank ON ITS OWN TRAINING IMAGES: `loader` yields the bank's images in the order of the build pass (the
+        project's data modules do: shuffle=False), the i-th image seen queries with group i, and every search excludes the bank rows of the
+        query's own image (`search_aggregate_grid_excluding`) -- so (k, beta, memory size) can be chosen without touching the validation split.
+        Not in the reference.  One pass, one excluding search per batch and bank; every configuration's mIoU is what `evaluate_grid` gives when,
+        image by image, the bank is replaced by its `memory_view(rows=all rows but that image's)`.
+        `views={key: HbirdEvaluation}`: the `memory_view`s of this bank (they carry their rows' images).  `max_images`: stop after that many
+        images (the cost control).  -> {(k, beta): mIoU}, with `views` {(key, k, beta): mIoU}.
+        ValueError when more images arrive than the bank was built from, for a bank without geometry (`row_groups`), under torch.distributed,
+        with a multi-GPU index and with `window=`."""
+        from hbird_mi.nn.search_hip import grid_plan
+        if window is not None:
+            raise ValueError("evaluate_leave_one_out: sliding windows (window=) are not supported")
+        if max_images is not None and int(max_images) < 1:
+            raise ValueError("evaluate_leave_one_out: max_images must be positive")
+        banks = {None: self} if views is None else dict(views)
+        if not banks:
+            raise ValueError("evaluate_leave_one_out: views is empty")
+        for key, ev in list(banks.items()) + [(None, self)]:
+            if not isinstance(ev, HbirdEvaluation):
+                raise ValueError(f"evaluate_leave_one_out: views[{key!r}] is not an HbirdEvaluation")
+            if ev.world > 1 or ev.sharded or len(ev.local_gpus) > 1 or not isinstance(ev.index, HipFlatIndex):
+                raise ValueError("evaluate_leave_one_out: excluding searches are single-index -- not available under torch.distributed or with "
+                                 "several GPUs in one process")
+            if ev.num_classes != self.num_classes or ev.gpu_device != self.gpu_device:
+                raise ValueError(f"evaluate_leave_one_out: views[{key!r}] differs from this evaluator in class count or device")
+        n_images = self._leave_one_out_images()
+        for ev in banks.values():
+            with torch.cuda.device(self.gpu_device):
+                ev.index.use_current_stream()
+                ev._groups_to_index()
+        plan = grid_plan(self.n_neighbours if n_neighbours is None else n_neighbours, self.beta if betas is None else betas)
+        metrics = {key: [PredsmIoU(self.num_classes, self.num_classes, ignore_index=ignore_index, device=self.gpu_device,
+                                   store_reordered_preds=False) for _ in plan.configs] for key in banks}
+        self.feature_extractor = self.feature_extractor.to(self.device)
+        S = eval_spatial_resolution
+        limit = n_images if max_images is None else min(n_images, int(max_images))
+        seen = 0
+        logger.info("Starting leave-one-out loop: %d configurations, %d bank(s), %d image(s)...", len(plan.configs), len(banks), limit)
+        with torch.no_grad(), torch.cuda.device(self.gpu_device):
+            for bi, (x, y) in tqdm(self._prefetched(enumerate(loader), True), desc="Leave-one-out loop"):
+                if max_images is not None and seen >= limit:
+                    break
+                if max_images is not None and seen + x.shape[0] > limit:
+                    x, y = x[:limit - seen], y[:limit - seen]
+                if seen + x.shape[0] > n_images:
+                    raise ValueError(f"evaluate_leave_one_out: the loader yields more than the {n_images} images the bank was built from "
+                                     "(it must yield the bank's images, in the order of the build pass)")
+                y = (y.to(self.gpu_device) * 255).long()
+                feats = self._tokens(x)
+                B, N, D = feats.shape
+                q = feats.reshape(B * N, D).contiguous()
+                qgroups = torch.arange(seen, seen + B, dtype=torch.int32, device=q.device).repeat_interleave(N)
+                seen += B
+                for key, ev in banks.items():
+                    ev.index.use_current_stream()
+                    lh = ev.index.search_aggregate_grid_excluding(q, plan.ks, plan.betas, qgroups, id_base=0)
+                    for i, m in enumerate(metrics[key]):
+                        m.update_from_label_hat(y, lh[i].view(B, N, -1), S)
+        out = {}
+        for key in banks:
+            for (k, beta), m in zip(plan.configs, metrics[key]):
+                jac = m.compute(is_global_zero=True, sync_distributed=False, return_reordered=False)[0]
+                out[(k, beta) if views is None else (key, k, beta)] = jac
+        logger.info("Leave-one-out evaluation complete (%d images).", seen)
+        return out
 
     # ------------------------------------------------------------------------------------------------
     # query path (reference evaluate 184-265, _find_nearest_key_to_query 611-637, _cross_attention 575-609)
@@ -992,7 +1118,7 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      train_fs_path: Optional[str] = None, val_fs_path: Optional[str] = None,
                      frame_size: Optional[Tuple[int, int]] = None, window_stride: Optional[int] = None,
                      f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, grid_k=None, grid_beta=None,
-                     memory_sizes=None):
+                     leave_one_out: bool = False, leave_one_out_images: Optional[int] = None, memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -1007,7 +1133,13 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     `grid_k=[...]` / `grid_beta=[...]` (either or both; the other defaults to `n_neighbours` / 0.02): the sweep over n_neighbours and the softmax
     temperature out of ONE validation pass with one search per batch (`HbirdEvaluation.evaluate_grid`); the call returns {(k, beta): mIoU},
     combined with `memory_sizes` {size: {(k, beta): mIoU}} -- still one validation pass, over all sizes.  Not with sliding windows,
-    return_knn_details or torch.distributed (ValueError)."""
+    return_knn_details or torch.distributed (ValueError).
+    `leave_one_out=True`: the scores come from the TRAIN loader instead of the validation loader -- every training image queries the bank
+    with its own rows excluded (`HbirdEvaluation.evaluate_leave_one_out`), so n_neighbours, the temperature and the memory size can be chosen
+    without tuning on the validation split; `leave_one_out_images=N` stops after N images.  The return shape is that of the call it
+    accompanies: a float, {(k, beta): mIoU} with a grid, {size: ...} with `memory_sizes`.  Same restrictions as the grid."""
+    if leave_one_out and (return_knn_details or frame_size is not None):
+        raise ValueError("leave_one_out is not available with return_knn_details or sliding windows (frame_size)")
     if memory_sizes is not None and memory_size is None:
         raise ValueError("memory_sizes needs memory_size: the bank is built once, at memory_size, and the listed sizes are views of it")
     if nn_params is None:
@@ -1044,6 +1176,30 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     last_run_info.clear()
     last_run_info.update(bank_loaded=bool(evaluator.bank_loaded), bank_build_s=float(evaluator.bank_build_s),
                          bank_rows=int(evaluator.total_rows), train_batches_loaded=int(evaluator.batches_loaded))
+    if leave_one_out:
+        gridded = grid_k is not None or grid_beta is not None
+        loo = dict(n_neighbours=grid_k if grid_k is not None else n_neighbours, betas=grid_beta if grid_beta is not None else evaluator.beta,
+                   ignore_index=effective_ignore, max_images=leave_one_out_images)
+        if memory_sizes is None:
+            res = evaluator.evaluate_leave_one_out(train_loader, eval_spatial_resolution, **loo)
+            return res if gridded else next(iter(res.values()))
+        views = {}
+        for size in memory_sizes:
+            size = int(size)
+            if size > memory_size or size in views:
+                continue
+            views[size] = evaluator if size == memory_size else evaluator.memory_view(
+                memory_size=size, rows_per_image=evaluator.num_sampled_features if evaluator.bank_loaded else None)
+        results = {size: {} for size in views}
+        try:
+            if views:
+                for (size, k, beta), v in evaluator.evaluate_leave_one_out(train_loader, eval_spatial_resolution, views=views, **loo).items():
+                    results[size][(k, beta)] = v
+        finally:
+            for ev in views.values():
+                if ev is not evaluator:
+                    ev.index.close()
+        return results if gridded else {size: next(iter(res.values())) for size, res in results.items()}
     if grid_k is not None or grid_beta is not None:
         grid = dict(n_neighbours=n_neighbours if grid_k is None else grid_k, betas=evaluator.beta if grid_beta is None else grid_beta,
                     ignore_index=effective_ignore, window=window, return_knn_details=return_knn_details)

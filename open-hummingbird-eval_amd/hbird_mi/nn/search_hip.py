@@ -92,6 +92,16 @@ def grid_plan(ks, betas, max_configs: int = _lib.GRID_MAX_CONFIGS) -> GridPlan:
     return GridPlan(tuple(k_out), tuple(b_out), configs, launches)
 
 
+def exclude_plan(k: int, gmax: int):
+    """The rungs (list lengths) of an excluding search for k and the largest group's size -- hb_exclude_plan_replay, the rule the
+    engine itself runs (csrc/hbird_calibrate.cpp); no GPU.  ValueError when k + gmax exceeds 2048."""
+    rungs = (ctypes.c_int * 2)()
+    n = _lib.lib().hb_exclude_plan_replay(int(k), int(gmax), rungs, 2)
+    if n < 0:
+        raise ValueError(_lib.last_error())
+    return [int(rungs[i]) for i in range(n)]
+
+
 def _new(like, shape, dtype):
     """An uninitialised output beside `like`: a tensor on its device for a CUDA tensor, a numpy array otherwise (dtype: a torch dtype)."""
     if isinstance(like, torch.Tensor) and like.is_cuda:
@@ -147,6 +157,7 @@ class HipFlatIndex:
 
     def reset(self):
         _lib.check(_lib.lib().hb_index_reset(self._h))
+        self._groups, self._n_groups = None, 0      # (hb_index_reset clears the row-group table)
 
     def add(self, x, normalize: bool = False):
         """x: float32 [n, d], numpy / CPU tensor (host path) or CUDA tensor on this GPU (device path)."""
@@ -315,6 +326,89 @@ class HipFlatIndex:
             out, idx, dist = out.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
         return (out, idx, dist) if want_neighbours else out
 
+    # searches that exclude one row group per query (hb_index_set_row_groups / hb_index_search_excluding, csrc/hbird_exclude.hip): leave-one-
+    # image-out evaluation -- the best k rows outside a group are the first k non-excluded entries of the best k + gmax, bit for bit
+    def set_row_groups(self, groups, n_groups: Optional[int] = None):
+        """The row-group table: groups[ntotal] integers, a value in [0, n_groups) names the row's group, -1 = in no group (never excluded);
+        None clears it.  n_groups defaults to max(groups) + 1.  Keeps a device copy (`row_groups`).  ValueError for a value outside the range."""
+        if groups is None:
+            _lib.check(_lib.lib().hb_index_set_row_groups(self._h, None, 0, 0, 0))
+            self._groups, self._n_groups = None, 0
+            return
+        g = torch.as_tensor(groups)
+        if g.numel() and (g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool):
+            raise ValueError(f"row groups must be integers, got {g.dtype}")
+        g = g.detach().reshape(-1).to(device=torch.device("cuda", self.device), dtype=torch.int32).contiguous()
+        if n_groups is None:
+            n_groups = int(g.max().item()) + 1 if g.numel() else 0
+        _lib.check(_lib.lib().hb_index_set_row_groups(self._h, _ptr(g), g.numel(), int(n_groups), 1), ValueError)
+        self._groups, self._n_groups = (g if g.numel() else None), (int(n_groups) if g.numel() else 0)
+
+    @property
+    def row_groups(self) -> Optional[torch.Tensor]:
+        """The device copy of the row-group table (int32 [n]) or None."""
+        return getattr(self, "_groups", None)
+
+    def _hand_groups(self, src: "HipFlatIndex", ids, appended: bool):
+        """After rows `ids` of `src` arrived here: the view of src's group table, groups[ids], through set_row_groups."""
+        sg = src.row_groups
+        if sg is None or ids.numel() == 0:
+            return
+        part = sg[ids.to(sg.device)]
+        mine = self.row_groups
+        if appended and mine is not None and mine.numel() + part.numel() == self.ntotal:
+            part = torch.cat([mine, part])
+        if part.numel() == self.ntotal:
+            self.set_row_groups(part, max(src._n_groups, getattr(self, "_n_groups", 0)))
+
+    def search_excluding(self, q, k: int, qgroups, id_base: int = 0):
+        """-> (idx int64 [nq,k], dist float32 [nq,k]) as `search`, over the rows whose group differs from qgroups[i] (-1: exclude nothing):
+        original row ids, and the bits of `search` on `select_rows(the allowed rows, ascending)`.  ValueError for a missing or short table, a
+        group id outside the range and k + (largest group) > 2048 -- raised before anything is searched."""
+        on_dev, q = self._as_f32(q)
+        nq = q.shape[0]
+        qg = torch.as_tensor(qgroups).detach().reshape(-1)
+        if qg.numel() != nq:
+            raise ValueError(f"search_excluding: {qg.numel()} query groups for {nq} queries")
+        if qg.numel() and (qg.dtype.is_floating_point or qg.dtype == torch.bool):
+            raise ValueError(f"query groups must be integers, got {qg.dtype}")
+        qg = qg.to(device=q.device if on_dev else "cpu", dtype=torch.int32).contiguous()
+        idx, dist = _new(q, (nq, k), torch.int64), _new(q, (nq, k), torch.float32)
+        _lib.check(_lib.lib().hb_index_search_excluding(self._h, _ptr(q), nq, int(k), int(id_base), _ptr(qg), _ptr(idx), _ptr(dist), int(on_dev)),
+                   ValueError)
+        return idx, dist
+
+    def last_exclusion(self) -> dict:
+        """Of the last excluding search: rungs run, queries sent to rung 1, the list length of the last rung run, the largest group's size."""
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.lib().hb_index_last_exclusion(self._h, out))
+        return {"rungs": int(out[0]), "rung1_queries": int(out[1]), "kf": int(out[2]), "gmax": int(out[3])}
+
+    def _excluding_lists(self, q, k, qgroups, id_base):
+        on_dev, q = self._as_f32(q)
+        qd = q if on_dev else torch.from_numpy(q).cuda(self.device)
+        idx, dist = self.search_excluding(qd, k, torch.as_tensor(qgroups).to(qd.device), id_base)
+        return on_dev, qd, idx, dist
+
+    def search_aggregate_excluding(self, q, k: int, qgroups, beta: float = 0.02, id_base: int = 0, want_neighbours: bool = False):
+        """`search_excluding`, then `aggregate` (beyond k = 256 its big-k form) on the lists: the bits of `search_aggregate` on the view of the
+        allowed rows, given that the label rows of this index cover its rows."""
+        on_dev, qd, idx, dist = self._excluding_lists(q, k, qgroups, id_base)
+        out = k5(self, "aggregate", k)(qd, idx, dist, beta=beta, id_base=id_base)
+        if not on_dev:
+            out, idx, dist = out.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
+        return (out, idx, dist) if want_neighbours else out
+
+    def search_aggregate_grid_excluding(self, q, ks, betas, qgroups, id_base: int = 0, want_neighbours: bool = False):
+        """ONE excluding search at max(ks), then `aggregate_grid` (the big-k prefix route included): -> [nk * nb, nq, C] as
+        `search_aggregate_grid`, every configuration with the bits of the single `search_aggregate_excluding` call."""
+        plan = grid_plan(ks, betas)
+        on_dev, qd, idx, dist = self._excluding_lists(q, plan.ks[-1], qgroups, id_base)
+        out = self.aggregate_grid(qd, idx, dist, plan.ks, plan.betas, id_base=id_base)
+        if not on_dev:
+            out, idx, dist = out.cpu().numpy(), idx.cpu().numpy(), dist.cpu().numpy()
+        return (out, idx, dist) if want_neighbours else out
+
     @property
     def num_classes(self) -> int:
         return int(self._c) if hasattr(self, "_c") else self._query_c()
@@ -368,6 +462,7 @@ class HipFlatIndex:
         _lib.check(_lib.lib().hb_index_add_from(self._h, src._h, _ptr(ids), ids.numel(), int(on_dev)), ValueError)
         if hasattr(src, "_c") and ids.numel() and int(_lib.lib().hb_index_nlabels(src._h)) > 0:
             self._c = src._c           # label rows came along: the destination's class count is the source's (an emptied one adopted it)
+        self._hand_groups(src, ids, appended=True)
 
     def select_rows(self, ids) -> "HipFlatIndex":
         """A NEW index holding rows `ids` of this one (hb_index_select_rows): 1 x its rows of memory, label rows included; its fp16 state,
@@ -380,6 +475,7 @@ class HipFlatIndex:
         _lib.check(_lib.lib().hb_index_select_rows(self._h, _ptr(ids), ids.numel(), int(on_dev), ctypes.byref(view._h)), ValueError)
         if hasattr(self, "_c"):
             view._c = self._c
+        view._hand_groups(self, ids, appended=False)
         return view
 
     def copy_norms(self) -> torch.Tensor:
@@ -1015,6 +1111,13 @@ class HipMultiIndex:
     def set_label_table(self, labels, norms, id_base: int = 0):
         raise RuntimeError("HipMultiIndex keeps its own label table on the home device")
 
+    def _no_exclusion(self, *args, **kwargs):
+        """Excluding searches (HipFlatIndex.search_excluding and its fused forms) are NOT supported on a sharded or replicated bank: the
+        row-group table and the rungs belong to one index on one GPU.  Always raises ValueError."""
+        raise ValueError("HipMultiIndex: excluding searches are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")
+
+    set_row_groups = search_excluding = search_aggregate_excluding = search_aggregate_grid_excluding = last_exclusion = _no_exclusion
+
     def select_rows(self, ids):
         raise ValueError("HipMultiIndex.select_rows: views are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")
 
@@ -1121,6 +1224,20 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
             return idx.cpu().numpy(), dist.cpu().numpy()
         indices, distances = self.index.search(q_np, k, self.id_base)
         return indices, distances                                                  # (I, D) order: search_faiss.py:89-90
+
+    def find_nearest_neighbors_excluding(self, q, qgroups, k=None):
+        """`find_nearest_neighbors` over the rows whose group (index.set_row_groups) differs from qgroups[i]; one GPU, no torch.distributed
+        sharding (ValueError otherwise)."""
+        if k is None:
+            k = self.n_neighbors
+        check_k(k)
+        if self.multi is not None or (self.idx_shard and self.world > 1):
+            raise ValueError("find_nearest_neighbors_excluding: excluding searches are single-index (one GPU, no sharding)")
+        if isinstance(q, torch.Tensor) and q.is_cuda:
+            self.index.use_current_stream()
+            return self.index.search_excluding(q, k, qgroups, self.id_base)
+        q_np = q.cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q)
+        return self.index.search_excluding(q_np, k, qgroups, self.id_base)
 
     def _search_local(self, q: torch.Tensor, k: int, id_base_unused: int = 0, scores: bool = False):
         """All local GPUs on q (a CUDA tensor) -> (idx, dist | ordering scores) on the first GPU."""
