@@ -106,6 +106,8 @@ int hb_index_gather_labels(hb_index_t* ix, const int64_t* ids, int64_t n, int64_
  * configurations from one neighbour list per query -- are declared in hbird_hip_grid.h, which this header includes at its end. */
 /* Searches that exclude one group of bank rows per query (leave-one-image-out evaluation) -- hb_index_set_row_groups, hb_index_search_excluding,
  * hb_exclude_filter, hb_index_last_exclusion, hb_exclude_plan_replay -- are declared in hbird_hip_exclude.h, which this header includes at its end. */
+/* The read-out of the fp16 screen's last candidate pass -- hb_index_last_screen: lists, pass scores and first certificates, for tests of the
+ * candidate kernel -- is declared in hbird_hip_screen.h, which this header includes at its end. */
 /* Sub-bank views -- hb_index_add_from, hb_index_select_rows: an index out of selected rows of another one, gathered on the device -- are
  * declared in hbird_hip_select.h, which this header includes at its end. */
 /* Multi-GPU aggregation tables: borrow device arrays labels[n, c] / norms[n] that cover the GLOBAL id range
@@ -441,6 +443,7 @@ int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, i
 #include "hbird_hip_select.h"
 #include "hbird_hip_grid.h"
 #include "hbird_hip_exclude.h"
+#include "hbird_hip_screen.h"
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,29 @@ extern "C" int hb_index_fp16_centre_info(const hb_index_t* ix, double out[8]) {
     out[6] = ix->fp16_centre; out[7] = ix->last_centred;
     return 0;
 }
+// What the level-0 candidate pass of the last search left behind (include/hbird_hip_screen.h): the merged lists and pass scores in `cand`,
+// the first certificates at the start of `fb`.  Host bookkeeping and copies only.
+extern "C" int hb_index_last_screen(hb_index_t* ix, int64_t* cand_rows, float* pass_scores, unsigned char* certified, int64_t capacity_queries, int64_t info[4]) {
+    if (!ix) return hb_fail("hb_index_last_screen: NULL index handle");
+    if (!info) return hb_fail("hb_index_last_screen: info is NULL");
+    info[0] = info[1] = info[2] = info[3] = 0;
+    const hb_index::screen_record& r = ix->screen;
+    if (r.state == HB_SCREEN_OVERWRITTEN)
+        return hb_fail("hb_index_last_screen: the second fp16 pass of the last search has overwritten the first pass's candidates (hb_index_set_fp16_escalation(ix, 1) keeps them)");
+    if (r.state != HB_SCREEN_VALID || !ix->cand || !ix->fb)
+        return hb_fail("hb_index_last_screen: the last search did not take the fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
+    info[0] = r.nq; info[1] = r.kc; info[2] = r.centred; info[3] = r.klw;
+    HB_HIP(hipSetDevice(ix->device));
+    HB_HIP(hipStreamSynchronize(ix->stream));
+    if (!cand_rows && !pass_scores && !certified) return 0;
+    if (capacity_queries < r.nq)
+        return hb_fail("hb_index_last_screen: room for " + std::to_string(capacity_queries) + " queries, the last search had " + std::to_string(r.nq));
+    const size_t n = (size_t)r.nq * r.kc;
+    if (cand_rows) HB_HIP(hipMemcpy(cand_rows, ix->cand, n * 8, hipMemcpyDeviceToHost));
+    if (pass_scores) HB_HIP(hipMemcpy(pass_scores, ix->cand + n * 8, n * 4, hipMemcpyDeviceToHost));
+    if (certified) HB_HIP(hipMemcpy(certified, ix->fb, (size_t)r.nq, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" int hb_last_search_path(const hb_index_t* ix, int* path, int* reason) {
     if (!ix || !path || !reason) return hb_fail("hb_last_search_path: NULL pointer");
     *path = ix->last_path; *reason = ix->last_reason;
@@ -364,6 +387,7 @@ extern "C" int hb_index_reserve(hb_index_t* ix, int64_t n_rows) {
     HB_HIP(hipStreamSynchronize(s));
     if (ix->tiles) { HB_HIP(hipFree(ix->tiles)); HB_HIP(hipFree(ix->binit)); HB_HIP(hipFree(ix->bnorm)); }
     ix->tiles = tiles; ix->binit = binit; ix->bnorm = bnorm; ix->cap_rows = cap;
+    ix->screen.state = HB_SCREEN_NONE;
     return 0;
 }
 
@@ -381,6 +405,7 @@ extern "C" int hb_index_reset(hb_index_t* ix) {
     ix->ntotal = 0; ix->nlabels = 0; ix->lab_checked = 0; ix->f16_rows = 0; ix->f16_overflow = 0; ix->rows32_rows = 0;
     ix->row_groups_n = 0; ix->n_groups = 0; ix->gmax = 0;      // the row-group table goes with the rows
     ix->centre.rows = 0;      // (f16_rows = 0: a centred copy derives its mean anew from the rows of the next search)
+    ix->screen.state = HB_SCREEN_NONE;
     if (ix->lab_flag) HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, s));
     if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s));
     return 0;
@@ -420,7 +445,7 @@ extern "C" int hb_index_add(hb_index_t* ix, const float* x, int64_t n, int x_on_
                                     normalize, 1, ix->stream)) return -1;
     }
     if (hb_launch_bnorm_max(ix->bnorm + ix->ntotal, n, ix->bmax, ix->stream)) return -1;
-    ix->ntotal += n;
+    ix->ntotal += n; ix->screen.state = HB_SCREEN_NONE;
     return 0;
 }
 

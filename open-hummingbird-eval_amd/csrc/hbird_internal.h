@@ -18,6 +18,11 @@
 
 #define HB_ID_NONE 0xFFFFFFFFu
 
+// hb_index::screen.state
+#define HB_SCREEN_NONE 0          // no level-0 fp16 candidate pass since the bank last changed
+#define HB_SCREEN_VALID 1
+#define HB_SCREEN_OVERWRITTEN 2   // a second fp16 pass (esc == 1) has reused `cand`
+
 // Optional ROCTx range around a host-side phase (shows up under `rocprofv3 --marker-trace`).  The marker library
 // (librocprofiler-sdk-roctx.so, else libroctx64.so) is looked up at run time; without it the ranges are no-ops.
 struct hb_range {
@@ -97,6 +102,10 @@ struct hb_index {
     int64_t last_fp16_fallbacks = 0;                     // queries of the last use_fp16 search that the fp32 kernel had to answer ...
     int64_t last_fp16_escalated = 0;                     // ... and queries whose first certificate failed (second fp16 pass, k' = 256, seeded floors)
     int fp16_escalation = 0;                             // 0 = on (automatic), 1 = off: uncertified queries go straight to the fp32 kernel (round 5)
+    // what the level-0 candidate pass of the last search left in `cand` (lists, pass scores) and at the start of `fb` (first certificates), for
+    // hb_index_last_screen: host bookkeeping only.  Valid from the end of knn_search_f16's level-0 tail until the next level-0 search, a second
+    // pass that reuses `cand`, or a change of the bank (reset, add, capacity).
+    struct screen_record { int state = 0; int64_t nq = 0; int kc = 0, klw = 0, centred = 0; } screen;   // state: HB_SCREEN_*
     hb_f16_adapt f16_adapt;                              // adaptive use of use_fp16 in mode 2 (hbird_calibrate.h): moving averages of the failing shares
     char* bigk = nullptr; size_t bigk_bytes = 0;         // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
     hb_schedule sched_esc; char* sched_esc_dev = nullptr; size_t sched_esc_bytes = 0;   // the nested searches' work list (the caller's stays cached)

@@ -1024,6 +1024,7 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     nested.esc = again16 ? 1 : 2; nested.seed = d_seed;
     nested.fp16 = again16 ? 1 : 0; nested.timed = false; nested.q_aux = d_aux; nested.score_out = c.score_out;
     if (!again16) ix->last_fp16_fallbacks = nf;
+    if (again16) ix->screen.state = HB_SCREEN_OVERWRITTEN;      // (the second pass merges into ix->cand)
     if (!rc) rc = knn_search(ix, nested, d_q, nf, k, id_base, d_fi, d_fd);
     if (esc == 0) { ix->last_fp16_escalated = nf; hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks); }
     if (rc) return -1;
@@ -1085,6 +1086,7 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     std::vector<int64_t> bad;
     for (int64_t i = 0; i < nq; ++i) if (!hc[i]) bad.push_back(i);
     const int64_t nf = (int64_t)bad.size();
+    if (esc == 0) { ix->screen.nq = nq; ix->screen.kc = kc; ix->screen.klw = klw; ix->screen.centred = centred ? 1 : 0; ix->screen.state = HB_SCREEN_VALID; }      // (cand and the certificates are complete: the stream is idle)
     if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
     if (esc == 0 && nf == 0) hb_f16_observe(ix->f16_adapt, path.how16, nq, 0, 0);
     if (nf > 0 && knn_research_failures(ix, c, path, p, wl, ws, bad, q_dev, nq, k, id_base, out_idx, out_dist, s)) return -1;
@@ -1131,6 +1133,7 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     if (k > 256) return hb_launch_knn_bigk(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
     hipStream_t s = ix->stream;
     const int esc = c.esc;
+    if (esc == 0) ix->screen.state = HB_SCREEN_NONE;      // (hb_index_last_screen: whatever an earlier search left is about to go)
     knn_path path;
     if (knn_choose_path(ix, c, nq, k, &path)) return -1;
     if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_screen_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;

@@ -166,7 +166,7 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
     }
     // max bank-row norm over the new rows, as hb_index_add: the fp16 screen's certificate is bounded by it
     if (hb_launch_bnorm_max(dst->bnorm + row0, n, dst->bmax, s)) return -1;
-    dst->ntotal += n;
+    dst->ntotal += n; dst->screen.state = HB_SCREEN_NONE;
     if (labs) {
         // counts that were valid in the source stay valid: no conversion happened, so there is nothing new to check
         if (dst->lab_checked == dst->nlabels) dst->lab_checked = dst->nlabels + n;

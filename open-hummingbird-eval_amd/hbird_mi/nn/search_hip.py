@@ -597,6 +597,19 @@ class HipFlatIndex:
         """use_fp16: uncertified queries get a second fp16 pass (k' = 256, seeded floors) before the fp32 kernel (default), or go straight to it."""
         _lib.check(_lib.lib().hb_index_set_fp16_escalation(self._h, 0 if on else 1))
 
+    def last_screen(self) -> dict:
+        """What the level-0 fp16 candidate pass of the last search left (hb_index_last_screen, include/hbird_hip_screen.h), as numpy arrays:
+        rows int64 [nq, kc] (bank rows without id_base, -1: none), scores float32 [nq, kc] (the kernel's own pass scores; centred: without
+        c_q), certified uint8 [nq] (the first certificates), and nq, kc, klw, centred.  Raises when the last search did not take the fp16
+        path, when its second pass has overwritten the lists (set_fp16_escalation(False) keeps them), or after reset / add."""
+        lib = _lib.lib()
+        info = (ctypes.c_int64 * 4)()
+        _lib.check(lib.hb_index_last_screen(self._h, None, None, None, 0, info))
+        nq, kc = int(info[0]), int(info[1])
+        rows, scores, cert = np.empty((nq, kc), dtype=np.int64), np.empty((nq, kc), dtype=np.float32), np.empty(nq, dtype=np.uint8)
+        _lib.check(lib.hb_index_last_screen(self._h, _ptr(rows), _ptr(scores), _ptr(cert), nq, info))
+        return {"rows": rows, "scores": scores, "certified": cert, "nq": nq, "kc": kc, "centred": bool(info[2]), "klw": int(info[3])}
+
     def set_variant(self, variant: int):
         _lib.check(_lib.lib().hb_index_set_variant(self._h, int(variant)))
 
