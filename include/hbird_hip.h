@@ -370,6 +370,10 @@ int hb_index_kernel_clock(hb_index_t* ix, double out[4]);
  * launch with minus without clusters in ms.  In calibrated mode the shares (hb_index_xcd_weights) belong to the PHYSICAL XCDs 0-7 as
  * HW_REG_XCC_ID numbers them. */
 int hb_index_xcd_stats(const hb_index_t* ix, int fp16_kernel, double out[12]);
+/* Device allocations the library's indexes (views included) hold at this moment, process-wide: their number and their bytes as allocated.  Both
+ * return to their earlier values once every index created since has been freed: a leak check exact to the byte (tests).  The per-device words
+ * and per-stream scratch the stateless entries keep for the life of the process are not counted. */
+int hb_debug_live_allocations(int64_t* count, int64_t* bytes);
 /* The calibration's decisions without a GPU (tests; like hb_schedule_plan* for the planner): a state as an index keeps per kernel family, fed with
  * the stamp sets of imagined launches.  hb_calibration_new(fp16_kernel) -> handle; hb_calibration_state: the GROUP shares the next launch would
  * run with (group g = blocks equal to g mod 8) and out[0..11] = rounds, locked, reverts, samples, rejected, moves of the group -> XCD map, cluster

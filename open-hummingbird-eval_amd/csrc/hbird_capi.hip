@@ -2,6 +2,7 @@
 #include "../../include/hbird_hip.h"
 #include "hbird_internal.h"
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +14,29 @@
 static thread_local std::string g_err;
 void hb_set_error(const std::string& msg) { g_err = msg; }
 int hb_fail(const std::string& msg) { g_err = msg; return -1; }
+
+// ---- the device side of hbird_devbuf.h: the only hipMalloc / hipFree of an index, and the counts of what is live -------------------------
+static std::atomic<int64_t> g_live_allocs{0}, g_live_bytes{0};
+const char* hb_dev_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return hipGetErrorString(e); }
+    ++g_live_allocs; g_live_bytes += (int64_t)bytes;
+    return nullptr;
+}
+void hb_dev_free(void* p, size_t bytes) {
+    (void)hipFree(p);
+    --g_live_allocs; g_live_bytes -= (int64_t)bytes;
+}
+const char* hb_dev_copy_sync(void* dst, const void* src, size_t bytes, void* stream) {
+    hipError_t e = bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+extern "C" int hb_debug_live_allocations(int64_t* count, int64_t* bytes) {
+    if (!count || !bytes) return hb_fail("hb_debug_live_allocations: NULL pointer");
+    *count = g_live_allocs.load(); *bytes = g_live_bytes.load();
+    return 0;
+}
 
 namespace {
 struct roctx_api {
@@ -73,7 +97,7 @@ extern "C" int hb_index_create(int d, int metric, int device, hb_index_t** out) 
     hipDeviceProp_t prop;
     HB_HIP(hipGetDeviceProperties(&prop, device));
     ix->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HB_HIP(hipMalloc((void**)&ix->bmax, 4));
+    if (ix->bmax.ensure(4, HB_GROW_EXACT)) return -1;
     HB_HIP(hipMemset(ix->bmax, 0, 4));
     HB_HIP(hipEventCreate(&ix->ev0));
     HB_HIP(hipEventCreate(&ix->ev1));
@@ -87,14 +111,10 @@ extern "C" int hb_index_free(hb_index_t* ix) {
     if (!ix) return 0;
     (void)hipSetDevice(ix->device);
     (void)hipStreamSynchronize(ix->stream);
-    void* ptrs[] = {ix->tiles, ix->binit, ix->bnorm, ix->labels, ix->q_tiles, ix->q_aux, ix->state, ix->sched_dev, ix->tmp,
-                    ix->tiles16, ix->stamp_keep, ix->q16, ix->cand, ix->bmax, ix->fb, ix->fb1, ix->sched_esc_dev, ix->bigk, ix->mtmp, ix->f16_flag, ix->labels16, ix->lab_flag, ix->rows32, ix->row_groups, ix->excl, ix->excl1};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    hb_centre_drop(ix);
     for (auto& c : ix->xcal) { if (c.stamp_host) (void)hipHostFree(c.stamp_host); if (c.stamp_ev) (void)hipEventDestroy(c.stamp_ev); }
     if (ix->ev0) (void)hipEventDestroy(ix->ev0);
     if (ix->ev1) (void)hipEventDestroy(ix->ev1);
-    delete ix;
+    delete ix;      // (every device buffer is a member: hbird_devbuf.h)
     return 0;
 }
 
@@ -141,8 +161,8 @@ extern "C" int hb_index_set_fp16_centre(hb_index_t* ix, int on) {
     if (on == ix->fp16_centre) return 0;
     HB_HIP(hipSetDevice(ix->device));
     HB_HIP(hipStreamSynchronize(ix->stream));
-    if (ix->tiles16) { HB_HIP(hipFree(ix->tiles16)); ix->tiles16 = nullptr; }
-    ix->f16_rows = 0; ix->f16_cap_rows = 0; ix->f16_overflow = 0; ix->f16_declined_cap = -1;
+    ix->drop_tiles16();
+    ix->f16_overflow = 0; ix->f16_declined_cap = -1;
     if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, ix->stream));      // (the flag speaks of the values of the copy's form)
     hb_centre_drop(ix);
     ix->fp16_centre = on; ix->last_centred = 0;
@@ -335,8 +355,7 @@ extern "C" int hb_index_set_rerank_copy(hb_index_t* ix, int mode) {
     if (mode == 2 && ix->rows32) {
         (void)hipSetDevice(ix->device);
         HB_HIP(hipStreamSynchronize(ix->stream));
-        HB_HIP(hipFree(ix->rows32));
-        ix->rows32 = nullptr; ix->rows32_cap_rows = 0; ix->rows32_rows = 0;
+        ix->drop_rows32();
     }
     return 0;
 }
@@ -353,26 +372,16 @@ extern "C" int hb_index_schedule_info(const hb_index_t* ix, int64_t out[8]) {
     return 0;
 }
 
-static int grow(void** p, size_t* have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) HB_HIP(hipFree(*p));
-    *p = nullptr; *have = 0;
-    HB_HIP(hipMalloc(p, need));
-    *have = need;
-    return 0;
-}
-
 extern "C" int hb_index_reserve(hb_index_t* ix, int64_t n_rows) {
     if (!ix) return hb_fail("hb_index_reserve: NULL index handle");
     HB_HIP(hipSetDevice(ix->device));
     int64_t cap = (n_rows + HB_BT - 1) / HB_BT * HB_BT;
     if (cap <= ix->cap_rows) return 0;
     hipStream_t s = ix->stream;
-    float *tiles = nullptr, *binit = nullptr, *bnorm = nullptr;
+    // the new arrays are locals until they are complete: a failing allocation or copy frees them and leaves the index as it was
+    hb_dev<float> tiles, binit, bnorm;
     const size_t tb = (size_t)cap * ix->dp * 4;
-    HB_HIP(hipMalloc((void**)&tiles, tb));
-    HB_HIP(hipMalloc((void**)&binit, (size_t)cap * 4));
-    HB_HIP(hipMalloc((void**)&bnorm, (size_t)cap * 4));
+    if (tiles.ensure(tb, HB_GROW_EXACT) || binit.ensure((size_t)cap * 4, HB_GROW_EXACT) || bnorm.ensure((size_t)cap * 4, HB_GROW_EXACT)) return -1;
     const size_t old_tb = (size_t)ix->cap_rows * ix->dp * 4;
     if (ix->cap_rows > 0) {
         // fragment tiles are row-tile major, so the old bank is a prefix of the new one
@@ -380,13 +389,12 @@ extern "C" int hb_index_reserve(hb_index_t* ix, int64_t n_rows) {
         HB_HIP(hipMemcpyAsync(binit, ix->binit, (size_t)ix->cap_rows * 4, hipMemcpyDeviceToDevice, s));
         HB_HIP(hipMemcpyAsync(bnorm, ix->bnorm, (size_t)ix->cap_rows * 4, hipMemcpyDeviceToDevice, s));
     }
-    HB_HIP(hipMemsetAsync((char*)tiles + old_tb, 0, tb - old_tb, s));
+    HB_HIP(hipMemsetAsync(tiles.as<char>(old_tb), 0, tb - old_tb, s));
     // padding rows start from -inf so they can never enter a top-k list
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)(binit + ix->cap_rows), 0xFF800000u, (size_t)(cap - ix->cap_rows), s));
     HB_HIP(hipMemsetAsync(bnorm + ix->cap_rows, 0, (size_t)(cap - ix->cap_rows) * 4, s));
     HB_HIP(hipStreamSynchronize(s));
-    if (ix->tiles) { HB_HIP(hipFree(ix->tiles)); HB_HIP(hipFree(ix->binit)); HB_HIP(hipFree(ix->bnorm)); }
-    ix->tiles = tiles; ix->binit = binit; ix->bnorm = bnorm; ix->cap_rows = cap;
+    ix->tiles = std::move(tiles); ix->binit = std::move(binit); ix->bnorm = std::move(bnorm); ix->cap_rows = cap;
     ix->screen.state = HB_SCREEN_NONE;
     return 0;
 }
@@ -431,11 +439,11 @@ extern "C" int hb_index_add(hb_index_t* ix, const float* x, int64_t n, int x_on_
     if (!x_on_device) {
         // host rows are staged in chunks of <= 256 MiB
         const int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)ix->d * 4));
-        if (grow((void**)&ix->tmp, &ix->tmp_bytes, (size_t)std::min(chunk, n) * ix->d * 4)) return -1;
+        if (ix->tmp.ensure((size_t)std::min(chunk, n) * ix->d * 4, HB_GROW_EXACT)) return -1;
         for (int64_t r = 0; r < n; r += chunk) {
             const int64_t m = std::min(chunk, n - r);
             if (stage_in(ix, x + r * (int64_t)ix->d, (size_t)m * ix->d * 4, 0)) return -1;
-            if (hb_launch_rows_to_tiles((const float*)ix->tmp, m, ix->d, ix->dp, ix->ntotal + r, ix->tiles, ix->binit, ix->bnorm,
+            if (hb_launch_rows_to_tiles(ix->tmp.as<const float>(), m, ix->d, ix->dp, ix->ntotal + r, ix->tiles, ix->binit, ix->bnorm,
                                         ix->metric, normalize, 1, ix->stream)) return -1;
             HB_HIP(hipStreamSynchronize(ix->stream));
         }
@@ -458,9 +466,7 @@ extern "C" int hb_index_set_label_denominator(hb_index_t* ix, int P) {
     if ((P == 0) != (ix->label_P == 0) && (ix->labels || ix->labels16)) {
         HB_HIP(hipSetDevice(ix->device));
         HB_HIP(hipStreamSynchronize(ix->stream));
-        if (ix->labels) HB_HIP(hipFree(ix->labels));
-        if (ix->labels16) HB_HIP(hipFree(ix->labels16));
-        ix->labels = nullptr; ix->labels16 = nullptr; ix->lab_cap = 0;
+        ix->drop_labels();
     }
     ix->label_P = P;
     return 0;
@@ -470,17 +476,16 @@ extern "C" int hb_index_labels_to_fp32(hb_index_t* ix) {
     if (ix->label_P == 0) return 0;
     HB_HIP(hipSetDevice(ix->device));
     if (hb_labels_checked(ix)) return -1;
-    float* nl = nullptr;
+    hb_dev<float> nl;
     const int64_t cap = std::max<int64_t>(ix->nlabels, ix->lab_cap);
     if (ix->nlabels > 0) {
-        HB_HIP(hipMalloc((void**)&nl, (size_t)cap * ix->c * 4));
+        if (nl.ensure((size_t)cap * ix->c * 4, HB_GROW_EXACT)) return -1;
         // one pass: count j of the value j / P -> (float)j / (float)P, the fp32 value K2 produced (hbird_eval.py:319-320)
-        if (hb_launch_gather_label_counts(ix->labels16, ix->nlabels, ix->c, ix->lab_stride(), ix->label_P, nullptr, ix->nlabels, nl, ix->stream)) { (void)hipFree(nl); return -1; }
+        if (hb_launch_gather_label_counts(ix->labels16, ix->nlabels, ix->c, ix->lab_stride(), ix->label_P, nullptr, ix->nlabels, nl, ix->stream)) return -1;
     }
     HB_HIP(hipStreamSynchronize(ix->stream));
-    if (ix->labels16) HB_HIP(hipFree(ix->labels16));
-    if (ix->labels) HB_HIP(hipFree(ix->labels));
-    ix->labels16 = nullptr; ix->labels = nl; ix->label_P = 0; ix->lab_cap = nl ? cap : 0; ix->lab_checked = 0;
+    ix->drop_labels();
+    ix->lab_cap = nl ? cap : 0; ix->labels = std::move(nl); ix->label_P = 0; ix->lab_checked = 0;
     return 0;
 }
 extern "C" int hb_index_label_denominator(const hb_index_t* ix, int* P) {
@@ -507,22 +512,15 @@ int hb_labels_checked(hb_index* ix) {
 int hb_labels_ensure(hb_index* ix, int c, int64_t n) {
     if (ix->c != c && ix->lab_cap > 0) {
         HB_HIP(hipStreamSynchronize(ix->stream));
-        if (ix->labels) HB_HIP(hipFree(ix->labels));
-        if (ix->labels16) HB_HIP(hipFree(ix->labels16));
-        ix->labels = nullptr; ix->labels16 = nullptr; ix->lab_cap = 0;
+        ix->drop_labels();
     }
     ix->c = c;
     const size_t esz = ix->label_P ? 2 : 4;      // uint16 counts or fp32 values
     const size_t ls = (size_t)ix->lab_stride();  // elements per stored row (counts: padded to 16 bytes)
     if (ix->nlabels + n > ix->lab_cap) {
         int64_t cap = std::max<int64_t>(ix->nlabels + n, std::max<int64_t>(ix->cap_rows, ix->lab_cap + ix->lab_cap / 2));
-        char* nl = nullptr;
-        char* old = ix->label_P ? (char*)ix->labels16 : (char*)ix->labels;
-        HB_HIP(hipMalloc((void**)&nl, (size_t)cap * ls * esz));
-        if (ix->nlabels > 0) HB_HIP(hipMemcpyAsync(nl, old, (size_t)ix->nlabels * ls * esz, hipMemcpyDeviceToDevice, ix->stream));
-        HB_HIP(hipStreamSynchronize(ix->stream));
-        if (old) HB_HIP(hipFree(old));
-        if (ix->label_P) ix->labels16 = (uint16_t*)nl; else ix->labels = (float*)nl;
+        hb_devbuf& table = ix->label_P ? static_cast<hb_devbuf&>(ix->labels16) : ix->labels;
+        if (table.ensure_keep((size_t)cap * ls * esz, HB_GROW_EXACT, (size_t)ix->nlabels * ls * esz, ix->stream)) return -1;
         ix->lab_cap = cap;
     }
     return 0;
@@ -538,12 +536,12 @@ extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t 
     const size_t ls = (size_t)ix->lab_stride();  // elements per stored row (counts: padded to 16 bytes)
     if (ix->label_P) {
         // values j / P (what K2 produces, hbird_eval.py:319-320) stored as the uint16 count j: half the table, the same fp32 value back
-        if (!ix->lab_flag) { HB_HIP(hipMalloc((void**)&ix->lab_flag, 4)); HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, ix->stream)); }
+        if (!ix->lab_flag) { if (ix->lab_flag.ensure(4, HB_GROW_EXACT)) return -1; HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, ix->stream)); }
         const float* src = labels;
         if (!on_device) {
-            if (grow((void**)&ix->tmp, &ix->tmp_bytes, (size_t)n * c * 4)) return -1;
+            if (ix->tmp.ensure((size_t)n * c * 4, HB_GROW_EXACT)) return -1;
             if (stage_in(ix, labels, (size_t)n * c * 4, 0)) return -1;
-            src = (const float*)ix->tmp;
+            src = ix->tmp.as<const float>();
         }
         if (hb_launch_labels_to_counts(src, n, c, (int)ls, ix->label_P, ix->labels16 + ix->nlabels * (int64_t)ls, ix->lab_flag, ix->stream)) return -1;
         if (!on_device) HB_HIP(hipStreamSynchronize(ix->stream));
@@ -556,8 +554,6 @@ extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t 
     ix->nlabels += n;
     return 0;
 }
-
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta, float* out_lab,
                        int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate, bool bigk = false, const hb_grid_spec* grid = nullptr) {
@@ -572,8 +568,8 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     hb_range range(aggregate ? "hbird:search_aggregate" : "hbird:search");
     HB_HIP(hipSetDevice(ix->device));
     const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
-    if (grow((void**)&ix->q_tiles, &ix->q_tiles_bytes, (size_t)nqp * ix->dp * 4)) return -1;
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (ix->q_tiles.ensure((size_t)nqp * ix->dp * 4, HB_GROW_EXACT)) return -1;
+    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
     // staging area in ix->tmp: [queries (host path)] [idx] [dist] [label_hat (host path)]
     const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4);
     const size_t b_idx = al256((size_t)nq * k * 8), b_dist = al256((size_t)nq * k * 4);
@@ -581,7 +577,7 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     const size_t b_lab = (aggregate && !io_on_device) ? al256(lab_bytes) : 0;
     const bool t_idx = !io_on_device || !out_idx, t_dist = !io_on_device || !out_dist;
     const size_t need = b_q + (t_idx ? b_idx : 0) + (t_dist ? b_dist : 0) + b_lab;
-    if (need && grow((void**)&ix->tmp, &ix->tmp_bytes, need)) return -1;
+    if (need && ix->tmp.ensure(need, HB_GROW_EXACT)) return -1;
     char* cur = ix->tmp;
     const float* qd = q;
     if (!io_on_device) {
@@ -642,7 +638,7 @@ static int aggregate_on_lists(hb_index* ix, const char* range_name, const float*
         HB_HIP(hipMemsetAsync(zero_if_empty, 0, (size_t)nq * ix->c * 4, ix->stream));
         return 0;
     }
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
     if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
     return launch(ix->q_aux + nq);
 }
@@ -799,11 +795,11 @@ static int gather_impl(hb_index* ix, const int64_t* ids, int64_t n, int64_t id_b
     const int64_t* d_ids = ids;
     float* d_out = out;
     if (!io_on_device) {
-        const size_t b_ids = ((size_t)n * 8 + 255) / 256 * 256;
-        if (grow((void**)&ix->tmp, &ix->tmp_bytes, b_ids + (size_t)n * width * 4)) return -1;
+        const size_t b_ids = al256((size_t)n * 8);
+        if (ix->tmp.ensure(b_ids + (size_t)n * width * 4, HB_GROW_EXACT)) return -1;
         if (stage_in(ix, ids, (size_t)n * 8, 0)) return -1;
-        d_ids = (const int64_t*)ix->tmp;
-        d_out = (float*)(ix->tmp + b_ids);
+        d_ids = ix->tmp.as<const int64_t>();
+        d_out = ix->tmp.as<float>(b_ids);
     }
     if (labels) {
         // shift global ids to local rows inside the kernel via src offset: ids are global, rows local
@@ -886,7 +882,7 @@ extern "C" int hb_index_distances_from_scores(hb_index_t* ix, const float* q, in
     if (k < 1) return hb_fail("hb_index_distances_from_scores: k must be positive");
     if (!q || !dist_inout) return hb_fail("hb_index_distances_from_scores: NULL pointer");
     HB_HIP(hipSetDevice(ix->device));
-    if (grow((void**)&ix->q_aux, &ix->q_aux_bytes, (size_t)nq * 2 * 4)) return -1;
+    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
     if (hb_launch_query_aux(q, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
     return hb_launch_scores_to_l2(ix->q_aux, nq, k, dist_inout, ix->stream);
 }

@@ -123,16 +123,6 @@ int hb_launch_exclude_filter(const int64_t* idx, const float* dist, int64_t nq, 
     return 0;
 }
 
-static int excl_grow(char** p, size_t* have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) HB_HIP(hipFree(*p));
-    *p = nullptr; *have = 0;
-    HB_HIP(hipMalloc((void**)p, need));
-    *have = need;
-    return 0;
-}
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 extern "C" int hb_exclude_filter(const int64_t* idx, const float* dist, int64_t nq, int k_list, int64_t id_base, const int32_t* groups,
                                  int64_t n_rows, const int32_t* qgroups, int k, float pad, int64_t* out_idx, float* out_dist,
                                  int32_t* out_complete, void* hip_stream) {
@@ -154,24 +144,22 @@ extern "C" int hb_index_set_row_groups(hb_index_t* ix, const int32_t* groups, in
     HB_HIP(hipSetDevice(ix->device));
     hipStream_t s = ix->stream;
     // the new table is built beside the old one: a failing call (a value outside the range) leaves the index as it was
-    int32_t* tab = nullptr;
-    HB_HIP(hipMalloc((void**)&tab, (size_t)n * 4));
-    auto fail = [&](const std::string& msg) { (void)hipFree(tab); return hb_fail(msg); };
+    hb_dev<int32_t> tab;
+    if (tab.ensure((size_t)n * 4, HB_GROW_EXACT)) return -1;
     const size_t cb = ((size_t)n_groups + 1) * 4;       // counts[n_groups], flag
-    if (excl_grow(&ix->excl, &ix->excl_bytes, al256(cb))) return fail(hb_last_error());
-    int32_t* counts = reinterpret_cast<int32_t*>(ix->excl);
+    if (ix->excl.ensure(al256(cb), HB_GROW_EXACT)) return -1;
+    int32_t* counts = ix->excl.as<int32_t>();
     hipError_t e = hipMemcpyAsync(tab, groups, (size_t)n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(counts, 0, cb, s);
-    if (e != hipSuccess) return fail(std::string("hb_index_set_row_groups: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hb_fail(std::string("hb_index_set_row_groups: ") + hipGetErrorString(e));
     exclude_group_sizes_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(tab, n, n_groups, counts, counts + n_groups);
     e = hipGetLastError();
     std::vector<int32_t> host((size_t)n_groups + 1);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), counts, cb, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(std::string("hb_index_set_row_groups: ") + hipGetErrorString(e));
-    if (host[n_groups]) return fail("hb_index_set_row_groups: a row's group lies outside [-1, " + std::to_string(n_groups) + ")");
-    if (ix->row_groups) HB_HIP(hipFree(ix->row_groups));
-    ix->row_groups = tab; ix->row_groups_cap = n; ix->row_groups_n = n; ix->n_groups = n_groups;
+    if (e != hipSuccess) return hb_fail(std::string("hb_index_set_row_groups: ") + hipGetErrorString(e));
+    if (host[n_groups]) return hb_fail("hb_index_set_row_groups: a row's group lies outside [-1, " + std::to_string(n_groups) + ")");
+    ix->row_groups = std::move(tab); ix->row_groups_cap = n; ix->row_groups_n = n; ix->n_groups = n_groups;
     ix->gmax = n_groups ? *std::max_element(host.begin(), host.begin() + n_groups) : 0;
     return 0;
 }
@@ -211,7 +199,7 @@ extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t
     const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4), b_qg = io_on_device ? 0 : al256((size_t)nq * 4);
     const size_t b_oi = io_on_device ? 0 : al256((size_t)nq * k * 8), b_od = io_on_device ? 0 : al256((size_t)nq * k * 4);
     const size_t b_li = al256((size_t)nq * kf0 * 8), b_ld = al256((size_t)nq * kf0 * 4);
-    if (excl_grow(&ix->excl, &ix->excl_bytes, b_flag + b_comp + b_q + b_qg + b_oi + b_od + b_li + b_ld)) return -1;
+    if (ix->excl.ensure(b_flag + b_comp + b_q + b_qg + b_oi + b_od + b_li + b_ld, HB_GROW_EXACT)) return -1;
     char* cur = ix->excl;
     int32_t* flags = reinterpret_cast<int32_t*>(cur); cur += b_flag;
     int32_t* complete = reinterpret_cast<int32_t*>(cur); cur += b_comp;
@@ -250,7 +238,7 @@ extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t
             const size_t c_rows = al256((size_t)n1 * 8), c_qg = al256((size_t)n1 * 4), c_q = al256((size_t)n1 * ix->d * 4);
             const size_t c_li = al256((size_t)n1 * kf1 * 8), c_ld = al256((size_t)n1 * kf1 * 4);
             const size_t c_fi = al256((size_t)n1 * k * 8), c_fd = al256((size_t)n1 * k * 4);
-            if (excl_grow(&ix->excl1, &ix->excl1_bytes, c_rows + c_qg + c_q + c_li + c_ld + c_fi + c_fd)) return -1;
+            if (ix->excl1.ensure(c_rows + c_qg + c_q + c_li + c_ld + c_fi + c_fd, HB_GROW_EXACT)) return -1;
             char* c = ix->excl1;
             int64_t* rows = reinterpret_cast<int64_t*>(c); c += c_rows;
             int32_t* qg1 = reinterpret_cast<int32_t*>(c); c += c_qg;

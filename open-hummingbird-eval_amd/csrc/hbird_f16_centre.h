@@ -3,15 +3,16 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "hbird_devbuf.h"
 
 struct hb_index;
 
 struct hb_centre_state {
-    float* mu = nullptr;            // [max(dp16, dp)] column mean of the rows present when the copy was made (0 on the padding dimensions)
-    float* g = nullptr;             // [cap_rows] mu.(b - mu), k-ascending fp32 chain
-    float* init16 = nullptr;        // [cap_rows] the candidate kernel's row init of the current search: fmaf(t, g, binit)
-    float* sc = nullptr;            // device scalars {cmax = max ||b - mu||, ||mu|| (rounded up), mu.mu, t of the last search}
-    char* qaux = nullptr; size_t qaux_bytes = 0;   // per search: [c_q nq][||q - t mu|| nq][partial sums of c_q]
+    hb_dev<float> mu;               // [max(dp16, dp)] column mean of the rows present when the copy was made (0 on the padding dimensions)
+    hb_dev<float> g;                // [cap_rows] mu.(b - mu), k-ascending fp32 chain
+    hb_dev<float> init16;           // [cap_rows] the candidate kernel's row init of the current search: fmaf(t, g, binit)
+    hb_dev<float> sc;               // device scalars {cmax = max ||b - mu||, ||mu|| (rounded up), mu.mu, t of the last search}
+    hb_dev<char> qaux;              // per search: [c_q nq][||q - t mu|| nq][partial sums of c_q]
     int64_t cap_rows = 0;           // capacity the row arrays were allocated for
     int64_t rows = 0;               // rows converted with mu
     int active = 0;                 // the fp16 copy holds centred rows (0: no copy yet, or a non-finite / all-zero mean: the plain copy)

@@ -240,9 +240,7 @@ __global__ __launch_bounds__(256) void centre_init16_kernel(const float* __restr
 // ---- host side ---------------------------------------------------------------------------------------------------------
 void hb_centre_drop(hb_index* ix) {
     hb_centre_state& c = ix->centre;
-    void* ptrs[] = {c.mu, c.g, c.init16, c.sc, c.qaux};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    c.mu = nullptr; c.g = nullptr; c.init16 = nullptr; c.sc = nullptr; c.qaux = nullptr; c.qaux_bytes = 0;
+    c.mu.drop(); c.g.drop(); c.init16.drop(); c.sc.drop(); c.qaux.drop();
     c.cap_rows = 0; c.active = 0; c.rows = 0;
 }
 
@@ -251,20 +249,17 @@ static int centre_derive_mean(hb_index* ix, hipStream_t s) {
     hb_centre_state& c = ix->centre;
     const int64_t nrt = (ix->ntotal + 31) / 32;
     const int64_t per = (nrt + HC_PARTS - 1) / HC_PARTS;
-    unsigned* valid = nullptr; double* part = nullptr; long long* part_rows = nullptr;
-    const size_t b_valid = ((size_t)nrt * 4 + 255) / 256 * 256, b_part = (size_t)HC_PARTS * ix->g8 * 8 * 8;
-    char* tmp = nullptr;
-    HB_HIP(hipMalloc((void**)&tmp, b_valid + b_part + HC_PARTS * 8));
-    valid = reinterpret_cast<unsigned*>(tmp); part = reinterpret_cast<double*>(tmp + b_valid); part_rows = reinterpret_cast<long long*>(tmp + b_valid + b_part);
+    const size_t b_valid = al256((size_t)nrt * 4), b_part = (size_t)HC_PARTS * ix->g8 * 8 * 8;
+    hb_devbuf tmp;
+    if (tmp.ensure(b_valid + b_part + HC_PARTS * 8, HB_GROW_EXACT)) return -1;
+    unsigned* valid = tmp.as<unsigned>(); double* part = tmp.as<double>(b_valid); long long* part_rows = tmp.as<long long>(b_valid + b_part);
     centre_row_valid_kernel<<<dim3((unsigned)((nrt + 3) / 4)), dim3(256), 0, s>>>(ix->tiles, ix->g8, ix->binit, nrt, valid);
     centre_colsum_kernel<<<dim3(HC_PARTS, (unsigned)ix->g8), dim3(256), 0, s>>>(ix->tiles, ix->g8, valid, nrt, per, part, part_rows);
     centre_mean_kernel<<<dim3(1), dim3(256), 0, s>>>(part, part_rows, ix->g8, std::max(ix->dp16, ix->g8 * 8), c.mu, c.sc);
-    hipError_t e = hipGetLastError();
+    HB_HIP(hipGetLastError());
     float h[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(h, c.sc, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    HB_HIP(e);
+    HB_HIP(hipMemcpyAsync(h, c.sc, 16, hipMemcpyDeviceToHost, s));
+    HB_HIP(hipStreamSynchronize(s));      // (the kernels are done with tmp)
     c.active = std::isfinite(h[1]) && h[2] > 0.0f ? 1 : 0;
     c.rows = 0;
     return 0;
@@ -276,11 +271,12 @@ int hb_centre_convert(hb_index* ix, hipStream_t s, int* centred_out) {
     hb_centre_state& c = ix->centre;
     *centred_out = 0;
     if (c.cap_rows != ix->cap_rows || !c.mu) {
+        // four locals until all are there: a failing allocation frees the earlier ones and leaves the index as it was
+        hb_dev<float> mu, g, init16, sc;
+        if (mu.ensure((size_t)std::max(ix->dp16, ix->g8 * 8) * 4, HB_GROW_EXACT) || g.ensure((size_t)ix->cap_rows * 4, HB_GROW_EXACT) ||
+            init16.ensure((size_t)ix->cap_rows * 4, HB_GROW_EXACT) || sc.ensure(16, HB_GROW_EXACT)) return -1;
         hb_centre_drop(ix);
-        HB_HIP(hipMalloc((void**)&c.mu, (size_t)std::max(ix->dp16, ix->g8 * 8) * 4));
-        HB_HIP(hipMalloc((void**)&c.g, (size_t)ix->cap_rows * 4));
-        HB_HIP(hipMalloc((void**)&c.init16, (size_t)ix->cap_rows * 4));
-        HB_HIP(hipMalloc((void**)&c.sc, 16));
+        c.mu = std::move(mu); c.g = std::move(g); c.init16 = std::move(init16); c.sc = std::move(sc);
         HB_HIP(hipMemsetAsync(c.g, 0, (size_t)ix->cap_rows * 4, s));
         HB_HIP(hipMemsetD32Async((hipDeviceptr_t)c.init16, 0xFF800000u, (size_t)ix->cap_rows, s));
         c.cap_rows = ix->cap_rows;
@@ -291,7 +287,7 @@ int hb_centre_convert(hb_index* ix, hipStream_t s, int* centred_out) {
     const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
     const int64_t threads = (need_rt - rt0) * 32;
     if (threads > 0) {
-        centre_bank_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(ix->tiles, ix->g8, c.mu, (_Float16*)ix->tiles16, ix->dp16 / 16, rt0,
+        centre_bank_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(ix->tiles, ix->g8, c.mu, ix->tiles16.as<_Float16>(), ix->dp16 / 16, rt0,
                                                                                          need_rt - rt0, ix->ntotal, c.g, c.sc, ix->f16_flag);
         HB_HIP(hipGetLastError());
     }
@@ -302,14 +298,9 @@ int hb_centre_convert(hb_index* ix, hipStream_t s, int* centred_out) {
 
 static int centre_qaux(hb_index* ix, int64_t nq, float** cq, float** qcn, double** part) {
     hb_centre_state& c = ix->centre;
-    const size_t b_f = ((size_t)nq * 4 + 255) / 256 * 256, need = 2 * b_f + (size_t)((nq + 63) / 64) * 8;
-    if (c.qaux_bytes < need) {
-        if (c.qaux) HB_HIP(hipFree(c.qaux));
-        c.qaux = nullptr; c.qaux_bytes = 0;
-        HB_HIP(hipMalloc((void**)&c.qaux, need + need / 4));
-        c.qaux_bytes = need + need / 4;
-    }
-    *cq = reinterpret_cast<float*>(c.qaux); *qcn = reinterpret_cast<float*>(c.qaux + b_f); *part = reinterpret_cast<double*>(c.qaux + 2 * b_f);
+    const size_t b_f = al256((size_t)nq * 4), need = 2 * b_f + (size_t)((nq + 63) / 64) * 8;
+    if (c.qaux.ensure(need, HB_GROW_QUARTER)) return -1;
+    *cq = c.qaux.as<float>(); *qcn = c.qaux.as<float>(b_f); *part = c.qaux.as<double>(2 * b_f);
     return 0;
 }
 

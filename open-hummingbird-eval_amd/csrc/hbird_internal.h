@@ -8,6 +8,7 @@
 #include "hbird_schedule.h"
 #include "hbird_calibrate.h"
 #include "hbird_f16_centre.h"
+#include "hbird_devbuf.h"
 
 // ---- tile geometry of the kNN kernel (see DESIGN.md "Data layout in HBM") -------------------
 #define HB_RT 32         // rows per fragment tile (MFMA 32x32x2)
@@ -36,13 +37,13 @@ struct hb_index {
     int d = 0, dp = 0, g8 = 0, metric = 0, device = 0;
     hipStream_t stream = nullptr;
     int64_t ntotal = 0, cap_rows = 0;      // cap_rows is a multiple of HB_BT
-    float* tiles = nullptr;                // fragment-tiled bank  [cap_rows/32][g8][256]
-    float* binit = nullptr;                // per-row accumulator init [cap_rows]
-    float* bnorm = nullptr;                // per-row L2 norm (fp32)  [cap_rows]
-    float* labels = nullptr;               // [lab_cap][c] fp32 (label_P == 0) ...
-    uint16_t* labels16 = nullptr;          // ... or [lab_cap][lab_stride()] uint16 counts j of values j / label_P (hb_index_set_label_denominator): rows padded to 8 counts = 16 B
+    hb_dev<float> tiles;                   // fragment-tiled bank  [cap_rows/32][g8][256]
+    hb_dev<float> binit;                   // per-row accumulator init [cap_rows]
+    hb_dev<float> bnorm;                   // per-row L2 norm (fp32)  [cap_rows]
+    hb_dev<float> labels;                  // [lab_cap][c] fp32 (label_P == 0) ...
+    hb_dev<uint16_t> labels16;             // ... or [lab_cap][lab_stride()] uint16 counts j of values j / label_P (hb_index_set_label_denominator): rows padded to 8 counts = 16 B
     int label_P = 0;
-    int* lab_flag = nullptr;               // sticky device flag: a label value was not a multiple of 1 / label_P
+    hb_dev<int> lab_flag;                  // sticky device flag: a label value was not a multiple of 1 / label_P
     int64_t lab_checked = 0;               // label rows whose conversion has been checked (one read-back after the table grew)
     int c = 0;
     int64_t nlabels = 0, lab_cap = 0;
@@ -52,11 +53,11 @@ struct hb_index {
     const float* ext_labels = nullptr; const float* ext_bnorm = nullptr; int64_t ext_n = 0, ext_base = 0;
     const uint16_t* ext_labels16 = nullptr; int ext_P = 0;   // the borrowed label table as counts (hb_index_set_label_count_table)
     // search workspace (grown on demand, reused)
-    float* q_tiles = nullptr; size_t q_tiles_bytes = 0;
-    float* q_aux = nullptr; size_t q_aux_bytes = 0;      // qn2 (chain) and qnorm (fp32), 2*nq floats
-    char* state = nullptr; size_t state_bytes = 0;
-    char* sched_dev = nullptr; size_t sched_bytes = 0;
-    char* tmp = nullptr; size_t tmp_bytes = 0;           // staging for host<->device convenience paths
+    hb_dev<float> q_tiles;
+    hb_dev<float> q_aux;                                 // qn2 (chain) and qnorm (fp32), 2*nq floats
+    hb_dev<char> state;
+    hb_dev<char> sched_dev;
+    hb_dev<char> tmp;                                    // staging for host<->device convenience paths
     hb_schedule sched;                                   // cached for (nqt, nbt)
     int force_G = 0, force_panel = 0;                    // test/tuning overrides
     int force_cq = 0, force_cb = 0;                      // cluster shape override (0 = automatic)
@@ -82,23 +83,23 @@ struct hb_index {
     int screen_env_off = 0;                              // HBIRD_EXACT_SCREEN=0 when the index was created
     int64_t f16_declined_cap = -1;                       // automatic state: no room for the fp16 tiles at this capacity (or the allocation failed): not asked again per search
     int last_path = 0, last_reason = 0;                  // what served the last search of a caller (hb_last_search_path)
-    unsigned* stamp_keep = nullptr; int stamp_keep_blocks = 0;   // the candidate launch's stamps, kept aside while nested searches reuse `state`
-    void* tiles16 = nullptr; int64_t f16_cap_rows = 0, f16_rows = 0;
-    int* f16_flag = nullptr; int f16_overflow = 0;       // a finite bank value overflowed fp16: the fp32 kernel serves this bank
+    hb_dev<unsigned> stamp_keep;                          // the candidate launch's stamps, kept aside while nested searches reuse `state`
+    hb_dev<void> tiles16; int64_t f16_cap_rows = 0, f16_rows = 0;
+    hb_dev<int> f16_flag; int f16_overflow = 0;       // a finite bank value overflowed fp16: the fp32 kernel serves this bank
     // ... and, where memory allows, the bank once more as plain fp32 rows [row][rows32_rs] for the exact re-rank (hbird_knn_f16.hip)
-    float* rows32 = nullptr; int64_t rows32_cap_rows = 0, rows32_rows = 0; int rows32_rs = 0;
+    hb_dev<float> rows32; int64_t rows32_cap_rows = 0, rows32_rows = 0; int rows32_rs = 0;
     int rerank_copy = 0;                                 // 0 = automatic, 1 = always, 2 = never (hb_index_set_rerank_copy)
     int64_t rows32_declined_cap = -1;                    // automatic mode found no room for the copy at this capacity: not asked again per search
     // the mean-centred form of that copy (hb_index_set_fp16_centre; hbird_f16_centre.hip): mu, two floats per row, four device scalars
     int fp16_centre = 0;                                 // the setting: 0 = the plain copy (default), 1 = centred
     int last_centred = 0;                                // the last search of a caller ran its candidate pass on the centred copy
     hb_centre_state centre;
-    void* q16 = nullptr; size_t q16_bytes = 0;
-    char* cand = nullptr; size_t cand_bytes = 0;
-    float* bmax = nullptr;                               // device scalar: max bank-row norm
-    char* mtmp = nullptr; size_t mtmp_bytes = 0;         // first-level lists of a two-level merge
-    char* fb = nullptr; size_t fb_bytes = 0;             // workspace of the uncertified queries (a caller's search) ...
-    char* fb1 = nullptr; size_t fb1_bytes = 0;           // ... and of their second fp16 pass
+    hb_dev<void> q16;
+    hb_dev<char> cand;
+    hb_dev<float> bmax;                                  // device scalar: max bank-row norm
+    hb_dev<char> mtmp;                                   // first-level lists of a two-level merge
+    hb_dev<char> fb;                                     // workspace of the uncertified queries (a caller's search) ...
+    hb_dev<char> fb1;                                    // ... and of their second fp16 pass
     int64_t last_fp16_fallbacks = 0;                     // queries of the last use_fp16 search that the fp32 kernel had to answer ...
     int64_t last_fp16_escalated = 0;                     // ... and queries whose first certificate failed (second fp16 pass, k' = 256, seeded floors)
     int fp16_escalation = 0;                             // 0 = on (automatic), 1 = off: uncertified queries go straight to the fp32 kernel (round 5)
@@ -107,8 +108,8 @@ struct hb_index {
     // pass that reuses `cand`, or a change of the bank (reset, add, capacity).
     struct screen_record { int state = 0; int64_t nq = 0; int kc = 0, klw = 0, centred = 0; } screen;   // state: HB_SCREEN_*
     hb_f16_adapt f16_adapt;                              // adaptive use of use_fp16 in mode 2 (hbird_calibrate.h): moving averages of the failing shares
-    char* bigk = nullptr; size_t bigk_bytes = 0;         // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
-    hb_schedule sched_esc; char* sched_esc_dev = nullptr; size_t sched_esc_bytes = 0;   // the nested searches' work list (the caller's stays cached)
+    hb_dev<char> bigk;                                   // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
+    hb_schedule sched_esc; hb_dev<char> sched_esc_dev;   // the nested searches' work list (the caller's stays cached)
     int score_output = 0;                                // 1: searches return ordering scores instead of distances
     int variant = 0;                                     // kernel selection for A/B runs and tests (hb_index_set_variant)
     int phases_on = 1;                                   // pool searches are launched in phases (hb_index_set_search_options)
@@ -118,11 +119,15 @@ struct hb_index {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int time_kernels = 0;
     // searches that exclude one row group per query (hb_index_set_row_groups / hb_index_search_excluding, hbird_exclude.hip)
-    int32_t* row_groups = nullptr; int64_t row_groups_n = 0, row_groups_cap = 0;   // device copy of groups[n]; n == 0: no table
+    hb_dev<int32_t> row_groups; int64_t row_groups_n = 0, row_groups_cap = 0;   // device copy of groups[n]; n == 0: no table
     int n_groups = 0; int64_t gmax = 0;                  // ... its group count and the largest group's rows
-    char* excl = nullptr; size_t excl_bytes = 0;         // workspace of an excluding search: staging, rung 0's lists, flags ...
-    char* excl1 = nullptr; size_t excl1_bytes = 0;       // ... and of its rung 1 (sized once the incomplete queries are counted)
+    hb_dev<char> excl;                                   // workspace of an excluding search: staging, rung 0's lists, flags ...
+    hb_dev<char> excl1;                                  // ... and of its rung 1 (sized once the incomplete queries are counted)
     int64_t last_excl[4] = {0, 0, 0, 0};                 // {rungs run, queries sent to rung 1, kf of the last rung run, gmax}
+    // a lazy copy or a table goes together with the counters that describe it (the caller has synchronised the stream where work may still read it)
+    void drop_tiles16() { tiles16.drop(); f16_rows = 0; f16_cap_rows = 0; }
+    void drop_rows32() { rows32.drop(); rows32_cap_rows = 0; rows32_rows = 0; }
+    void drop_labels() { labels.drop(); labels16.drop(); lab_cap = 0; }
 };
 
 void hb_set_error(const std::string& msg);

@@ -227,16 +227,6 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_fused_kernel(knn_args a) {
 }
 
 // ---- merge of the partial lists of one query: rank by counting over <= slots*k candidates --------
-static int ensure_bytes(char** p, size_t* have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) HB_HIP(hipFree(*p));
-    *p = nullptr; *have = 0;
-    size_t sz = need + need / 4;
-    HB_HIP(hipMalloc((void**)p, sz));
-    *have = sz;
-    return 0;
-}
-
 // Slot selection of a merge block: either the work list's slots of the query tile (qt_slots) or, in the second
 // level of a two-level merge, the `fixed_ng` group lists written by the first level (slot = qt * fixed_ng + j).
 // grp_size > 0 (first level): block (q, grp) merges only slots [grp*grp_size, (grp+1)*grp_size) of its query tile
@@ -405,9 +395,9 @@ static int launch_merge(hb_index* ix, const float* state_s, const unsigned* stat
     const int ng = (max_slots + grp - 1) / grp;
     if ((size_t)ng * k * 8 > lim) return hb_fail("hb_index_search: too many partial lists per query tile for the merge kernel");
     const size_t half = (size_t)nqt * ng * HB_QT * klw * 4;
-    if (ensure_bytes(&ix->mtmp, &ix->mtmp_bytes, 2 * half)) return -1;
-    float* ts = reinterpret_cast<float*>(ix->mtmp);
-    unsigned* ti = reinterpret_cast<unsigned*>(ix->mtmp + half);
+    if (ix->mtmp.ensure(2 * half, HB_GROW_QUARTER)) return -1;
+    float* ts = ix->mtmp.as<float>();
+    unsigned* ti = ix->mtmp.as<unsigned>(half);
     knn_merge_kernel<<<dim3((unsigned)nq, (unsigned)ng), dim3(64), (size_t)grp * per * 8, s>>>(state_s, state_i, cnts, pthr, per, qt_off, qt_slots,
                                                                                                 0, grp, ng, ts, ti, nq, k, klw, 0, 0,
                                                                                                 nullptr, nullptr, nullptr);
@@ -612,8 +602,6 @@ __global__ __launch_bounds__(256) void bigk_place_kernel(const int64_t* __restri
     }
 }
 
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }      // every carve-up of a workspace in this unit
-
 // What distinguishes ONE invocation of the launcher from the index's settings.  hb_launch_knn builds the level-0 call from the index; the
 // passes of a search with k > 256 (hb_launch_knn_bigk) and the re-search of uncertified queries (knn_research_failures) build a new one for
 // their nested search.  Nothing here is written to the index, so a nested search that fails leaves no trace in it.
@@ -634,11 +622,11 @@ static int hb_launch_knn_bigk(hb_index* ix, const knn_call& c, const float* q_de
     hipStream_t s = ix->stream;
     const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
     const size_t o_sc = al256((size_t)nq * 256 * 8), o_cs = o_sc + al256((size_t)nq * 256 * 4), o_ci = o_cs + al256((size_t)nqp * 4), tot = o_ci + al256((size_t)nqp * 4);
-    if (ensure_bytes(&ix->bigk, &ix->bigk_bytes, tot)) return -1;
-    int64_t* tmp_idx = reinterpret_cast<int64_t*>(ix->bigk);
-    float* tmp_sc = reinterpret_cast<float*>(ix->bigk + o_sc);
-    float* ceil_s = reinterpret_cast<float*>(ix->bigk + o_cs);
-    unsigned* ceil_i = reinterpret_cast<unsigned*>(ix->bigk + o_ci);
+    if (ix->bigk.ensure(tot, HB_GROW_QUARTER)) return -1;
+    int64_t* tmp_idx = ix->bigk.as<int64_t>();
+    float* tmp_sc = ix->bigk.as<float>(o_sc);
+    float* ceil_s = ix->bigk.as<float>(o_cs);
+    unsigned* ceil_i = ix->bigk.as<unsigned>(o_ci);
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)ceil_s, 0xFF800000u, (size_t)nqp, s));      // (padding queries: nothing behind -inf)
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)ceil_i, 0xFFFFFFFFu, (size_t)nqp, s));
     const int out_metric = c.score_out ? 0 : ix->metric;
@@ -658,13 +646,6 @@ static int hb_launch_knn_bigk(hb_index* ix, const knn_call& c, const float* q_de
     }
     if (c.timed) ix->last_knn_ms = knn_ms;
     return rc;
-}
-
-// the fp16 copy of the bank goes (the bank grew, the copy overflowed, or its allocation is about to be repeated)
-static int knn_drop_tiles16(hb_index* ix) {
-    if (ix->tiles16) HB_HIP(hipFree(ix->tiles16));
-    ix->tiles16 = nullptr; ix->f16_rows = 0; ix->f16_cap_rows = 0;
-    return 0;
 }
 
 // ---- stage 1: which path serves the call, and the upkeep of the screen's two optional copies of the bank --------------------------------
@@ -700,7 +681,7 @@ static int knn_choose_path(hb_index* ix, const knn_call& c, int64_t nq, int k, k
     p.automatic = c.fp16 == HB_FP16_AUTO;
     p.f16 = hb_screen_choose(sin, &p.why);
     if (p.f16 && p.automatic && !sin.have_copy && nq > 0 && ix->ntotal > 0) {      // the copy has to be made: only where it leaves the device room
-        if (knn_drop_tiles16(ix)) return -1;      // (the bank grew: the old copy goes first)
+        ix->drop_tiles16();      // (the bank grew: the old copy goes first)
         size_t free_b = 0, total_b = 0;
         HB_HIP(hipMemGetInfo(&free_b, &total_b));
         sin.mem_known = true; sin.free_b = free_b; sin.total_b = total_b;
@@ -727,15 +708,14 @@ static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, 
     // bring the fp16 copy of the bank fragment tiles up to date.  A finite value beyond the fp16 range (|x| > 65504) turns
     // into inf there and the scores into inf / NaN, which the exactness certificate cannot bound: such a bank stays on the
     // fp32 kernel (every query counts as a fallback)
-    if (!ix->f16_flag) { HB_HIP(hipMalloc((void**)&ix->f16_flag, 4)); HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s0)); }
+    if (!ix->f16_flag) { if (ix->f16_flag.ensure(4, HB_GROW_EXACT)) return -1; HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s0)); }
     if (ix->f16_cap_rows != ix->cap_rows) {
-        if (knn_drop_tiles16(ix)) return -1;
+        ix->drop_tiles16();      // (the bank grew, or the allocation is about to be repeated)
         // states 1 / 2: the caller asked for the copy, no memory for it is the search's error.  Automatic: the copy only buys speed, so an
         // allocation that fails all the same (the device filled up since hipMemGetInfo) is remembered for this capacity and the fp32 kernel answers
-        if (!automatic) HB_HIP(hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2));
-        else if (hipMalloc(&ix->tiles16, (size_t)ix->cap_rows * ix->dp16 * 2) != hipSuccess) {
-            (void)hipGetLastError();
-            ix->tiles16 = nullptr; ix->f16_declined_cap = ix->cap_rows;
+        if (!automatic) { if (ix->tiles16.ensure((size_t)ix->cap_rows * ix->dp16 * 2, HB_GROW_EXACT)) return -1; }
+        else if (ix->tiles16.try_ensure((size_t)ix->cap_rows * ix->dp16 * 2, HB_GROW_EXACT)) {
+            ix->f16_declined_cap = ix->cap_rows;
             f16 = false; why = HB_WHY_MEMORY;
             if (esc == 0) { ix->last_fp16_fallbacks = 0; ix->last_fp16_escalated = 0; }
         }
@@ -749,7 +729,7 @@ static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, 
         // (hb_index_set_fp16_centre: the rows as fl32(b - mu) with their per-row term, hbird_f16_centre.hip; a bank without a usable mean: the plain copy)
         int centred = 0;
         if (ix->fp16_centre && hb_centre_convert(ix, s0, &centred)) return -1;
-        if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, (_Float16*)ix->tiles16, ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
+        if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, ix->tiles16.as<_Float16>(), ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
         ix->f16_rows = ix->ntotal;
         HB_HIP(hipMemcpyAsync(&ix->f16_overflow, ix->f16_flag, 4, hipMemcpyDeviceToHost, s0));
         HB_HIP(hipStreamSynchronize(s0));
@@ -757,16 +737,13 @@ static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, 
     if (f16 && ix->f16_overflow) {
         f16 = false; why = HB_WHY_OVERFLOW;
         if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; }
-        if (automatic && knn_drop_tiles16(ix)) return -1;      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
+        if (automatic) ix->drop_tiles16();      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
     }
     // ... and the row-major fp32 copy for the re-rank (hbird_knn_f16.hip).  Automatic: by the bank's size (below; a 10 M x 768 bank:
     // 30.7 GB of tiles + 15.4 GB of fp16 tiles + 30.7 GB of rows, of 288)
     if (f16 && ix->rerank_copy != 2) {
         const int rs = (ix->g8 * 8 + 31) / 32 * 32;
-        if (ix->rows32 && (ix->rows32_cap_rows != ix->cap_rows || ix->rows32_rs != rs)) {
-            HB_HIP(hipFree(ix->rows32));
-            ix->rows32 = nullptr; ix->rows32_cap_rows = 0; ix->rows32_rows = 0;
-        }
+        if (ix->rows32 && (ix->rows32_cap_rows != ix->cap_rows || ix->rows32_rs != rs)) ix->drop_rows32();
         if (!ix->rows32 && (ix->rerank_copy == 1 || ix->rows32_declined_cap != ix->cap_rows)) {
             const size_t need = (size_t)ix->cap_rows * rs * 4;
             size_t free_b = 0, total_b = 0;
@@ -783,8 +760,8 @@ static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, 
             const size_t bank_b = (size_t)ix->cap_rows * ix->dp * 4;
             if (ix->rerank_copy == 1 || (bank_b <= (size_t)16e9 && bank_b + bank_b / 2 + need <= total_b / 100 * 55 &&
                                          free_b > need + std::max<size_t>(total_b / 16, (size_t)2 << 30))) {
-                if (hipMalloc((void**)&ix->rows32, need) == hipSuccess) { ix->rows32_cap_rows = ix->cap_rows; ix->rows32_rs = rs; ix->rows32_rows = 0; ix->rows32_declined_cap = -1; }
-                else { (void)hipGetLastError(); ix->rows32 = nullptr; if (ix->rerank_copy == 1) return hb_fail("hb_index_search: no memory for the re-rank copy of the bank"); }
+                if (!ix->rows32.try_ensure(need, HB_GROW_EXACT)) { ix->rows32_cap_rows = ix->cap_rows; ix->rows32_rs = rs; ix->rows32_rows = 0; ix->rows32_declined_cap = -1; }
+                else if (ix->rerank_copy == 1) return hb_fail("hb_index_search: no memory for the re-rank copy of the bank");
             }
         }
         if (ix->rows32 && ix->rows32_rows < ix->ntotal) {
@@ -824,8 +801,7 @@ static int knn_get_work_list(hb_index* ix, int esc, const hb_knn_plan& p, hipStr
     }
     const double* shares = wl.shares;
     hb_schedule& sc = esc == 0 ? ix->sched : ix->sched_esc;      // (the nested searches of uncertified queries keep a list of their own: the caller's stays cached)
-    char*& sched_dev = esc == 0 ? ix->sched_dev : ix->sched_esc_dev;
-    size_t& sched_bytes = esc == 0 ? ix->sched_bytes : ix->sched_esc_bytes;
+    hb_dev<char>& sched_dev = esc == 0 ? ix->sched_dev : ix->sched_esc_dev;
     const int nqt = p.nqt, nbt = p.nbt, G = p.G;
     const bool rebuilt = !(sc.nqt == nqt && sc.nbt == nbt && sc.panel == p.panel && sc.cq == p.cq && sc.cb == p.cb && sc.phased == p.phased &&
                            sc.xcd_share == p.xs && (sc.G == G || (long long)nqt * nbt < G) &&
@@ -836,14 +812,14 @@ static int knn_get_work_list(hb_index* ix, int esc, const hb_knn_plan& p, hipStr
         {sc.phase_bounds.data(), sc.phase_bounds.size() * 4}};
     size_t off[7] = {0};
     for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + al256(part[i].bytes);
-    const bool need_upload = rebuilt || sched_bytes < off[6];
-    if (ensure_bytes(&sched_dev, &sched_bytes, off[6])) return -1;
+    const bool need_upload = rebuilt || sched_dev.bytes < off[6];
+    if (sched_dev.ensure(off[6], HB_GROW_QUARTER)) return -1;
     if (need_upload) {
         for (int i = 0; i < 6; ++i) HB_HIP(hipMemcpyAsync(sched_dev + off[i], part[i].data, part[i].bytes, hipMemcpyHostToDevice, s));
         HB_HIP(hipStreamSynchronize(s));   // host vectors may be rebuilt by the next call
     }
-    auto ints = [&](int i) { return reinterpret_cast<const int*>(sched_dev + off[i]); };
-    wl.sc = &sc; wl.segs = reinterpret_cast<const hb_seg*>(sched_dev);
+    auto ints = [&](int i) { return sched_dev.as<const int>(off[i]); };
+    wl.sc = &sc; wl.segs = sched_dev.as<const hb_seg>();
     wl.wg_off = ints(1); wl.qt_off = ints(2); wl.qt_slots = ints(3); wl.wg_member = ints(4); wl.phase_bounds = ints(5);
     wl.n_phases = (int)sc.phase_clock.size() + 1;
     return 0;
@@ -864,7 +840,7 @@ static int knn_carve_workspace(hb_index* ix, const knn_call& c, const hb_knn_pla
     const size_t floor_bytes = (size_t)nqt * HB_QT * 4 * 17;              // shared threshold floors, one per query, + 16 quota-floor keys per query
     const size_t prog_bytes = ((size_t)std::max(1, sc.n_clusters) * HB_CLUSTER_MAX + 1) * HB_CLUSTER_LINE * 4;   // progress words, a line each, + statistics
     const size_t stamp_bytes = (size_t)sc.G * 32;                       // per-block {start, end, XCC id} stamps of the last kNN launch with its shader-cycle counts (wg_stamp, hbird_knn_dev.h)
-    if (ensure_bytes(&ix->state, &ix->state_bytes, 2 * state_half + 2 * state_aux + floor_bytes + prog_bytes + stamp_bytes)) return -1;
+    if (ix->state.ensure(2 * state_half + 2 * state_aux + floor_bytes + prog_bytes + stamp_bytes, HB_GROW_QUARTER)) return -1;
     out->state_aux = state_aux; out->prog_bytes = prog_bytes; out->stamp_bytes = stamp_bytes;
     char* const floors = ix->state + 2 * state_half + 2 * state_aux;
     knn_args& a = out->a;
@@ -875,11 +851,11 @@ static int knn_carve_workspace(hb_index* ix, const knn_call& c, const hb_knn_pla
     if (a.wg_stamp) HB_HIP(hipMemsetAsync(a.wg_stamp, 0, stamp_bytes, s));   // a block that never stamps reads 0 / 0 (hb_stamps_summarise)
     a.bank_tiles = ix->tiles; a.binit = ix->binit; a.q_tiles = ix->q_tiles;
     a.ceil_s = c.ceil_s; a.ceil_i = c.ceil_i; a.segs = wl.segs; a.wg_off = wl.wg_off; a.wg_end = a.wg_off + 1;
-    a.state_s = reinterpret_cast<float*>(ix->state);
-    a.state_i = reinterpret_cast<unsigned*>(ix->state + state_half);
+    a.state_s = ix->state.as<float>();
+    a.state_i = ix->state.as<unsigned>(state_half);
     a.g8 = ix->g8; a.k = k; a.klw = klw;
-    a.state_cnt = reinterpret_cast<int*>(ix->state + 2 * state_half);
-    a.state_thr = reinterpret_cast<float*>(ix->state + 2 * state_half + state_aux);
+    a.state_cnt = ix->state.as<int>(2 * state_half);
+    a.state_thr = ix->state.as<float>(2 * state_half + state_aux);
     a.gthr = reinterpret_cast<unsigned*>(floors);
     a.qfl = a.gthr + (size_t)nqt * HB_QT;
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)a.gthr, 0x007FFFFF, (size_t)nqt * HB_QT * 17, s));   // key(-inf)
@@ -961,12 +937,12 @@ static int knn_read_time(hb_index* ix, const knn_call& c) {
 // known, [their rows][queries][aux][floors][ids][distances]
 // -- a caller's search keeps it in fb, the second fp16 pass in fb1 (the fp32 search of what is left has no failures of its own)
 struct knn_level_buf {
-    char*& buf; size_t& bytes;
+    hb_devbuf& buf;
     size_t o_kth, o_flo, o_rows;
-    knn_level_buf(hb_index* ix, int esc, int64_t nq) : buf(esc == 0 ? ix->fb : ix->fb1), bytes(esc == 0 ? ix->fb_bytes : ix->fb1_bytes), o_kth(al256((size_t)nq + 64)),
+    knn_level_buf(hb_index* ix, int esc, int64_t nq) : buf(esc == 0 ? ix->fb : ix->fb1), o_kth(al256((size_t)nq + 64)),
                                                        o_flo(o_kth + al256((size_t)nq * 4)), o_rows(o_flo + al256((size_t)nq * 4)) {}
-    float* kth() const { return reinterpret_cast<float*>(buf + o_kth); }
-    float* flo() const { return reinterpret_cast<float*>(buf + o_flo); }
+    float* kth() const { return buf.as<float>(o_kth); }
+    float* flo() const { return buf.as<float>(o_flo); }
 };
 
 // The queries `bad` of this level are searched again: gathered, re-tiled, searched by a nested call, scattered into the outputs.
@@ -976,28 +952,20 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     const int esc = c.esc;
     const int64_t nf = (int64_t)bad.size();
     const knn_level_buf lv(ix, esc, nq);
-    char*& fbuf = lv.buf;
-    size_t& fbuf_bytes = lv.bytes;
+    hb_devbuf& fbuf = lv.buf;
     const size_t o_rows = lv.o_rows;
     // the second pass needs k' = 256 > the first one's, a bank worth a candidate pass, and is not repeated
     const bool again16 = esc == 0 && ix->fp16_escalation == 0 && p.kc < 256 && ix->ntotal >= 4096;
     const size_t o_q = o_rows + al256((size_t)nf * 8), o_aux = o_q + al256((size_t)nf * ix->d * 4), o_seed = o_aux + al256((size_t)nf * 8),
                  o_idx = o_seed + al256((size_t)nf * 4), o_dist = o_idx + al256((size_t)nf * k * 8), tot2 = o_dist + al256((size_t)nf * k * 4);
-    if (fbuf_bytes < tot2) {
-        char* nb = nullptr;
-        HB_HIP(hipMalloc((void**)&nb, tot2 + tot2 / 4));
-        HB_HIP(hipMemcpyAsync(nb, fbuf, o_rows, hipMemcpyDeviceToDevice, s));      // (the seeds of this level)
-        HB_HIP(hipStreamSynchronize(s));
-        HB_HIP(hipFree(fbuf));
-        fbuf = nb; fbuf_bytes = tot2 + tot2 / 4;
-    }
+    if (fbuf.ensure_keep(tot2, HB_GROW_QUARTER, o_rows, s)) return -1;      // (kept: the certificates and the seeds of this level)
     const float *kth = lv.kth(), *flo = lv.flo();      // (after the move)
-    int64_t* d_rows = reinterpret_cast<int64_t*>(fbuf + o_rows);
-    float* d_q = reinterpret_cast<float*>(fbuf + o_q);
-    float* d_aux = reinterpret_cast<float*>(fbuf + o_aux);
-    float* d_seed = reinterpret_cast<float*>(fbuf + o_seed);
-    int64_t* d_fi = reinterpret_cast<int64_t*>(fbuf + o_idx);
-    float* d_fd = reinterpret_cast<float*>(fbuf + o_dist);
+    int64_t* d_rows = fbuf.as<int64_t>(o_rows);
+    float* d_q = fbuf.as<float>(o_q);
+    float* d_aux = fbuf.as<float>(o_aux);
+    float* d_seed = fbuf.as<float>(o_seed);
+    int64_t* d_fi = fbuf.as<int64_t>(o_idx);
+    float* d_fd = fbuf.as<float>(o_dist);
     HB_HIP(hipMemcpyAsync(d_rows, bad.data(), (size_t)nf * 8, hipMemcpyHostToDevice, s));
     if (hb_launch_gather_rows(q_dev, nq, ix->d, d_rows, nf, d_q, s)) return -1;
     if (hb_launch_gather_rows(again16 ? flo : kth, nq, 1, d_rows, nf, d_seed, s)) return -1;
@@ -1008,14 +976,7 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     //   sched    the nested levels keep ONE work list of their own (sched_esc), so the caller's stays cached;
     //   fb       this level's workspace, the second fp16 pass's is fb1 (knn_level_buf).
     if (esc == 0 && ws.a.wg_stamp) {
-        const hb_schedule& sc = *wl.sc;
-        const size_t stamp_bytes = ws.stamp_bytes;
-        if (ix->stamp_keep_blocks < sc.G) {
-            if (ix->stamp_keep) HB_HIP(hipFree(ix->stamp_keep));
-            ix->stamp_keep = nullptr; ix->stamp_keep_blocks = 0;
-            HB_HIP(hipMalloc((void**)&ix->stamp_keep, stamp_bytes));
-            ix->stamp_keep_blocks = sc.G;
-        }
+        if (ix->stamp_keep.ensure(ws.stamp_bytes, HB_GROW_EXACT)) return -1;      // (32 bytes per workgroup of the candidate launch)
         HB_HIP(hipMemcpyAsync(ix->stamp_keep, ws.a.wg_stamp, ws.stamp_bytes, hipMemcpyDeviceToDevice, s));
         ix->wg_stamp_dev = ix->stamp_keep;
     }
@@ -1042,17 +1003,17 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     const bool centred = path.centred;
     // fp16 copy of the query fragment tiles (the bank's is up to date: top of this function)
     const int64_t nqp = (int64_t)nqt * HB_QT;
-    if (ensure_bytes((char**)&ix->q16, &ix->q16_bytes, (size_t)nqp * ix->dp16 * 2)) return -1;
+    if (ix->q16.ensure((size_t)nqp * ix->dp16 * 2, HB_GROW_QUARTER)) return -1;
     // centred: fp16 tiles of q - t mu, c_q and ||q - t mu|| per query; a caller's search also derives t and, from it, the rows' init values
     hb_centre_view cview{nullptr, nullptr, nullptr};
-    if (centred) { if (hb_centre_queries(ix, nq, esc == 0, (_Float16*)ix->q16, &cview, s)) return -1; }
-    else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, (_Float16*)ix->q16, ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
-    if (ensure_bytes(&ix->cand, &ix->cand_bytes, (size_t)nq * kc * 12)) return -1;
-    int64_t* cand_idx = reinterpret_cast<int64_t*>(ix->cand);
-    float* cand_dist = reinterpret_cast<float*>(ix->cand + (size_t)nq * kc * 8);
+    if (centred) { if (hb_centre_queries(ix, nq, esc == 0, ix->q16.as<_Float16>(), &cview, s)) return -1; }
+    else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, ix->q16.as<_Float16>(), ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
+    if (ix->cand.ensure((size_t)nq * kc * 12, HB_GROW_QUARTER)) return -1;
+    int64_t* cand_idx = ix->cand.as<int64_t>();
+    float* cand_dist = ix->cand.as<float>((size_t)nq * kc * 8);
     knn16_args h;
     h.wg_stamp = a.wg_stamp;
-    h.bank16 = reinterpret_cast<const _Float16*>(ix->tiles16); h.binit = centred ? ix->centre.init16 : ix->binit; h.q16 = reinterpret_cast<const _Float16*>(ix->q16); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
+    h.bank16 = ix->tiles16.as<const _Float16>(); h.binit = centred ? ix->centre.init16 : ix->binit; h.q16 = ix->q16.as<const _Float16>(); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
     h.state_s = a.state_s; h.state_i = a.state_i; h.g16 = ix->dp16 / 16; h.k = kc; h.klw = klw;
     h.state_cnt = a.state_cnt; h.state_thr = a.state_thr; h.gthr = a.gthr;
     h.wg_member = a.wg_member; h.prog = a.prog; h.cl = a.cl; h.lag = a.lag; h.cl_stats = a.cl_stats;
@@ -1064,8 +1025,8 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     if (launch_merge(ix, a.state_s, a.state_i, a.state_cnt, a.state_thr, wl.qt_off, wl.qt_slots, sc.max_slots_per_qt, nqt, nq, kc, klw, 0, 0, nullptr,
                      cand_idx, cand_dist, s)) return -1;
     const knn_level_buf lv(ix, esc, nq);
-    if (ensure_bytes(&lv.buf, &lv.bytes, lv.o_rows)) return -1;
-    unsigned char* cert = reinterpret_cast<unsigned char*>(lv.buf);
+    if (lv.buf.ensure(lv.o_rows, HB_GROW_QUARTER)) return -1;
+    unsigned char* cert = lv.buf.as<unsigned char>();
     float *kth = lv.kth(), *flo = lv.flo();
     HB_HIP(hipMemsetD32Async((hipDeviceptr_t)kth, 0xFF800000u, (lv.o_rows - lv.o_kth) / 4, s));    // -inf: no seed (a query with fewer than k candidates)
     const float* q_aux = c.q_aux;

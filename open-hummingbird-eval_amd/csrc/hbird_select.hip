@@ -76,15 +76,6 @@ __global__ __launch_bounds__(256) void select_label_rows_kernel(const T* __restr
     dst[t] = src[sid * per_row + p];
 }
 
-static int sel_grow(char** p, size_t* have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) HB_HIP(hipFree(*p));
-    *p = nullptr; *have = 0;
-    HB_HIP(hipMalloc((void**)p, need));
-    *have = need;
-    return 0;
-}
-
 static inline bool has_labels(const hb_index* ix) { return ix->nlabels > 0 && (ix->labels || ix->labels16); }
 
 extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const int64_t* ids, int64_t n, int ids_on_device) {
@@ -115,12 +106,12 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
         if (e != hipSuccess) return hb_fail(std::string("hb_index_add_from: ") + hipGetErrorString(e));
     }
     // staging in dst->tmp: [flag, 256 B] [ids (host path)]
-    if (sel_grow(&dst->tmp, &dst->tmp_bytes, 256 + (ids_on_device ? 0 : (size_t)n * 8))) return -1;
-    int* flag = reinterpret_cast<int*>(dst->tmp);
+    if (dst->tmp.ensure(256 + (ids_on_device ? 0 : (size_t)n * 8), HB_GROW_EXACT)) return -1;
+    int* flag = dst->tmp.as<int>();
     const int64_t* d_ids = ids;
     if (!ids_on_device) {
         HB_HIP(hipMemcpyAsync(dst->tmp + 256, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
-        d_ids = reinterpret_cast<const int64_t*>(dst->tmp + 256);
+        d_ids = dst->tmp.as<const int64_t>(256);
     }
     HB_HIP(hipMemsetAsync(flag, 0, 4, s));
     select_check_ids_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(d_ids, n, src->ntotal, labs ? src->nlabels : src->ntotal, flag);
@@ -154,8 +145,8 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
         const size_t row_bytes = (size_t)dst->lab_stride() * (dst->label_P ? 2 : 4);
         if (row_bytes % 16 == 0) {
             const int per = (int)(row_bytes / 16);
-            const uint4* sp = dst->label_P ? (const uint4*)src->labels16 : (const uint4*)src->labels;
-            uint4* dp = (dst->label_P ? (uint4*)dst->labels16 : (uint4*)dst->labels) + dst->nlabels * (int64_t)per;
+            const uint4* sp = dst->label_P ? src->labels16.as<const uint4>() : src->labels.as<const uint4>();
+            uint4* dp = (dst->label_P ? dst->labels16.as<uint4>() : dst->labels.as<uint4>()) + dst->nlabels * (int64_t)per;
             select_label_rows_kernel<uint4><<<dim3((unsigned)((n * per + 255) / 256)), dim3(256), 0, s>>>(sp, src->nlabels, per, d_ids, n, dp);
         } else {
             const int per = dst->c;

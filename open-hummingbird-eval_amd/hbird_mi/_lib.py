@@ -102,6 +102,7 @@ SIGNATURES = {
     "hb_schedule_plan_weighted": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_int64, POINTER(c_int64)]),
     "hb_index_kernel_clock": (c_int, [c_void_p, POINTER(c_double)]),
     "hb_index_xcd_stats": (c_int, [c_void_p, c_int, POINTER(c_double)]),
+    "hb_debug_live_allocations": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
     "hb_calibration_new": (c_void_p, [c_int]),
     "hb_calibration_free": (None, [c_void_p]),
     "hb_calibration_state": (c_int, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
