@@ -183,6 +183,12 @@ extern "C" int hb_index_fp16_centre_info(const hb_index_t* ix, double out[8]) {
     out[6] = ix->fp16_centre; out[7] = ix->last_centred;
     return 0;
 }
+extern "C" int hb_index_last_centre(hb_index_t* ix, float* mu, float* scalars, float* g, float* init16, uint16_t* bank16, float* cq, float* qcn, uint16_t* q16,
+                                    int64_t info[8]) {
+    if (!ix) return hb_fail("hb_index_last_centre: NULL index handle");
+    if (!info) return hb_fail("hb_index_last_centre: info is NULL");
+    return hb_centre_readout(ix, mu, scalars, g, init16, bank16, cq, qcn, q16, info);
+}
 // What the level-0 candidate pass of the last search left behind (include/hbird_hip_screen.h): the merged lists and pass scores in `cand`,
 // the first certificates at the start of `fb`.  Host bookkeeping and copies only.
 extern "C" int hb_index_last_screen(hb_index_t* ix, int64_t* cand_rows, float* pass_scores, unsigned char* certified, int64_t capacity_queries, int64_t info[4]) {

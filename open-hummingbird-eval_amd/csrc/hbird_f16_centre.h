@@ -16,6 +16,9 @@ struct hb_centre_state {
     int64_t cap_rows = 0;           // capacity the row arrays were allocated for
     int64_t rows = 0;               // rows converted with mu
     int active = 0;                 // the fp16 copy holds centred rows (0: no copy yet, or a non-finite / all-zero mean: the plain copy)
+    // hb_index_last_centre: host bookkeeping of the last centred pass (hb_centre_queries), whose c_q and ||q - t mu|| lie in qaux
+    int64_t q_n = 0;                // its queries
+    int q_level = -1;               // 0: a caller's pass, 1: the second pass over its uncertified queries, -1: none since the state was dropped
 };
 
 // per-query constants of one centred pass, for the re-rank: c_q = q.mu, ||q - t mu||, the device scalars above
@@ -24,3 +27,4 @@ struct hb_centre_view { const float* cq; const float* qcn; const float* sc; };
 void hb_centre_drop(hb_index* ix);
 int hb_centre_convert(hb_index* ix, hipStream_t s, int* centred_out);
 int hb_centre_queries(hb_index* ix, int64_t nq, int first, _Float16* q16, hb_centre_view* view, hipStream_t s);
+int hb_centre_readout(hb_index* ix, float* mu, float* scalars, float* g, float* init16, uint16_t* bank16, float* cq, float* qcn, uint16_t* q16, int64_t info[8]);

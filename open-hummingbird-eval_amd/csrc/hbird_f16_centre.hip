@@ -216,7 +216,12 @@ __global__ __launch_bounds__(256) void centre_query_kernel(const float* __restri
             const float m[8] = {me[0], me[1], me[2], me[3], mo[0], mo[1], mo[2], mo[3]};
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const float d0 = fmaf(nt, m[2 * c], e[c]), d1 = fmaf(nt, m[2 * c + 1], o[c]);
+                float d0 = fmaf(nt, m[2 * c], e[c]), d1 = fmaf(nt, m[2 * c + 1], o[c]);
+                // The fp16 image is taken of the ROUNDED fp32 value, the one the norm below is summed from.  Left to itself the compiler merges
+                // the fmaf and the conversion of the first and last component of every 8-group into v_fma_mixlo/hi_f16, which rounds the exact
+                // q - t mu to fp16 ONCE: one element in 2^13 then differs in its last bit from the image of fl32(q - t mu)
+                // (tests/test_f16_centre_readout_gpu.py caught it).  The empty asm hides where d0 / d1 came from.
+                asm volatile("" : "+v"(d0), "+v"(d1));
                 n2 = fma((double)d0, (double)d0, n2); n2 = fma((double)d1, (double)d1, n2);
                 out[2 * c] = (_Float16)d0; out[2 * c + 1] = (_Float16)d1;
             }
@@ -241,7 +246,7 @@ __global__ __launch_bounds__(256) void centre_init16_kernel(const float* __restr
 void hb_centre_drop(hb_index* ix) {
     hb_centre_state& c = ix->centre;
     c.mu.drop(); c.g.drop(); c.init16.drop(); c.sc.drop(); c.qaux.drop();
-    c.cap_rows = 0; c.active = 0; c.rows = 0;
+    c.cap_rows = 0; c.active = 0; c.rows = 0; c.q_n = 0; c.q_level = -1;
 }
 
 // mu from the rows present now.  -> c.active (0: a non-finite or all-zero mean: the plain copy serves this bank)
@@ -322,5 +327,37 @@ int hb_centre_queries(hb_index* ix, int64_t nq, int first, _Float16* q16, hb_cen
     centre_query_kernel<<<dim3((unsigned)((nqp + 255) / 256)), dim3(256), 0, s>>>(ix->q_tiles, ix->g8, c.mu, c.sc, q16, ix->dp16 / 16, nqp / 32, nq, qcn);
     HB_HIP(hipGetLastError());
     view->cq = cq; view->qcn = qcn; view->sc = c.sc;
+    c.q_n = nq; c.q_level = first ? 0 : 1;      // (hb_index_last_centre)
+    return 0;
+}
+
+// What the conversion left (include/hbird_hip_centre.h): host bookkeeping and copies, no launch.
+int hb_centre_readout(hb_index* ix, float* mu, float* scalars, float* g, float* init16, uint16_t* bank16, float* cq, float* qcn, uint16_t* q16,
+                      int64_t info[8]) {
+    const hb_centre_state& c = ix->centre;
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    info[4] = -1;
+    const int64_t n_g = (c.rows + 31) / 32 * 32, n_init = (c.rows + HB_BT - 1) / HB_BT * HB_BT;
+    if (!ix->fp16_centre || !c.active || c.rows <= 0 || !ix->tiles16 || !c.mu || !c.g || !c.init16 || !c.sc || c.cap_rows < n_init || ix->f16_cap_rows < n_g)
+        return hb_fail("hb_index_last_centre: no active centred copy (centring off, no screened search yet, a bank without a usable mean, or a reset since)");
+    const int n_mu = std::max(ix->dp16, ix->g8 * 8);
+    // the query side: the last search of a caller ran centred and the bank has not changed since (the screen record goes with either)
+    const bool q_ok = c.q_level >= 0 && ix->last_centred && ix->screen.state != HB_SCREEN_NONE && c.qaux.bytes >= 2 * al256((size_t)c.q_n * 4) &&
+                      ix->q16.bytes >= (size_t)((c.q_n + HB_QT - 1) / HB_QT * HB_QT) * ix->dp16 * 2;
+    const int64_t n = q_ok ? c.q_n : 0, n_qpad = (n + HB_QT - 1) / HB_QT * HB_QT;
+    info[0] = c.rows; info[1] = ix->dp16; info[2] = n_mu; info[3] = n; info[4] = q_ok ? c.q_level : -1; info[5] = n_g; info[6] = n_init; info[7] = n_qpad;
+    HB_HIP(hipSetDevice(ix->device));
+    HB_HIP(hipStreamSynchronize(ix->stream));
+    if ((cq || qcn || q16) && !q_ok)
+        return hb_fail("hb_index_last_centre: the last search of a caller did not run centred (or the bank has changed since: reset, add, capacity)");
+    if (mu) HB_HIP(hipMemcpy(mu, c.mu, (size_t)n_mu * 4, hipMemcpyDeviceToHost));
+    if (scalars) HB_HIP(hipMemcpy(scalars, c.sc, 16, hipMemcpyDeviceToHost));
+    if (g) HB_HIP(hipMemcpy(g, c.g, (size_t)n_g * 4, hipMemcpyDeviceToHost));
+    if (init16) HB_HIP(hipMemcpy(init16, c.init16, (size_t)n_init * 4, hipMemcpyDeviceToHost));
+    if (bank16) HB_HIP(hipMemcpy(bank16, ix->tiles16, (size_t)n_g * ix->dp16 * 2, hipMemcpyDeviceToHost));
+    const size_t b_f = al256((size_t)n * 4);      // (centre_qaux's carve-up)
+    if (cq && n) HB_HIP(hipMemcpy(cq, c.qaux.as<float>(), (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (qcn && n) HB_HIP(hipMemcpy(qcn, c.qaux.as<float>(b_f), (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (q16 && n) HB_HIP(hipMemcpy(q16, ix->q16, (size_t)n_qpad * ix->dp16 * 2, hipMemcpyDeviceToHost));
     return 0;
 }

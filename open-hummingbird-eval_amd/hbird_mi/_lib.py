@@ -123,6 +123,7 @@ SIGNATURES_CENTRE = {
     "hb_index_set_fp16_centre": (c_int, [c_void_p, c_int]),
     "hb_index_fp16_centre_info": (c_int, [c_void_p, POINTER(c_double)]),
     "hb_multi_set_fp16_centre": (c_int, [c_void_p, c_int]),
+    "hb_index_last_centre": (c_int, [c_void_p] + [c_void_p] * 8 + [POINTER(c_int64)]),
 }
 
 # ... and include/hbird_hip_select.h (sub-bank views, csrc/hbird_select.hip: rows of one index gathered into another on the device)

@@ -581,6 +581,31 @@ class HipFlatIndex:
         return {"centred": bool(out[0]), "mu_norm": float(out[1]), "cmax": float(out[2]), "bmax": float(out[3]), "t": float(out[4]),
                 "rows": int(out[5]), "setting": bool(out[6]), "last_search_centred": bool(out[7])}
 
+    def last_centre(self, queries: bool = True) -> dict:
+        """What the centred conversion left (hb_index_last_centre, include/hbird_hip_centre.h), as numpy arrays.  Bank side: mu float32 [n_mu],
+        cmax / mu_norm / mu2 / t (numpy float32 scalars, the device's four), g float32 [32 ceil(rows / 32)], init16 float32 [256 ceil(rows / 256)],
+        bank16 uint16 (the raw fp16 tiles of the converted row tiles; layout in the header), rows, dp16, n_mu.  Query side, of the last centred
+        pass: n, level (0: the caller's pass, 1: the second pass over its uncertified queries), cq / qcn float32 [n], q16 uint16 (raw tiles of
+        256 ceil(n / 256) queries).  queries=False reads the bank side only (n = 0, level = -1 when the query side is not valid).  Raises
+        when there is no active centred copy, and with queries=True when the last search of a caller did not run centred or the bank has changed
+        since."""
+        lib = _lib.lib()
+        info = (ctypes.c_int64 * 8)()
+        _lib.check(lib.hb_index_last_centre(self._h, None, None, None, None, None, None, None, None, info))
+        rows, dp16, n_mu, n, level, n_g, n_init, n_qpad = (int(v) for v in info)
+        mu, sc = np.empty(n_mu, dtype=np.float32), np.empty(4, dtype=np.float32)
+        g, init16 = np.empty(n_g, dtype=np.float32), np.empty(n_init, dtype=np.float32)
+        bank16 = np.empty(n_g * dp16, dtype=np.uint16)
+        out = {"rows": rows, "dp16": dp16, "n_mu": n_mu, "n": n, "level": level}
+        if queries:
+            cq, qcn, q16 = np.empty(max(n, 1), dtype=np.float32), np.empty(max(n, 1), dtype=np.float32), np.empty(max(n_qpad * dp16, 1), dtype=np.uint16)
+            _lib.check(lib.hb_index_last_centre(self._h, _ptr(mu), _ptr(sc), _ptr(g), _ptr(init16), _ptr(bank16), _ptr(cq), _ptr(qcn), _ptr(q16), info))
+            out.update(cq=cq[:n], qcn=qcn[:n], q16=q16[:n_qpad * dp16])
+        else:
+            _lib.check(lib.hb_index_last_centre(self._h, _ptr(mu), _ptr(sc), _ptr(g), _ptr(init16), _ptr(bank16), None, None, None, info))
+        out.update(mu=mu, cmax=sc[0], mu_norm=sc[1], mu2=sc[2], t=sc[3], g=g, init16=init16, bank16=bank16)
+        return out
+
     def last_fp16_fallbacks(self) -> int:
         n = ctypes.c_int64(0)
         _lib.check(_lib.lib().hb_index_last_fp16_fallbacks(self._h, ctypes.byref(n)))

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import f16_centre_refs as CR
 import f16_pass_refs as R
 from hbird_mi import _lib
 from hbird_mi.nn.search_hip import HipFlatIndex
@@ -210,6 +211,17 @@ def test_centred_form_h1_h2_and_flags(cuda_device, c):
     L, info = ix.last_screen(), ix.fp16_centre_info()
     assert ix.last_search_path()["path"] == "fp16_chain" and L["centred"] and info["centred"] and info["last_search_centred"] and info["rows"] == c.N, (c, info)
     assert (L["nq"], L["kc"], L["klw"]) == (c.nq, kc, R.klw_of(kc))
+    # the cmax, ||mu|| and t that enter E' below are the reference's (tests/f16_centre_refs.py), computed from the read-out mu: the theorem is
+    # checked under a bound this test has verified, not one it was handed
+    C = ix.last_centre()
+    u32 = lambda v: np.asarray(v, np.float32).view(np.uint32)
+    assert (info["cmax"], info["mu_norm"], info["t"]) == (float(C["cmax"]), float(C["mu_norm"]), float(C["t"])), (c, info)
+    mu2_ref, mu_norm_ref = CR.mu_scalars(C["mu"])
+    cmax_ref = CR.cmax_ref(CR.differences(W["bank"], C["mu"]))
+    assert u32(C["cmax"]) == u32(cmax_ref), f"{c}: cmax {C['cmax']!r}, max ||fl32(b - mu)|| rounded up is {cmax_ref!r}"
+    assert u32(C["mu_norm"]) == u32(mu_norm_ref), f"{c}: ||mu|| {C['mu_norm']!r}, rounded up from the read-out mu {mu_norm_ref!r}"
+    t_ref, t_tol = CR.t_ref(CR.chain_dot(W["queries"], C["mu"][:c.D]), c.nq, mu2_ref)
+    assert abs(float(C["t"]) - float(t_ref)) <= t_tol, f"{c}: t {C['t']!r}, sum c_q / (nq mu.mu) = {t_ref!r} (tolerance {t_tol:.3g})"
     bad, fig = R.check_centred(L["rows"], L["scores"], L["certified"], W["queries"], W["bank"], c.metric, c.k, kc, info)
     print("F16PASS " + json.dumps(dict(c._asdict(), kc=kc, centred=True, certified_share=float(L["certified"].mean()), **fig)))
     _no_complaints(bad, c)

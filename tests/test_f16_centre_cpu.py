@@ -199,19 +199,20 @@ def test_a_bound_with_075_is_caught_on_the_shifted_rounding_world(D, metric):
 
 
 # ---- the C entries ---------------------------------------------------------------------------------------------------------------------------
-NEW_ENTRIES = ("hb_index_set_fp16_centre", "hb_index_fp16_centre_info", "hb_multi_set_fp16_centre")
+NEW_ENTRIES = ("hb_index_set_fp16_centre", "hb_index_fp16_centre_info", "hb_multi_set_fp16_centre", "hb_index_last_centre")
 
 
-def test_the_three_centre_entries_are_declared_exported_and_bound():
+def test_the_four_centre_entries_are_declared_exported_and_bound():
     from hbird_mi import _lib
     L = _lib.lib()
     header = open(os.path.join(ROOT, "include", "hbird_hip_centre.h")).read()
     declared = set(re.findall(r"^int (hb_[a-z0-9_]+)\(", header, flags=re.M))
     assert declared == set(NEW_ENTRIES) == set(_lib.SIGNATURES_CENTRE)
     assert '#include "hbird_hip_centre.h"' in open(os.path.join(ROOT, "include", "hbird_hip.h")).read()
-    c_int, c_void_p, dp = ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
+    c_int, c_void_p, dp, ip = ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
     want = {"hb_index_set_fp16_centre": (c_int, [c_void_p, c_int]), "hb_index_fp16_centre_info": (c_int, [c_void_p, dp]),
-            "hb_multi_set_fp16_centre": (c_int, [c_void_p, c_int])}
+            "hb_multi_set_fp16_centre": (c_int, [c_void_p, c_int]),
+            "hb_index_last_centre": (c_int, [c_void_p] * 9 + [ip])}      # the handle, eight host arrays (each may be NULL), info[8]
     for name in NEW_ENTRIES:
         fn = getattr(L, name)                       # AttributeError: not exported
         assert fn.restype is want[name][0] and list(fn.argtypes) == want[name][1], name
@@ -222,8 +223,9 @@ def test_the_three_centre_entries_are_declared_exported_and_bound():
 def test_the_centre_entries_reject_null_handles_and_bad_values_without_a_gpu():
     from hbird_mi import _lib
     L = _lib.lib()
-    out = (ctypes.c_double * 8)()
-    for name, args in {"hb_index_set_fp16_centre": (None, 1), "hb_index_fp16_centre_info": (None, out), "hb_multi_set_fp16_centre": (None, 1)}.items():
+    out, info = (ctypes.c_double * 8)(), (ctypes.c_int64 * 8)()
+    for name, args in {"hb_index_set_fp16_centre": (None, 1), "hb_index_fp16_centre_info": (None, out), "hb_multi_set_fp16_centre": (None, 1),
+                       "hb_index_last_centre": (None,) + (None,) * 8 + (info,)}.items():
         assert getattr(L, name)(*args) != 0 and b"NULL" in L.hb_last_error(), name
 
 
@@ -231,6 +233,7 @@ def test_the_python_surface_has_the_switches():
     from hbird_mi.nn import search_hip
     for cls in (search_hip.HipFlatIndex, search_hip.HipMultiIndex):
         assert callable(getattr(cls, "set_fp16_centre")) and callable(getattr(cls, "fp16_centre_info"))
+    assert callable(search_hip.HipFlatIndex.last_centre)
     import inspect
     src = inspect.getsource(search_hip.NearestNeighborSearchHIP.__init__)
     assert 'kwargs.pop("fp16_centre", False)' in src
