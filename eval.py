@@ -74,6 +74,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="score on the TRAINING images instead of the validation split (not in the reference): every training image queries the "
                         "bank with its own rows excluded, so --grid-k / --grid-beta / --memory-sizes can be chosen without tuning on validation data")
     p.add_argument("--leave-one-out-images", type=_positive_int, default=None, metavar="N", help="stop the leave-one-out pass after N images")
+    p.add_argument("--leave-one-out-screen", action="store_true",
+                   help="with --leave-one-out: the certified fp16 screen serves the excluding searches where it applies (same scores; the cost of "
+                        "plain searches at k instead of searches at k + the largest image's rows)")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -183,7 +186,8 @@ def main(argv: Optional[List[str]] = None) -> None:
                               frame_size=tuple(args.frame_size) if args.frame_size else None,
                               window_stride=args.window_stride, f_mem_p=args.f_mem_p, l_mem_p=args.l_mem_p,
                               **({"memory_sizes": args.memory_sizes} if args.memory_sizes else {}),
-                              **({"leave_one_out": True, "leave_one_out_images": args.leave_one_out_images} if args.leave_one_out else {}),
+                              **({"leave_one_out": True, "leave_one_out_images": args.leave_one_out_images, "leave_one_out_screen": args.leave_one_out_screen}
+                                 if args.leave_one_out else {}),
                               **({"grid_k": args.grid_k, "grid_beta": args.grid_beta} if args.grid_k or args.grid_beta else {}))
     from hbird_mi import hbird_eval as _he
     by_size = grid = grid_by_size = None

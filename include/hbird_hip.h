@@ -108,6 +108,9 @@ int hb_index_gather_labels(hb_index_t* ix, const int64_t* ids, int64_t n, int64_
  * hb_exclude_filter, hb_index_last_exclusion, hb_exclude_plan_replay -- are declared in hbird_hip_exclude.h, which this header includes at its end. */
 /* The read-out of the fp16 screen's last candidate pass -- hb_index_last_screen: lists, pass scores and first certificates, for tests of the
  * candidate kernel -- is declared in hbird_hip_screen.h, which this header includes at its end. */
+/* Excluding searches served by that screen -- hb_index_set_exclude_screen, hb_index_last_exclusion_screen, hb_index_exclude_rerank: the query's
+ * group is dropped among the candidates of a plain search at k, under the unchanged certificate -- are declared in hbird_hip_exclude_screen.h,
+ * which this header includes at its end. */
 /* Sub-bank views -- hb_index_add_from, hb_index_select_rows: an index out of selected rows of another one, gathered on the device -- are
  * declared in hbird_hip_select.h, which this header includes at its end. */
 /* Multi-GPU aggregation tables: borrow device arrays labels[n, c] / norms[n] that cover the GLOBAL id range
@@ -448,6 +451,7 @@ int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, i
 #include "hbird_hip_grid.h"
 #include "hbird_hip_exclude.h"
 #include "hbird_hip_screen.h"
+#include "hbird_hip_exclude_screen.h"
 
 #ifdef __cplusplus
 }

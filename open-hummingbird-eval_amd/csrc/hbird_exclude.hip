@@ -171,56 +171,18 @@ extern "C" int hb_index_last_exclusion(const hb_index_t* ix, int64_t out[4]) {
     return 0;
 }
 
-extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, const int32_t* qgroups,
-                                         int64_t* out_idx, float* out_dist, int io_on_device) {
-    if (!ix) return hb_fail("hb_index_search_excluding: NULL index handle");
-    if (nq < 0) return hb_fail("hb_index_search_excluding: negative query count");
-    if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search_excluding: k must be in [1, " + std::to_string(HB_MAX_K) + "]");
-    if (ix->row_groups_n == 0) return hb_fail("hb_index_search_excluding: the index has no row-group table (hb_index_set_row_groups)");
-    if (ix->row_groups_n != ix->ntotal)
-        return hb_fail("hb_index_search_excluding: the row-group table covers " + std::to_string(ix->row_groups_n) + " rows, the bank holds " +
-                       std::to_string(ix->ntotal) + " (rows were added or removed since hb_index_set_row_groups: set the table again)");
-    int rungs[2] = {0, 0};
-    const int n_rungs = hb_exclude_plan_replay(k, ix->gmax, rungs, 2);      // (need > HB_MAX_K: its message names k, gmax, the limit and the remedy)
-    if (n_rungs < 0) return -1;
-    if (nq == 0) return 0;
-    if (!q || !qgroups || !out_idx || !out_dist) return hb_fail("hb_index_search_excluding: NULL pointer");
-    if (!io_on_device)
-        for (int64_t i = 0; i < nq; ++i)
-            if (qgroups[i] < -1 || qgroups[i] >= ix->n_groups)
-                return hb_fail("hb_index_search_excluding: query " + std::to_string(i) + " names group " + std::to_string(qgroups[i]) + ", outside [-1, " +
-                               std::to_string(ix->n_groups) + ")");
-    hb_range range("hbird:search_excluding");
-    HB_HIP(hipSetDevice(ix->device));
-    hipStream_t s = ix->stream;
+// The rung route on device pointers: rung 0 at rungs[0] into the workspace's lists, the filter, and rung 1 on the queries it left incomplete.
+// ws: exclude_rungs_bytes(nq, rungs[0]) bytes -- [flags: incomplete count | 256 B] [complete, nq] [rung 0's lists]; rung 1 sizes ix->excl1 once
+// its queries are counted.  Writes last_excl.
+static size_t exclude_rungs_bytes(int64_t nq, int kf0) { return 256 + al256((size_t)nq * 4) + al256((size_t)nq * kf0 * 8) + al256((size_t)nq * kf0 * 4); }
+static int exclude_rungs(hb_index* ix, const float* qd, int64_t nq, int k, int64_t id_base, const int32_t* qgd, int64_t* d_oi, float* d_od,
+                         const int* rungs, int n_rungs, char* ws, hipStream_t s) {
     const int kf0 = rungs[0];
-    // workspace: [flags: incomplete count, bad-group flag | 256 B] [complete, nq] [queries, qgroups, idx, dist (host path)] [rung 0's lists]
-    const size_t b_flag = 256, b_comp = al256((size_t)nq * 4);
-    const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4), b_qg = io_on_device ? 0 : al256((size_t)nq * 4);
-    const size_t b_oi = io_on_device ? 0 : al256((size_t)nq * k * 8), b_od = io_on_device ? 0 : al256((size_t)nq * k * 4);
-    const size_t b_li = al256((size_t)nq * kf0 * 8), b_ld = al256((size_t)nq * kf0 * 4);
-    if (ix->excl.ensure(b_flag + b_comp + b_q + b_qg + b_oi + b_od + b_li + b_ld, HB_GROW_EXACT)) return -1;
-    char* cur = ix->excl;
-    int32_t* flags = reinterpret_cast<int32_t*>(cur); cur += b_flag;
-    int32_t* complete = reinterpret_cast<int32_t*>(cur); cur += b_comp;
-    const float* qd = q; const int32_t* qgd = qgroups; int64_t* d_oi = out_idx; float* d_od = out_dist;
-    if (!io_on_device) {
-        HB_HIP(hipMemcpyAsync(cur, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice, s)); qd = reinterpret_cast<const float*>(cur); cur += b_q;
-        HB_HIP(hipMemcpyAsync(cur, qgroups, (size_t)nq * 4, hipMemcpyHostToDevice, s)); qgd = reinterpret_cast<const int32_t*>(cur); cur += b_qg;
-        d_oi = reinterpret_cast<int64_t*>(cur); cur += b_oi;
-        d_od = reinterpret_cast<float*>(cur); cur += b_od;
-    }
-    int64_t* l_idx = reinterpret_cast<int64_t*>(cur); cur += b_li;
-    float* l_dist = reinterpret_cast<float*>(cur);
+    int32_t* flags = reinterpret_cast<int32_t*>(ws);
+    int32_t* complete = reinterpret_cast<int32_t*>(ws + 256);
+    int64_t* l_idx = reinterpret_cast<int64_t*>(ws + 256 + al256((size_t)nq * 4));
+    float* l_dist = reinterpret_cast<float*>(ws + 256 + al256((size_t)nq * 4) + al256((size_t)nq * kf0 * 8));
     HB_HIP(hipMemsetAsync(flags, 0, 8, s));
-    if (io_on_device) {      // device query groups: one small launch and a flag read, before anything is searched or written
-        exclude_check_qgroups_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(qgd, nq, ix->n_groups, flags + 1);
-        HB_HIP(hipGetLastError());
-        int32_t bad = 0;
-        HB_HIP(hipMemcpyAsync(&bad, flags + 1, 4, hipMemcpyDeviceToHost, s));
-        HB_HIP(hipStreamSynchronize(s));
-        if (bad) return hb_fail("hb_index_search_excluding: a query names a group outside [-1, " + std::to_string(ix->n_groups) + ")");
-    }
     // the missing-neighbour value of the search these lists come from
     const float pad = (ix->metric == HB_METRIC_L2 && !ix->score_output) ? INFINITY : -INFINITY;
     ix->last_excl[0] = 1; ix->last_excl[1] = 0; ix->last_excl[2] = kf0; ix->last_excl[3] = ix->gmax;
@@ -257,6 +219,125 @@ extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t
             ix->last_excl[0] = 2; ix->last_excl[1] = n1; ix->last_excl[2] = kf1;
         }
     }
+    return 0;
+}
+
+// The queries `left` (ascending) that the screen could not certify, through the rungs: compacted, gathered, searched, scattered into the outputs.
+static int exclude_rungs_on(hb_index* ix, const std::vector<int64_t>& left, const float* qd, int64_t nq, int k, int64_t id_base, const int32_t* qgd,
+                            int64_t* d_oi, float* d_od, const int* rungs, int n_rungs, hipStream_t s) {
+    const int64_t n = (int64_t)left.size();
+    // [rows, n] [complete, nq] [their groups] [their query rows] [their lists] [the rungs' workspace]
+    const size_t o_comp = al256((size_t)n * 8), o_qg = o_comp + al256((size_t)nq * 4), o_q = o_qg + al256((size_t)n * 4),
+                 o_oi = o_q + al256((size_t)n * ix->d * 4), o_od = o_oi + al256((size_t)n * k * 8), o_ws = o_od + al256((size_t)n * k * 4);
+    if (ix->excl_sub.ensure(o_ws + exclude_rungs_bytes(n, rungs[0]), HB_GROW_EXACT)) return -1;
+    int64_t* rows = ix->excl_sub.as<int64_t>();
+    int32_t* complete = ix->excl_sub.as<int32_t>(o_comp);
+    int32_t* qg = ix->excl_sub.as<int32_t>(o_qg);
+    float* q1 = ix->excl_sub.as<float>(o_q);
+    int64_t* oi = ix->excl_sub.as<int64_t>(o_oi);
+    float* od = ix->excl_sub.as<float>(o_od);
+    std::vector<int32_t> done((size_t)nq, 1);
+    for (int64_t i : left) done[(size_t)i] = 0;
+    HB_HIP(hipMemcpyAsync(complete, done.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    exclude_compact_kernel<<<dim3(1), dim3(256), 0, s>>>(complete, qgd, nq, rows, qg);
+    HB_HIP(hipGetLastError());
+    if (hb_launch_gather_rows(qd, nq, ix->d, rows, n, q1, s)) return -1;
+    HB_HIP(hipStreamSynchronize(s));      // (`done` goes out of use)
+    if (exclude_rungs(ix, q1, n, k, id_base, qg, oi, od, rungs, n_rungs, ix->excl_sub.as<char>(o_ws), s)) return -1;
+    return hb_launch_scatter_rows(rows, n, k, oi, od, d_oi, d_od, s);
+}
+
+extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, const int32_t* qgroups,
+                                         int64_t* out_idx, float* out_dist, int io_on_device) {
+    if (!ix) return hb_fail("hb_index_search_excluding: NULL index handle");
+    if (nq < 0) return hb_fail("hb_index_search_excluding: negative query count");
+    if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search_excluding: k must be in [1, " + std::to_string(HB_MAX_K) + "]");
+    if (ix->row_groups_n == 0) return hb_fail("hb_index_search_excluding: the index has no row-group table (hb_index_set_row_groups)");
+    if (ix->row_groups_n != ix->ntotal)
+        return hb_fail("hb_index_search_excluding: the row-group table covers " + std::to_string(ix->row_groups_n) + " rows, the bank holds " +
+                       std::to_string(ix->ntotal) + " (rows were added or removed since hb_index_set_row_groups: set the table again)");
+    int rungs[2] = {0, 0};
+    const int n_rungs = hb_exclude_plan_replay(k, ix->gmax, rungs, 2);      // (need > HB_MAX_K: its message names k, gmax, the limit and the remedy)
+    if (n_rungs < 0) return -1;
+    if (nq == 0) return 0;
+    if (!q || !qgroups || !out_idx || !out_dist) return hb_fail("hb_index_search_excluding: NULL pointer");
+    if (!io_on_device)
+        for (int64_t i = 0; i < nq; ++i)
+            if (qgroups[i] < -1 || qgroups[i] >= ix->n_groups)
+                return hb_fail("hb_index_search_excluding: query " + std::to_string(i) + " names group " + std::to_string(qgroups[i]) + ", outside [-1, " +
+                               std::to_string(ix->n_groups) + ")");
+    hb_range range("hbird:search_excluding");
+    HB_HIP(hipSetDevice(ix->device));
+    hipStream_t s = ix->stream;
+    // Does the certified fp16 screen get the search (hb_index_set_exclude_screen; include/hbird_hip_exclude_screen.h)?  What can be told here;
+    // whether the index's own choice for (nq, k) is the candidate pass is the search's decision (hb_launch_knn_excluding).
+    int why_not = HB_EXCL_SCREEN_SERVED;
+    if (!ix->excl_screen) why_not = HB_EXCL_SCREEN_OFF;
+    else if (k > 128) why_not = HB_EXCL_SCREEN_K;
+    else if ((int64_t)k + ix->gmax <= 128) why_not = HB_EXCL_SCREEN_NEED;
+    else if (ix->fp16 == 0) why_not = HB_EXCL_SCREEN_PATH;
+    else if (ix->ntotal == 0) why_not = HB_EXCL_SCREEN_EMPTY;
+    const bool try_screen = why_not == HB_EXCL_SCREEN_SERVED;
+    // workspace: [bad-group flag | 256 B] [queries, qgroups, idx, dist (host path)] [the rungs' workspace (where the screen is not tried)]
+    const size_t b_flag = 256;
+    const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4), b_qg = io_on_device ? 0 : al256((size_t)nq * 4);
+    const size_t b_oi = io_on_device ? 0 : al256((size_t)nq * k * 8), b_od = io_on_device ? 0 : al256((size_t)nq * k * 4);
+    const size_t b_head = b_flag + b_q + b_qg + b_oi + b_od, b_rungs = exclude_rungs_bytes(nq, rungs[0]);
+    if (ix->excl.ensure(b_head + (try_screen ? 0 : b_rungs), HB_GROW_EXACT)) return -1;
+    const float* qd = q; const int32_t* qgd = qgroups; int64_t* d_oi = out_idx; float* d_od = out_dist;
+    auto carve = [&]() {      // (again after the buffer has moved)
+        if (io_on_device) return;
+        char* cur = ix->excl.as<char>(b_flag);
+        qd = reinterpret_cast<const float*>(cur); cur += b_q;
+        qgd = reinterpret_cast<const int32_t*>(cur); cur += b_qg;
+        d_oi = reinterpret_cast<int64_t*>(cur); cur += b_oi;
+        d_od = reinterpret_cast<float*>(cur);
+    };
+    carve();
+    if (!io_on_device) {
+        HB_HIP(hipMemcpyAsync(const_cast<float*>(qd), q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice, s));
+        HB_HIP(hipMemcpyAsync(const_cast<int32_t*>(qgd), qgroups, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    }
+    if (io_on_device) {      // device query groups: one small launch and a flag read, before anything is searched or written
+        int32_t* flags = ix->excl.as<int32_t>();
+        HB_HIP(hipMemsetAsync(flags, 0, 8, s));
+        exclude_check_qgroups_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(qgd, nq, ix->n_groups, flags + 1);
+        HB_HIP(hipGetLastError());
+        int32_t bad = 0;
+        HB_HIP(hipMemcpyAsync(&bad, flags + 1, 4, hipMemcpyDeviceToHost, s));
+        HB_HIP(hipStreamSynchronize(s));
+        if (bad) return hb_fail("hb_index_search_excluding: a query names a group outside [-1, " + std::to_string(ix->n_groups) + ")");
+    }
+    hb_excl_screen_result res;
+    if (try_screen) {
+        if (hb_launch_knn_excluding(ix, qd, nq, k, id_base, qgd, d_oi, d_od, &res)) return -1;
+        if (!res.served) why_not = HB_EXCL_SCREEN_PATH;
+    }
+    for (int i = 0; i < 8; ++i) ix->last_excl_screen[i] = 0;
+    ix->last_excl_screen[1] = why_not;
+    if (!res.served) {
+        if (try_screen) {      // the screen declined: the rungs' workspace after all, behind the staged inputs
+            if (ix->excl.ensure_keep(b_head + b_rungs, HB_GROW_EXACT, b_head, s)) return -1;
+            carve();
+        }
+        if (exclude_rungs(ix, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, ix->excl.as<char>(b_head), s)) return -1;
+    } else {
+        // The rungs of the leftover are searches of their own; what describes THIS search is its level-0 pass, and the adaptive fp16 policy is left
+        // as that pass' choice left it (an excluding search's failures say nothing about plain searches)
+        const int path0 = ix->last_path, reason0 = ix->last_reason, centred0 = ix->last_centred;
+        const int64_t escalated0 = ix->last_fp16_escalated;
+        const hb_f16_adapt adapt0 = ix->f16_adapt;
+        const int64_t n_left = (int64_t)res.left.size();
+        ix->last_excl[0] = 0; ix->last_excl[1] = 0; ix->last_excl[2] = 0; ix->last_excl[3] = ix->gmax;
+        int rc = 0;
+        if (n_left > 0) rc = exclude_rungs_on(ix, res.left, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, s);
+        ix->last_path = path0; ix->last_reason = reason0; ix->last_centred = centred0;
+        ix->last_fp16_escalated = escalated0; ix->last_fp16_fallbacks = n_left;
+        ix->f16_adapt = adapt0;
+        if (rc) return -1;
+        int64_t* o = ix->last_excl_screen;
+        o[0] = 1; o[2] = res.kc; o[3] = res.certified0; o[4] = res.sent1; o[5] = res.certified1; o[6] = n_left; o[7] = res.centred;
+    }
     if (!io_on_device) {
         HB_HIP(hipMemcpyAsync(out_idx, d_oi, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
         HB_HIP(hipMemcpyAsync(out_dist, d_od, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
@@ -264,3 +345,4 @@ extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t
     }
     return 0;
 }
+

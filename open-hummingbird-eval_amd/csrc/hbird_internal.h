@@ -124,6 +124,10 @@ struct hb_index {
     hb_dev<char> excl;                                   // workspace of an excluding search: staging, rung 0's lists, flags ...
     hb_dev<char> excl1;                                  // ... and of its rung 1 (sized once the incomplete queries are counted)
     int64_t last_excl[4] = {0, 0, 0, 0};                 // {rungs run, queries sent to rung 1, kf of the last rung run, gmax}
+    // ... on the certified fp16 screen (hb_index_set_exclude_screen, hbird_exclude_screen.hip): the re-rank drops the query's group among the candidates
+    int excl_screen = 0;                                 // the setting: 0 = the rungs serve every excluding search (default), 1 = the screen where it applies
+    int64_t last_excl_screen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hb_index_last_exclusion_screen's slots
+    hb_dev<char> excl_sub;                               // the queries the screen left to the rungs: their rows, groups, query rows and lists
     // a lazy copy or a table goes together with the counters that describe it (the caller has synchronised the stream where work may still read it)
     void drop_tiles16() { tiles16.drop(); f16_rows = 0; f16_cap_rows = 0; }
     void drop_rows32() { rows32.drop(); rows32_cap_rows = 0; rows32_rows = 0; }
@@ -196,6 +200,20 @@ int hb_launch_aggregate_grid(const hb_index* ix, const float* qnorm, const int64
 int hb_launch_exclude_filter(const int64_t* idx, const float* dist, int64_t nq, int k_list, int64_t id_base, const int32_t* groups, int64_t n_rows,
                              const int32_t* qgroups, int k, float pad, int64_t* out_idx, float* out_dist, int32_t* complete_opt, int32_t* incomplete_opt,
                              hipStream_t s);
+// the excluding form of the screen's re-rank, from the fragment tiles, and the gather of the re-searched queries' groups (hbird_exclude_screen.hip)
+int hb_launch_excl_screen_rerank(const hb_rerank_args& a, const float* tiles, int g8, const int32_t* groups, int64_t n_group_rows, const int32_t* qgroups,
+                                 hipStream_t s);
+int hb_launch_gather_groups(const int32_t* src, int64_t n_src, const int64_t* ids, int64_t n, int32_t* out, hipStream_t s);
+// One excluding search at k on the screen (hbird_knn.hip): the candidate pass of a plain search at k, the excluding re-rank, the second pass for
+// what fails.  What both levels leave uncertified comes back in `left` (ascending query numbers) for the rungs; their output rows hold no result.
+// served == 0: the index's own choice for (nq, k) is not the candidate pass -- nothing was searched or written.
+struct hb_excl_screen_result {
+    int served = 0, kc = 0, centred = 0;
+    int64_t certified0 = 0, sent1 = 0, certified1 = 0;
+    std::vector<int64_t> left;
+};
+int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, const int32_t* qgroups, int64_t* out_idx, float* out_dist,
+                            hb_excl_screen_result* res);
 int hb_launch_patch_label_hist(const int64_t* y, int64_t B, int H, int W, int ps, int C, int map255, float* out,
                                hipStream_t s);
 int hb_launch_normalize_rows(const float* x, int64_t n, int d, float* out, hipStream_t s);

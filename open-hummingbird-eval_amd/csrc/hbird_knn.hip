@@ -614,6 +614,11 @@ struct knn_call {
     bool timed = false;                // events around the kernel launches, workgroup stamps, last_knn_ms
     const float* q_aux = nullptr;      // [nq] chain ||q||^2 and [nq] fp32 norms of THIS call's queries
     bool score_out = false;            // the ordering score goes out as it is, whatever the metric
+    // an excluding search on the screen (hb_launch_knn_excluding): per query the row group its re-rank drops among the candidates (nullptr: a
+    // plain search), where the levels report, and (second pass) the caller's query number of each of this call's queries
+    const int32_t* groups = nullptr;
+    hb_excl_screen_result* excl = nullptr;
+    const int64_t* excl_orig = nullptr;
 };
 static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
 
@@ -956,8 +961,15 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     const size_t o_rows = lv.o_rows;
     // the second pass needs k' = 256 > the first one's, a bank worth a candidate pass, and is not repeated
     const bool again16 = esc == 0 && ix->fp16_escalation == 0 && p.kc < 256 && ix->ntotal >= 4096;
+    // An excluding search: a floor-seeded fp32 search knows nothing of groups, so what the second pass cannot take is handed back to the caller
+    // (hb_index_search_excluding: the rungs, on these queries only)
+    if (c.groups && !again16) {
+        for (int64_t b : bad) c.excl->left.push_back(c.excl_orig ? c.excl_orig[b] : b);
+        return 0;
+    }
     const size_t o_q = o_rows + al256((size_t)nf * 8), o_aux = o_q + al256((size_t)nf * ix->d * 4), o_seed = o_aux + al256((size_t)nf * 8),
-                 o_idx = o_seed + al256((size_t)nf * 4), o_dist = o_idx + al256((size_t)nf * k * 8), tot2 = o_dist + al256((size_t)nf * k * 4);
+                 o_idx = o_seed + al256((size_t)nf * 4), o_dist = o_idx + al256((size_t)nf * k * 8), o_qg = o_dist + al256((size_t)nf * k * 4),
+                 tot2 = o_qg + (c.groups ? al256((size_t)nf * 4) : 0);
     if (fbuf.ensure_keep(tot2, HB_GROW_QUARTER, o_rows, s)) return -1;      // (kept: the certificates and the seeds of this level)
     const float *kth = lv.kth(), *flo = lv.flo();      // (after the move)
     int64_t* d_rows = fbuf.as<int64_t>(o_rows);
@@ -984,10 +996,17 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     knn_call nested;
     nested.esc = again16 ? 1 : 2; nested.seed = d_seed;
     nested.fp16 = again16 ? 1 : 0; nested.timed = false; nested.q_aux = d_aux; nested.score_out = c.score_out;
+    if (c.groups) {      // (again16) the second pass drops the same groups: gathered with the queries
+        int32_t* d_qg = fbuf.as<int32_t>(o_qg);
+        if (!rc) rc = hb_launch_gather_groups(c.groups, nq, d_rows, nf, d_qg, s);
+        nested.groups = d_qg; nested.excl = c.excl; nested.excl_orig = bad.data();
+        c.excl->sent1 = nf;
+    }
     if (!again16) ix->last_fp16_fallbacks = nf;
     if (again16) ix->screen.state = HB_SCREEN_OVERWRITTEN;      // (the second pass merges into ix->cand)
     if (!rc) rc = knn_search(ix, nested, d_q, nf, k, id_base, d_fi, d_fd);
-    if (esc == 0) { ix->last_fp16_escalated = nf; hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks); }
+    if (esc == 0) ix->last_fp16_escalated = nf;
+    if (esc == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks);      // (an excluding search's failures say nothing about plain ones)
     if (rc) return -1;
     if (hb_launch_scatter_rows(d_rows, nf, k, d_fi, d_fd, out_idx, out_dist, s)) return -1;
     HB_HIP(hipStreamSynchronize(s));         // `bad` and the workspace are reused by the next call
@@ -1033,7 +1052,9 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     const hb_rerank_args ra{ix->binit, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax, cert, kc, nq, k, id_base, ix->metric, out_metric,
                             ix->ntotal, out_idx, out_dist, hb_rerank_seeds{esc == 1 ? c.seed : nullptr, kth, flo}, cview};
     const bool row_copy = ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal;
-    if (hb_launch_rerank(ra, ix->tiles, ix->g8, row_copy ? ix->rows32 : nullptr, ix->rows32_rs, s)) return -1;
+    // an excluding search: the re-rank that drops every query's group among its candidates (hbird_exclude_screen.hip; from the tiles)
+    if (c.groups ? hb_launch_excl_screen_rerank(ra, ix->tiles, ix->g8, ix->row_groups, ix->row_groups_n, c.groups, s)
+                 : hb_launch_rerank(ra, ix->tiles, ix->g8, row_copy ? ix->rows32 : nullptr, ix->rows32_rs, s)) return -1;
     if (knn_read_time(ix, c)) return -1;
     // Queries whose certificate failed are searched again.  ESCALATION (round 6): first by a second fp16 pass with k' = 256 candidates
     // (the certificate compares the exact k-th best with the fp16 score of rank k': four times the ranks apart) whose pools start from
@@ -1049,7 +1070,11 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     const int64_t nf = (int64_t)bad.size();
     if (esc == 0) { ix->screen.nq = nq; ix->screen.kc = kc; ix->screen.klw = klw; ix->screen.centred = centred ? 1 : 0; ix->screen.state = HB_SCREEN_VALID; }      // (cand and the certificates are complete: the stream is idle)
     if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
-    if (esc == 0 && nf == 0) hb_f16_observe(ix->f16_adapt, path.how16, nq, 0, 0);
+    if (esc == 0 && nf == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, 0, 0);
+    if (c.groups) {
+        if (esc == 0) { c.excl->served = 1; c.excl->kc = kc; c.excl->centred = centred ? 1 : 0; c.excl->certified0 = nq - nf; }
+        else c.excl->certified1 = nq - nf;
+    }
     if (nf > 0 && knn_research_failures(ix, c, path, p, wl, ws, bad, q_dev, nq, k, id_base, out_idx, out_dist, s)) return -1;
     return 0;
 }
@@ -1099,6 +1124,11 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     if (knn_choose_path(ix, c, nq, k, &path)) return -1;
     if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_screen_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;
     path.centred = path.f16 && ix->fp16_centre && ix->centre.active;
+    if (c.groups && !path.f16) {      // an excluding search goes where a plain search at (nq, k) takes the candidate pass, and nowhere else
+        if (esc != 0) return hb_fail("hb_index_search_excluding: the second pass of an excluding search left the fp16 screen");
+        c.excl->served = 0;
+        return 0;
+    }
     if (esc == 0) { ix->last_path = !path.f16 ? HB_PATH_FP32 : path.wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = path.why; ix->last_centred = path.centred ? 1 : 0; }
     if (nq == 0) return 0;
     // score output (sharded searches): the ordering score goes out as it is, whatever the metric
@@ -1136,5 +1166,20 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
 int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
     knn_call c;
     c.fp16 = ix->fp16; c.timed = ix->time_kernels != 0; c.q_aux = ix->q_aux; c.score_out = ix->score_output != 0;
+    return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
+}
+
+// An excluding search on the screen (hbird_internal.h): the level-0 call of a plain search at k -- query tiles and norms as hb_index_search
+// prepares them -- with the queries' groups in its context.  The caller has checked 1 <= k <= 128, nq > 0, ntotal > 0 and the group table.
+int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, const int32_t* qgroups, int64_t* out_idx, float* out_dist,
+                            hb_excl_screen_result* res) {
+    const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
+    if (ix->q_tiles.ensure((size_t)nqp * ix->dp * 4, HB_GROW_EXACT)) return -1;
+    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
+    if (hb_launch_rows_to_tiles(q_dev, nq, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, ix->stream)) return -1;
+    if (hb_launch_query_aux(q_dev, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
+    knn_call c;
+    c.fp16 = ix->fp16; c.timed = ix->time_kernels != 0; c.q_aux = ix->q_aux; c.score_out = ix->score_output != 0;
+    c.groups = qgroups; c.excl = res;
     return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
 }

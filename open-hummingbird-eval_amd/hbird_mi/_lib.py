@@ -156,6 +156,15 @@ SIGNATURES_SCREEN = {
     "hb_index_last_screen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
 }
 
+# ... and include/hbird_hip_exclude_screen.h (excluding searches served by the fp16 screen, csrc/hbird_exclude_screen.hip)
+EXCL_SCREEN_REASONS = {0: "served", 1: "off", 2: "k", 3: "need", 4: "path", 5: "empty"}      # HB_EXCL_SCREEN_*
+SIGNATURES_EXCLUDE_SCREEN = {
+    "hb_index_set_exclude_screen": (c_int, [c_void_p, c_int]),
+    "hb_index_last_exclusion_screen": (c_int, [c_void_p, POINTER(c_int64)]),
+    "hb_index_exclude_rerank": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -177,7 +186,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

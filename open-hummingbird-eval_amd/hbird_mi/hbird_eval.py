@@ -176,6 +176,8 @@ class HbirdEvaluation:
             self.index.set_rerank_copy(int(nn_params.get("rerank_copy", 0)))   # 0 automatic (when memory allows), 1 always, 2 never
         if nn_params.get("fp16_centre", False):       # the screen's fp16 copy in its mean-centred form (HipFlatIndex.set_fp16_centre): same results
             self.index.set_fp16_centre(True)
+        if nn_params.get("exclude_screen", False) and isinstance(self.index, HipFlatIndex):   # excluding searches on the fp16 screen: same results
+            self.index.set_exclusion_screen(True)
         self.id_base = 0            # global id of this rank's first bank row
         self.total_rows = 0         # bank rows over all ranks
         self._label_table = None    # all-gathered labels / norms in sharded mode
@@ -638,12 +640,14 @@ class HbirdEvaluation:
                                           n_neighbours=self.n_neighbours if n_neighbours is None else n_neighbours, device=self.device,
                                           beta=self.beta)
         view.nn_method = self.nn_method
-        view.nn_params = {k: self.nn_params[k] for k in ("distance_measure", "use_fp16", "rerank_copy", "fp16_centre") if k in self.nn_params}
+        view.nn_params = {k: self.nn_params[k] for k in ("distance_measure", "use_fp16", "rerank_copy", "fp16_centre", "exclude_screen") if k in self.nn_params}
         if view.nn_params.get("use_fp16", False):
             index.set_fp16(2)
             index.set_rerank_copy(int(view.nn_params.get("rerank_copy", 0)))
         if view.nn_params.get("fp16_centre", False):
             index.set_fp16_centre(True)
+        if view.nn_params.get("exclude_screen", False):
+            index.set_exclusion_screen(True)
         view.augmentation_epoch = self.augmentation_epoch
         view.compress_labels = self.compress_labels
         view.memory_size = memory_size if memory_size is not None else self.memory_size
@@ -707,7 +711,7 @@ class HbirdEvaluation:
             self._row_groups_on_index = True
 
     def evaluate_leave_one_out(self, loader, eval_spatial_resolution: int, n_neighbours=None, betas=None, views=None, ignore_index: int = 255,
-                               max_images: Optional[int] = None, window=None) -> Dict[tuple, float]:
+                               max_images: Optional[int] = None, window=None, screen: Optional[bool] = None) -> Dict[tuple, float]:
         """`evaluate_grid` of the bank ON ITS OWN TRAINING IMAGES: `loader` yields the bank's images in the order of the build pass (the
         project's data modules do: shuffle=False), the i-th image seen queries with group i, and every search excludes the bank rows of the
         query's own image (`search_aggregate_grid_excluding`) -- so (k, beta, memory size) can be chosen without touching the validation split.
@@ -715,6 +719,9 @@ class HbirdEvaluation:
         image by image, the bank is replaced by its `memory_view(rows=all rows but that image's)`.
         `views={key: HbirdEvaluation}`: the `memory_view`s of this bank (they carry their rows' images).  `max_images`: stop after that many
         images (the cost control).  -> {(k, beta): mIoU}, with `views` {(key, k, beta): mIoU}.
+        `screen`: True / False switches excluding searches on the certified fp16 screen (`HipFlatIndex.set_exclusion_screen`) on / off on every
+        bank of the pass, None leaves the indexes as they are; same floats either way.  `self.loo_screen_served` counts the pass's searches
+        (batch x bank) that the screen served.
         ValueError when more images arrive than the bank was built from, for a bank without geometry (`row_groups`), under torch.distributed,
         with a multi-GPU index and with `window=`."""
         from hbird_mi.nn.search_hip import grid_plan
@@ -738,6 +745,9 @@ class HbirdEvaluation:
             with torch.cuda.device(self.gpu_device):
                 ev.index.use_current_stream()
                 ev._groups_to_index()
+                if screen is not None:
+                    ev.index.set_exclusion_screen(bool(screen))
+        self.loo_screen_served = 0
         plan = grid_plan(self.n_neighbours if n_neighbours is None else n_neighbours, self.beta if betas is None else betas)
         metrics = {key: [PredsmIoU(self.num_classes, self.num_classes, ignore_index=ignore_index, device=self.gpu_device,
                                    store_reordered_preds=False) for _ in plan.configs] for key in banks}
@@ -764,6 +774,7 @@ class HbirdEvaluation:
                 for key, ev in banks.items():
                     ev.index.use_current_stream()
                     lh = ev.index.search_aggregate_grid_excluding(q, plan.ks, plan.betas, qgroups, id_base=0)
+                    self.loo_screen_served += ev.index.last_exclusion_screen()["served"]
                     for i, m in enumerate(metrics[key]):
                         m.update_from_label_hat(y, lh[i].view(B, N, -1), S)
         out = {}
@@ -1118,7 +1129,8 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      train_fs_path: Optional[str] = None, val_fs_path: Optional[str] = None,
                      frame_size: Optional[Tuple[int, int]] = None, window_stride: Optional[int] = None,
                      f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, grid_k=None, grid_beta=None,
-                     leave_one_out: bool = False, leave_one_out_images: Optional[int] = None, memory_sizes=None):
+                     leave_one_out: bool = False, leave_one_out_images: Optional[int] = None,
+                     leave_one_out_screen: bool = False, memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -1136,7 +1148,8 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     return_knn_details or torch.distributed (ValueError).
     `leave_one_out=True`: the scores come from the TRAIN loader instead of the validation loader -- every training image queries the bank
     with its own rows excluded (`HbirdEvaluation.evaluate_leave_one_out`), so n_neighbours, the temperature and the memory size can be chosen
-    without tuning on the validation split; `leave_one_out_images=N` stops after N images.  The return shape is that of the call it
+    without tuning on the validation split; `leave_one_out_images=N` stops after N images; `leave_one_out_screen=True` lets the certified fp16 screen
+    serve the excluding searches (`HipFlatIndex.set_exclusion_screen`: same scores, the cost of plain searches at k).  The return shape is that of the call it
     accompanies: a float, {(k, beta): mIoU} with a grid, {size: ...} with `memory_sizes`.  Same restrictions as the grid."""
     if leave_one_out and (return_knn_details or frame_size is not None):
         raise ValueError("leave_one_out is not available with return_knn_details or sliding windows (frame_size)")
@@ -1179,7 +1192,8 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     if leave_one_out:
         gridded = grid_k is not None or grid_beta is not None
         loo = dict(n_neighbours=grid_k if grid_k is not None else n_neighbours, betas=grid_beta if grid_beta is not None else evaluator.beta,
-                   ignore_index=effective_ignore, max_images=leave_one_out_images)
+                   ignore_index=effective_ignore, max_images=leave_one_out_images,
+                   screen=True if leave_one_out_screen else None)
         if memory_sizes is None:
             res = evaluator.evaluate_leave_one_out(train_loader, eval_spatial_resolution, **loo)
             return res if gridded else next(iter(res.values()))

@@ -384,6 +384,32 @@ class HipFlatIndex:
         _lib.check(_lib.lib().hb_index_last_exclusion(self._h, out))
         return {"rungs": int(out[0]), "rung1_queries": int(out[1]), "kf": int(out[2]), "gmax": int(out[3])}
 
+    def set_exclusion_screen(self, on: bool = True):
+        """Excluding searches on the certified fp16 screen (hb_index_set_exclude_screen, include/hbird_hip_exclude_screen.h): where k <= 128,
+        k + (largest group) > 128 and the index's own choice for a plain search at k is the candidate pass, the re-rank drops the query's group
+        among the candidates of a search at k -- the cost of a plain search -- and only what fails both certificates goes through the rungs.
+        Same ids and distance bits either way.  Off by default."""
+        _lib.check(_lib.lib().hb_index_set_exclude_screen(self._h, int(bool(on))))
+
+    def last_exclusion_screen(self) -> dict:
+        """Of the last excluding search (hb_index_last_exclusion_screen): served by the screen (0 / 1), the reason when not ("off", "k", "need",
+        "path", "empty"), kc of level 0, queries certified at level 0, sent to and certified at the second pass, sent to the rungs, centred."""
+        out = (ctypes.c_int64 * 8)()
+        _lib.check(_lib.lib().hb_index_last_exclusion_screen(self._h, out))
+        return {"served": int(out[0]), "reason": _lib.EXCL_SCREEN_REASONS.get(int(out[1]), str(int(out[1]))), "kc": int(out[2]),
+                "certified0": int(out[3]), "second_pass": int(out[4]), "certified1": int(out[5]), "rung_queries": int(out[6]), "centred": int(out[7])}
+
+    def exclude_rerank(self, q, cand_rows, pass_scores, qgroups, k: int, id_base: int = 0):
+        """The excluding re-rank kernel alone on given candidate lists (hb_index_exclude_rerank): device tensors q [nq, d] float32, cand_rows
+        [nq, kc] int64 and pass_scores [nq, kc] float32 as `last_screen` hands them out, qgroups [nq] int32.
+        -> (idx [nq, k], dist [nq, k], certified [nq] uint8, kth [nq], floor [nq]).  ValueError where the entry refuses."""
+        nq, kc = cand_rows.shape
+        idx, dist = _new(q, (nq, k), torch.int64), _new(q, (nq, k), torch.float32)
+        cert, kth, flo = _new(q, (nq,), torch.uint8), _new(q, (nq,), torch.float32), _new(q, (nq,), torch.float32)
+        _lib.check(_lib.lib().hb_index_exclude_rerank(self._h, _ptr(q), nq, _ptr(cand_rows), _ptr(pass_scores), int(kc), _ptr(qgroups), int(k),
+                                                      int(id_base), _ptr(idx), _ptr(dist), _ptr(cert), _ptr(kth), _ptr(flo)), ValueError)
+        return idx, dist, cert, kth, flo
+
     def _excluding_lists(self, q, k, qgroups, id_base):
         on_dev, q = self._as_f32(q)
         qd = q if on_dev else torch.from_numpy(q).cuda(self.device)
@@ -1155,6 +1181,7 @@ class HipMultiIndex:
         raise ValueError("HipMultiIndex: excluding searches are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")
 
     set_row_groups = search_excluding = search_aggregate_excluding = search_aggregate_grid_excluding = last_exclusion = _no_exclusion
+    set_exclusion_screen = last_exclusion_screen = _no_exclusion
 
     def select_rows(self, ids):
         raise ValueError("HipMultiIndex.select_rows: views are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")
@@ -1188,6 +1215,7 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
         self.use_fp16 = use_fp16
         self.exact_screen = bool(kwargs.pop("exact_screen", True))     # use_fp16=False: the index's automatic state (True) or the fp32 kernel only (False)
         self.fp16_centre = bool(kwargs.pop("fp16_centre", False))     # the fp16 copy in its mean-centred form (set_fp16_centre): same results, a tighter certificate on ViT-shaped banks
+        self.exclude_screen = bool(kwargs.pop("exclude_screen", False))     # excluding searches on the certified fp16 screen (set_exclusion_screen): same results
         self.rerank_copy = int(kwargs.pop("rerank_copy", 0))     # use_fp16 only: the re-rank's row-major copy of the bank (0 automatic, 1 always, 2 never)
         self.embed_d = feature_memory.size(1)
 
@@ -1232,6 +1260,8 @@ class NearestNeighborSearchHIP(NearestNeighborSearchBase):
             index.set_rerank_copy(self.rerank_copy)
             if self.fp16_centre:
                 index.set_fp16_centre(True)
+            if self.exclude_screen and isinstance(index, HipFlatIndex):
+                index.set_exclusion_screen(True)
         return out
 
     def _add_features_to_index(self, feature_memory):
