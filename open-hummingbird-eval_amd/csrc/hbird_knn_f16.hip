@@ -1,7 +1,7 @@
 // Row f5 of SURVEY.md 8: `use_fp16` (reference hbird/nn/search_faiss.py:7, 40: GpuIndexFlatConfig.useFloat16 --
 // fp16 storage and fp16 GEMM with fp32 accumulation).
 //
-// Here: a CANDIDATE pass on fp16 copies of the bank and query fragment tiles with v_mfma_f32_32x32x16_f16 (16x the
+// Here: a CANDIDATE pass on fp16 copies of the bank and query fragment tiles with v_mfma_f32_16x16x32_f16 (16x the
 // fp32 MFMA rate), fused running top-k' (k' = 64 .. 256 >= 2k) exactly like the fp32 kernel, followed by an EXACT
 // re-rank of the k' candidates in the fp32 chain arithmetic of the fp32 kernel (every score one k-ascending fmaf
 // chain on the fp32 tiles).  Indices and distances are therefore those of the fp32 definition whenever the true
@@ -64,8 +64,8 @@ int hb_launch_tiles_to_f16(const float* t32, int g8, _Float16* t16, int g16, int
 // A wave's query fragment (32 queries x k16 = 1 KiB per group) is read by that wave ONLY: staging it through LDS buys no
 // reuse.  Here it goes straight from global memory into registers (inline-asm global_load_dwordx4, four k32 stages ahead,
 // counted by hand with the copies), which halves the LDS-DMA traffic and drops the ninth fragment read of every group;
-// the ring then holds bank fragments only (8 slots x 16 KiB) and the bank fragments need ONE register set: fragment t is
-// re-loaded right after MFMA t has issued, 8 MFMAs before its next use.  Per group: 64 KiB of reads + 8 KiB of copies.
+// the ring then holds bank fragments only (8 slots x 16 KiB) and the bank fragments need ONE register set: a fragment is
+// re-loaded right after its last MFMA has issued, half a stage before its next use.  Per group: 64 KiB of reads + 8 KiB of copies.
 // Stages are unrolled by four so that the register buffers of the query fragments have static indices.
 //
 // Round 4: the stage loop's SCALAR side.  A model of this loop with the same traffic on random operands
@@ -77,6 +77,16 @@ int hb_launch_tiles_to_f16(const float* t32, int g8, _Float16* t16, int g16, int
 // tile, row-init values) that advance by constants, the copies use the saddr form (wave-uniform base + 32-bit lane offset, M0
 // = wave-uniform LDS address) from inline asm, every wave issues at the same MFMA gaps, the cluster tick sits in the one
 // stage of four that can act, and arguments used only at segment boundaries are re-read from the kernarg segment (HB_KARG).
+//
+// Round 21: the MFMA shape.  The loop is power-limited (the chip holds its clock near 1.55 GHz), so what helps is less energy per FLOP:
+// v_mfma_f32_16x16x32_f16 writes half the accumulator registers per FLOP of v_mfma_f32_32x32x16_f16.  Same wave tile (32 queries x 256
+// rows, 128 accumulator registers), same LDS and L2 bytes: per k32 stage and wave 32 MFMAs = 16 bank fragments (16 rows x k32, one
+// ds_read_b128 each, read once, used twice) x 2 query fragments (16 queries x k32, both live for the whole stage).  The tile layouts in
+// HBM and LDS are those of the 32x32x16 loop ([h][i][8 halves] blocks of k16): an operand lane (c4 = lane >> 4, m16 = lane & 15) takes
+// k-chunk c4 of the stage's k32 from block c4 >> 1, half c4 & 1.  The tile epilogue (hbird_knn_dev.h) is shared with the fp32 kernels and
+// expects the 32x32 output layout: the bank fragments are read through a row permutation rho and one v_permlane16_swap per register pair
+// at a tile's end lands exactly on it (F2_SWAP_TILE; the algebra is enumerated in tests/test_f16_mfma_layout_cpu.py).  Measured on the
+// 10 M x 768 step: 281.7 -> 265.9 ms (1.059x) at 1.80 instead of 1.55 GHz, matrix pipe busy 0.74 -> 0.69 (profiles/r21/README.md).
 #define F2_RING 8
 #define F2_SLOT 16384                                  // bank fragments of one k32 stage: [row tile 0..7][group 0..1][1 KiB]
 #define F2_BINIT (F2_RING * F2_SLOT)
@@ -92,7 +102,21 @@ static_assert(F2_LDS_TOTAL <= 160 * 1024, "LDS budget");
 #define F2_DMA(SRC, LDS_ADDR, VOFF)                                                                                          \
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(VOFF), "s"(SRC), "s"(LDS_ADDR) : "memory", "m0");
 // a query-fragment load into registers (untracked by the compiler: the hand-counted vmcnt below names the registers it releases)
-#define F2_BL(REG, SRC, OFF) asm volatile("global_load_dwordx4 %0, %1, %2 offset:" #OFF : "+v"(REG) : "v"(lane_off), "s"(SRC) : "memory");
+#define F2_BL(REG, SRC, OFF) asm volatile("global_load_dwordx4 %0, %1, %2 offset:" #OFF : "+v"(REG) : "v"(q_off), "s"(SRC) : "memory");
+
+// one 16x16x32 MFMA on quarter Q of a 16-register accumulator (registers 4Q .. 4Q+3: a sub-tuple, no copies)
+template <int Q>
+__device__ __forceinline__ void f2_mm16(f32x16& acc, const f16x8& a, const f16x8& b) {
+    f32x4 c = {acc[4 * Q], acc[4 * Q + 1], acc[4 * Q + 2], acc[4 * Q + 3]};
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    acc[4 * Q] = c[0]; acc[4 * Q + 1] = c[1]; acc[4 * Q + 2] = c[2]; acc[4 * Q + 3] = c[3];
+}
+// v_permlane16_swap_b32 on a register pair: the odd 16-lane rows of x change places with the even rows of y
+template <int X, int Y>
+__device__ __forceinline__ void f2_swap16(f32x16& acc) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[X]), __float_as_uint(acc[Y]), false, false);
+    acc[X] = __uint_as_float(r[0]); acc[Y] = __uint_as_float(r[1]);
+}
 
 // EMAX: pool capacity / 64 that the instantiation can compact (registers of the rare compaction path)
 template <int EMAX>
@@ -101,13 +125,19 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = lane >> 5;
+    const int c4 = lane >> 4, m16 = lane & 15;   // MFMA operand lane: k-chunk c4 (8 halves) of the k32, row / query m16 of the fragment
     float* sc = reinterpret_cast<float*>(smem + F2_SCRATCH) + w * 256;
     int* pcnt = reinterpret_cast<int*>(smem + F2_PCNT);
     const int g16 = a.g16;
     const int NS = g16 / 2;   // k32 stages per bank tile, a multiple of 4 (dp16 is a multiple of 128)
     const int myq = w * 32 + (lane & 31);
     const unsigned lane_off = (unsigned)lane * 16u;
+    // operand offsets inside a stage's two 1 KiB blocks [h][i][8 halves]: chunk c4 is block c4 >> 1, half c4 & 1.  The query fragment
+    // takes query m16 (+ 16 b); the bank fragment takes tile row rho(m16) = 8 ((m16 >> 2) & 1) + 4 (m16 >> 3) + (m16 & 3) (+ 16 f'),
+    // the permutation that lets the lane swap at a tile's end land on the epilogue's layout (see the stage loop)
+    const unsigned q_off = (unsigned)((c4 >> 1) * 1024 + ((c4 & 1) * 32 + m16) * 16);
+    const unsigned a_off = (unsigned)((c4 >> 1) * 1024 + ((c4 & 1) * 32 + 8 * ((m16 >> 2) & 1) + 4 * (m16 >> 3) + (m16 & 3)) * 16);
+    const int ri = 2 * (c4 & 1) + (c4 >> 1);     // row-init quad of this lane's MFMA output rows 4 c4 .. 4 c4 + 3: rho(4 c4) / 4
     const unsigned lds_0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned lds_w = lds_0 + (unsigned)w * 2048u;   // this wave's two pieces of a ring slot
     cl_sync cs = cl_init(a.wg_member, a.prog, a.cl, a.lag, blockIdx.x, w == 0, smem + F2_CLWORDS);
@@ -129,20 +159,19 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
         }
         const int total = seg.n_tiles * NS, clock0 = seg.tile0 * NS;
         f32x16 acc[8];
-        f16x8 fa[8];        // bank fragments of the current group (one set)
-        f16x8 bq[4][2];     // query fragments of four stages, two k16 groups each
+        f16x8 fa[8];        // bank fragments (16 rows x k32) of the current half stage (one set)
+        f16x8 bq[4][2];     // query fragments of four stages, two fragments of 16 queries x k32 each
 
-        // What one wave requests for one stage, in this order: query fragment B0 (group 0 of the stage; registers), two 1 KiB
-        // bank pieces C0, C1 (row tile w, both groups; LDS-DMA) -- all three during group 1 of the stage four earlier -- and
-        // query fragment B1 (group 1) during group 0 of the stage three earlier (its register is free only then).  Wave 0
-        // adds the row-init values behind the first stage of a tile.
+        // What one wave requests for one stage, in this order: two 1 KiB bank pieces C0, C1 (row tile w, both k16 blocks; LDS-DMA)
+        // during the second half of the stage four earlier, and the query fragments B0, B1 (queries 0..15 / 16..31 of the wave, the
+        // whole k32 each; registers) behind that stage's last MFMA: both stay live for the whole stage, so their registers are free
+        // only then.  Wave 0 adds the row-init values behind the first stage of a tile.
         // The fetch position, all wave-uniform: qf / bf / bi point at the NEXT stage to request (this wave's query fragments
-        // [g16][1 KiB]; row tile w of the bank tile: [g16][1 KiB], the next row tile behind it; the tile's row-init values),
-        // qf1 at the stage whose B1 is still to be requested.  A stage advances qf and bf by 2 KiB; at a tile's end qf returns
-        // to the wave's first fragment and bf jumps from the end of row tile w to row tile w of the next tile of the segment.
+        // [g16][1 KiB]; row tile w of the bank tile: [g16][1 KiB], the next row tile behind it; the tile's row-init values).
+        // A stage advances qf and bf by 2 KiB; at a tile's end qf returns to the wave's first fragment and bf jumps from the end
+        // of row tile w to row tile w of the next tile of the segment.
         const char* const qbase = reinterpret_cast<const char*>(a.q16) + (size_t)(seg.q_tile * 8 + w) * g16 * 1024;
         const char* qf = qbase;
-        const char* qf1 = qbase;
         const char* bf = reinterpret_cast<const char*>(a.bank16) + ((size_t)seg.b_tile0 * 8 + w) * g16 * 1024;
         const float* bi = a.binit + (size_t)seg.b_tile0 * HB_BT;
         const long long b_wrap = ((long long)seg.stride * 8 - 1) * g16 * 1024;
@@ -150,77 +179,94 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
         int fks = 0, left = total;
         unsigned slot_f = 0, fpar = 0;        // ring slot being filled (byte offset), parity of the row-init buffer being filled
 #define F2_REQ_B0(U) F2_BL(bq[U][0], qf, 0)
-#define F2_REQ_B1(U) F2_BL(bq[U][1], qf1, 1024)
+#define F2_REQ_B1(U) F2_BL(bq[U][1], qf, 256)
 #define F2_REQ_C(I) F2_DMA(bf, lds_w + slot_f + (I) * 1024u, lane_off + (I) * 1024u)
 #define F2_ADVANCE()                                                                                                         \
         {                                                                                                                    \
             if (fks == 0 && w == 0) F2_DMA(bi, lds_0 + F2_BINIT + fpar, lane_off)                                            \
-            qf1 = qf;                                                                                                        \
             if (--left > 0) {                                                                                                \
                 qf += 2048; bf += 2048;                                                                                      \
                 if (++fks == NS) { fks = 0; qf = qbase; bf += b_wrap; bi += bi_step; fpar ^= 1024u; }                        \
             }                                                                                                                \
             slot_f = (slot_f + F2_SLOT) & (F2_RING * F2_SLOT - 1);                                                           \
         }
-        // vmcnt by hand.  Order of a wave's requests: ... B1(s+3) | B0(s+4) C0 C1 | B1(s+4) | B0(s+5) ... (wave 0: now and
-        // then one more, which only makes a wait stricter).  At the barrier in the middle of stage s everything of stage
-        // s + 1 must have landed; its youngest request is B1(s+1), behind it come B0 C0 C1 (s+2), B1(s+2), B0 C0 C1 (s+3) and
-        // B1(s+3) -> "all but the newest 8".  Past the last stage the fetch position stays put (same requests again, results
-        // unused), so the count never changes.
-        F2_REQ_B0(0) F2_REQ_C(0) F2_REQ_C(1) F2_ADVANCE() F2_REQ_B1(0)
-        F2_REQ_B0(1) F2_REQ_C(0) F2_REQ_C(1) F2_ADVANCE() F2_REQ_B1(1)
-        F2_REQ_B0(2) F2_REQ_C(0) F2_REQ_C(1) F2_ADVANCE() F2_REQ_B1(2)
-        F2_REQ_B0(3) F2_REQ_C(0) F2_REQ_C(1) F2_ADVANCE()
-        // stage 0 (and B1 of it) has landed: eleven younger requests
-        asm volatile("s_waitcnt vmcnt(11)" : "+v"(bq[0][0]), "+v"(bq[0][1]) :: "memory");
+        // vmcnt by hand.  Order of a wave's requests: ... C0 C1 B0 B1 (s+3) | C0 C1 B0 B1 (s+4) ... (wave 0: now and then one more
+        // behind B1, which only makes a wait stricter), all four of stage s + 4 in the second half of stage s.  At the barrier in
+        // the middle of stage s everything of stage s + 1 must have landed; its youngest request is B1(s+1), behind it come C0 C1 B0
+        // B1 (s+2) and C0 C1 B0 B1 (s+3) -> "all but the newest 8".  Past the last stage the fetch position stays put (same requests
+        // again, results unused), so the count never changes.
+        F2_REQ_C(0) F2_REQ_C(1) F2_REQ_B0(0) F2_REQ_B1(0) F2_ADVANCE()
+        F2_REQ_C(0) F2_REQ_C(1) F2_REQ_B0(1) F2_REQ_B1(1) F2_ADVANCE()
+        F2_REQ_C(0) F2_REQ_C(1) F2_REQ_B0(2) F2_REQ_B1(2) F2_ADVANCE()
+        F2_REQ_C(0) F2_REQ_C(1) F2_REQ_B0(3) F2_REQ_B1(3) F2_ADVANCE()
+        // stage 0 has landed: twelve younger requests (C0 C1 B0 B1 of stages 1, 2 and 3)
+        asm volatile("s_waitcnt vmcnt(12)" : "+v"(bq[0][0]), "+v"(bq[0][1]) :: "memory");
         __syncthreads();
         unsigned slot_c = 0;                  // ring slot being computed (byte offset)
         int ks = 0, bt = seg.b_tile0, cpar = 0;
         bool bulk = seg.tile0 < 16;   // loose floors at the start of a search: the epilogue's quarter loop right away (pool_epilogue_scan)
+        // The accumulators are the epilogue's eight 16-register tuples.  While a tile is summed, quarter 2 f' + b of acc[t] is the
+        // 16x16 output of bank fragment f = 2 t + f' (tile rows 32 t + 16 f' + rho(0..15)) x query fragment b: lane (c4, m16) holds
+        // query 16 b + m16, MFMA rows 4 c4 + j.  F2_SWAP_TILE (below) turns that into the epilogue's layout.  The row-init values go
+        // in BEFORE the MFMAs, so in the pre-swap layout: register 8 f' + 4 b + j = row 32 t + 16 f' + rho(4 c4 + j), rho(4 c4 + j) =
+        // 4 ri + j, for b = 0 and 1 alike.
 #define F2_INIT_TILE()                                                                                                       \
         {                                                                                                                    \
             const f32x4* bi_ = reinterpret_cast<const f32x4*>(smem + F2_BINIT + cpar * 1024);                                \
             _Pragma("unroll") for (int t = 0; t < 8; ++t)                                                                    \
-                _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                              \
-                    const f32x4 v = bi_[8 * t + 2 * g + h];                                                                  \
-                    acc[t][4 * g + 0] = v[0]; acc[t][4 * g + 1] = v[1]; acc[t][4 * g + 2] = v[2]; acc[t][4 * g + 3] = v[3]; \
+                _Pragma("unroll") for (int f = 0; f < 2; ++f) {                                                              \
+                    const f32x4 v = bi_[8 * t + 4 * f + ri];                                                                 \
+                    _Pragma("unroll") for (int j = 0; j < 4; ++j) { acc[t][8 * f + j] = v[j]; acc[t][8 * f + 4 + j] = v[j]; } \
                 }                                                                                                            \
         }
+        // After a tile's last stage: one v_permlane16_swap per register pair (quarter 2 f', quarter 2 f' + 1)[j] exchanges the odd
+        // 16-lane rows of the b = 0 register with the even rows of the b = 1 register.  Then lane l holds query l & 31 only, the first
+        // register MFMA row 8 (l >> 5) + j, the second 8 (l >> 5) + 4 + j; with rho those are tile rows 16 f' + 4 h + j and 16 f' + 8 +
+        // 4 h + j: acc[t][4 g + j] = row 32 t + 8 g + 4 h + j, the layout of the 32x32 MFMA that the shared epilogue scans.
+#define F2_SWAP_TILE()                                                                                                       \
+        _Pragma("unroll") for (int t = 0; t < 8; ++t) {                                                                      \
+            f2_swap16<0, 4>(acc[t]); f2_swap16<1, 5>(acc[t]); f2_swap16<2, 6>(acc[t]); f2_swap16<3, 7>(acc[t]);              \
+            f2_swap16<8, 12>(acc[t]); f2_swap16<9, 13>(acc[t]); f2_swap16<10, 14>(acc[t]); f2_swap16<11, 15>(acc[t]);        \
+        }
+        // fragment F = 0 .. 15 of a slot: row tile F >> 1, half tile F & 1
+#define F2_FRAG(BASE, F) (*reinterpret_cast<const f16x8*>((BASE) + ((F) >> 1) * 2048 + ((F) & 1) * 256))
         {
-            const f16x8* A = reinterpret_cast<const f16x8*>(smem) + lane;
+            const char* A = smem + a_off;
 #pragma unroll
-            for (int t = 0; t < 8; ++t) fa[t] = A[(t * 2) * 64];
+            for (int i = 0; i < 8; ++i) fa[i] = F2_FRAG(A, i);
         }
         F2_INIT_TILE()
-#define F2_MM(T, B) acc[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[T], B, acc[T], 0, 0, 0);
+        // fragment F against both query fragments of stage register U (fa[F & 7] feeds two MFMAs)
+#define F2_MM(F, U) f2_mm16<2 * ((F) & 1)>(acc[(F) >> 1], fa[(F) & 7], bq[U][0]); f2_mm16<2 * ((F) & 1) + 1>(acc[(F) >> 1], fa[(F) & 7], bq[U][1]);
 #define F2_STAGE(U)                                                                                                          \
         {                                                                                                                    \
-            const f16x8* Ac = reinterpret_cast<const f16x8*>(smem + slot_c) + lane;                                          \
+            const char* Ac = smem + slot_c + a_off;                                                                          \
             const unsigned slot_n = (slot_c + F2_SLOT) & (F2_RING * F2_SLOT - 1);                                            \
-            const f16x8* An = reinterpret_cast<const f16x8*>(smem + slot_n) + lane;                                          \
-            /* group 0; filler after MFMA t: fragment t of group 1; B1 of the stage three ahead */                           \
-            KN_FENCE F2_MM(0, bq[U][0]) KN_FENCE fa[0] = Ac[(0 * 2 + 1) * 64]; F2_REQ_B1((U + 3) & 3)                           \
-            KN_FENCE F2_MM(1, bq[U][0]) KN_FENCE fa[1] = Ac[(1 * 2 + 1) * 64];                                                  \
-            KN_FENCE F2_MM(2, bq[U][0]) KN_FENCE fa[2] = Ac[(2 * 2 + 1) * 64];                                                  \
-            KN_FENCE F2_MM(3, bq[U][0]) KN_FENCE fa[3] = Ac[(3 * 2 + 1) * 64];                                                  \
-            KN_FENCE F2_MM(4, bq[U][0]) KN_FENCE fa[4] = Ac[(4 * 2 + 1) * 64];                                                  \
-            KN_FENCE F2_MM(5, bq[U][0]) KN_FENCE fa[5] = Ac[(5 * 2 + 1) * 64];                                                  \
-            KN_FENCE F2_MM(6, bq[U][0]) KN_FENCE fa[6] = Ac[(6 * 2 + 1) * 64];                                                  \
-            KN_FENCE F2_MM(7, bq[U][0]) KN_FENCE fa[7] = Ac[(7 * 2 + 1) * 64];                                                  \
+            const char* An = smem + slot_n + a_off;                                                                          \
+            /* fragments 0..7; filler after pair i: fragment 8 + i */                                                        \
+            KN_FENCE F2_MM(0, U) KN_FENCE fa[0] = F2_FRAG(Ac, 8);                                                               \
+            KN_FENCE F2_MM(1, U) KN_FENCE fa[1] = F2_FRAG(Ac, 9);                                                               \
+            KN_FENCE F2_MM(2, U) KN_FENCE fa[2] = F2_FRAG(Ac, 10);                                                              \
+            KN_FENCE F2_MM(3, U) KN_FENCE fa[3] = F2_FRAG(Ac, 11);                                                              \
+            KN_FENCE F2_MM(4, U) KN_FENCE fa[4] = F2_FRAG(Ac, 12);                                                              \
+            KN_FENCE F2_MM(5, U) KN_FENCE fa[5] = F2_FRAG(Ac, 13);                                                              \
+            KN_FENCE F2_MM(6, U) KN_FENCE fa[6] = F2_FRAG(Ac, 14);                                                              \
+            KN_FENCE F2_MM(7, U) KN_FENCE fa[7] = F2_FRAG(Ac, 15);                                                              \
             KN_FENCE                                                                                                         \
             /* the next stage has landed: my requests (and my query fragments of it), then everyone's */                    \
-            asm volatile("s_waitcnt vmcnt(8)" : "+v"(bq[(U + 1) & 3][0]), "+v"(bq[(U + 1) & 3][1]), "+v"(bq[U][1]) :: "memory"); \
+            asm volatile("s_waitcnt vmcnt(8)" : "+v"(bq[(U + 1) & 3][0]), "+v"(bq[(U + 1) & 3][1]) :: "memory");             \
             __builtin_amdgcn_s_barrier();   /* raw s_barrier: __syncthreads() would drain the LDS-DMA copies (vmcnt(0)) */   \
-            /* group 1; filler after MFMA t: fragment t of the next stage's group 0; B0 C0 C1 of the stage four ahead */     \
+            /* fragments 8..15; filler after pair i: fragment i of the next stage; C0 C1 of the stage four ahead, its B0 B1 */ \
+            /* behind the last MFMA that reads the registers they land in */                                                 \
             if ((U) == 0 && w == 0) cl_tick(cs, clock0 + st, lane);   /* cluster soft sync, ahead of the stage's requests; acts when the clock is a multiple of 4: st is, clock0 is (NS is) */ \
-            KN_FENCE F2_MM(0, bq[U][1]) KN_FENCE fa[0] = An[(0 * 2) * 64]; F2_REQ_B0(U)                                         \
-            KN_FENCE F2_MM(1, bq[U][1]) KN_FENCE fa[1] = An[(1 * 2) * 64];                                                      \
-            KN_FENCE F2_MM(2, bq[U][1]) KN_FENCE fa[2] = An[(2 * 2) * 64]; F2_REQ_C(0)                                          \
-            KN_FENCE F2_MM(3, bq[U][1]) KN_FENCE fa[3] = An[(3 * 2) * 64];                                                      \
-            KN_FENCE F2_MM(4, bq[U][1]) KN_FENCE fa[4] = An[(4 * 2) * 64]; F2_REQ_C(1)                                          \
-            KN_FENCE F2_MM(5, bq[U][1]) KN_FENCE fa[5] = An[(5 * 2) * 64];                                                      \
-            KN_FENCE F2_MM(6, bq[U][1]) KN_FENCE fa[6] = An[(6 * 2) * 64];                                                      \
-            KN_FENCE F2_MM(7, bq[U][1]) KN_FENCE fa[7] = An[(7 * 2) * 64];                                                      \
+            KN_FENCE F2_MM(8, U) KN_FENCE fa[0] = F2_FRAG(An, 0);                                                               \
+            KN_FENCE F2_MM(9, U) KN_FENCE fa[1] = F2_FRAG(An, 1);                                                               \
+            KN_FENCE F2_MM(10, U) KN_FENCE fa[2] = F2_FRAG(An, 2); F2_REQ_C(0)                                                  \
+            KN_FENCE F2_MM(11, U) KN_FENCE fa[3] = F2_FRAG(An, 3);                                                              \
+            KN_FENCE F2_MM(12, U) KN_FENCE fa[4] = F2_FRAG(An, 4); F2_REQ_C(1)                                                  \
+            KN_FENCE F2_MM(13, U) KN_FENCE fa[5] = F2_FRAG(An, 5);                                                              \
+            KN_FENCE F2_MM(14, U) KN_FENCE fa[6] = F2_FRAG(An, 6);                                                              \
+            KN_FENCE F2_MM(15, U) KN_FENCE fa[7] = F2_FRAG(An, 7); F2_REQ_B0(U) F2_REQ_B1(U)                                    \
             KN_FENCE                                                                                                         \
             F2_ADVANCE()                                                                                                     \
             KN_FENCE                                                                                                         \
@@ -232,14 +278,15 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
             if (ks == NS) {
                 // a slot's first tile: filter below the k'-th largest of its 256 scores (bisection over the accumulators)
                 // instead of appending all 256 rows of every query through the overflow path
+                F2_SWAP_TILE()
                 if (seg.first && bt == seg.b_tile0 && cold_start_needed(thr)) thr = fmaxf(thr, cold_start_threshold(acc, k));
                 pool_epilogue_scan<EMAX>(acc, thr, wl_s, wl_i, sc, w * 32, lane, k, (unsigned)bt, klw, pcnt, bulk);
                 ks = 0; bt += seg.stride; cpar ^= 1;
                 F2_INIT_TILE()
                 {   // the next tile's first fragments again (rather than kept live across the epilogue: fewer registers)
-                    const f16x8* A = reinterpret_cast<const f16x8*>(smem + slot_c) + lane;
+                    const char* A = smem + slot_c + a_off;
 #pragma unroll
-                    for (int t = 0; t < 8; ++t) fa[t] = A[(t * 2) * 64];
+                    for (int i = 0; i < 8; ++i) fa[i] = F2_FRAG(A, i);
                 }
             }
         }
@@ -248,6 +295,8 @@ __global__ __launch_bounds__(HB_THREADS, 2) void knn_f16v2_kernel(knn16_args a) 
                      "+v"(bq[3][0]), "+v"(bq[3][1]) :: "memory");
 #undef F2_STAGE
 #undef F2_MM
+#undef F2_FRAG
+#undef F2_SWAP_TILE
 #undef F2_INIT_TILE
 #undef F2_ADVANCE
 #undef F2_REQ_B0

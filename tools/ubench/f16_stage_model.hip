@@ -10,6 +10,12 @@
 //      so it is L2-resident like a clustered search)
 //   B  one s_barrier per k32 stage
 // SHAPE 0 = v_mfma_f32_32x32x16_f16, 1 = the same FLOPs as pairs of v_mfma_f32_16x16x32_f16.
+// SHAPE 2 = the 16x16x32 loop as the candidate kernel runs it (QT = 1): per k32 stage 16 bank fragments of 16 rows x k32, each read once
+// (ds_read_b128 at the row-permuted lane offset) and fed to two MFMAs against the stage's two query fragments (16 queries x k32 each, both
+// live for the whole stage, loaded at the permuted lane offset behind the stage's last MFMA), 32 accumulators of 4 registers, and every
+// 24 stages the 64 v_permlane16_swap of a tile's end.  SHAPE 3 = the same with the MFMA order "all 8 fragments against the first query
+// fragment, then all 8 against the second" (the B operand stays put for 8 MFMAs, as it does in the 32x32x16 loop); SHAPE 4 = SHAPE 2 with
+// the fragment reads at the 32x32x16 loop's lane offsets (lane x 16 B: what the row permutation costs, if anything).
 // Variants: NW = 8, QT = 1 (the shipped tile: 2 waves per SIMD, 128 accumulator registers), NW = 4, QT = 2 (one wave per SIMD,
 // 256 accumulators), NW = 4, QT = 3 (384 accumulators: VERDICT r3 item 1b).
 // Prints ms, TFLOP/s, the in-kernel clock (s_memtime / s_memrealtime) and the matrix pipe's busy share.
@@ -35,6 +41,11 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void model(const char* __restrict_
     constexpr int CPW = 8 / NW;                       // LDS-DMA pieces per wave and group
     f32x16 acc[QT][8];
     f32x4 acc4[SHAPE ? QT * 32 : 1];
+    // SHAPE 2: operand lane (c4, m16) = k-chunk c4 of the k32, row rho(m16) of the bank fragment / query m16 of the query fragment
+    const int c4 = lane >> 4, m16 = lane & 15;
+    const unsigned q_off = SHAPE >= 2 ? (unsigned)((c4 >> 1) * 1024 + ((c4 & 1) * 32 + m16) * 16) : lane_off;
+    const unsigned a_off = SHAPE == 4 ? lane_off : (unsigned)((c4 >> 1) * 1024 + ((c4 & 1) * 32 + 8 * ((m16 >> 2) & 1) + 4 * (m16 >> 3) + (m16 & 3)) * 16);
+    int tile_groups = 0;
     for (int j = 0; j < QT; ++j) for (int t = 0; t < 8; ++t) for (int r = 0; r < 16; ++r) acc[j][t][r] = 0.f;
     if (SHAPE) for (int i = 0; i < QT * 32; ++i) for (int r = 0; r < 4; ++r) acc4[i][r] = 0.f;
     // ring prefill: 128 KiB of random fragments
@@ -56,19 +67,31 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void model(const char* __restrict_
                                                                   : STREAM == 3 ? (blockIdx.x & 7) * 2 + (blockIdx.x >> 7) : (blockIdx.x & 7)) * REGION;   // 3: sixteen share, 4: an XCD's 32
 #define MM(J, T, BQ)                                                                                                          \
     if (SHAPE == 0) acc[J][T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[T], BQ, acc[J][T], 0, 0, 0);                          \
-    else { acc4[(J) * 32 + 4 * (T)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[T], BQ, acc4[(J) * 32 + 4 * (T)], 0, 0, 0);     \
+    else if (SHAPE == 1) { acc4[(J) * 32 + 4 * (T)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[T], BQ, acc4[(J) * 32 + 4 * (T)], 0, 0, 0);     \
            acc4[(J) * 32 + 4 * (T) + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[(T) ^ 1], BQ, acc4[(J) * 32 + 4 * (T) + 1], 0, 0, 0); }
+    // SHAPE 2: fragment T of half stage U & 1 against both query fragments of the stage
+#define MM2A(T, U) acc4[((U) & 1) * 16 + 2 * (T)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[T], bq[(U) & ~1][0], acc4[((U) & 1) * 16 + 2 * (T)], 0, 0, 0);
+#define MM2B(T, U) acc4[((U) & 1) * 16 + 2 * (T) + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[T], bq[(U) | 1][0], acc4[((U) & 1) * 16 + 2 * (T) + 1], 0, 0, 0);
+#define FRAG2(SLOT, F) (*reinterpret_cast<const f16x8*>(smem + (SLOT) * 16384 + a_off + ((F) >> 1) * 2048 + ((F) & 1) * 256))
     // one group with static register-ring index U
 #define GROUP(U)                                                                                                              \
     {                                                                                                                         \
         const f16x8* A = reinterpret_cast<const f16x8*>(smem + slot * 16384) + lane;                                          \
+        if (SHAPE == 3) { _Pragma("unroll") for (int t = 0; t < 8; ++t) { FENCE MM2A(t, U) FENCE } }                            \
         _Pragma("unroll") for (int t = 0; t < 8; ++t) {                                                                       \
-            _Pragma("unroll") for (int j = 0; j < QT; ++j) { FENCE MM(j, t, bq[U][j]) FENCE }                                  \
-            if (R) fa[t] = A[((t * 2 + ((U) & 1)) * 64)];                                                                      \
+            if (SHAPE == 3) { FENCE MM2B(t, U) FENCE }                                                                         \
+            else if (SHAPE >= 2) { FENCE MM2A(t, U) MM2B(t, U) FENCE }                                                         \
+            else { _Pragma("unroll") for (int j = 0; j < QT; ++j) { FENCE MM(j, t, bq[U][j]) FENCE } }                         \
+            if (R && SHAPE >= 2) fa[t] = ((U) & 1) ? FRAG2((slot + 1) & 7, t) : FRAG2(slot, 8 + t);                            \
+            else if (R) fa[t] = A[((t * 2 + ((U) & 1)) * 64)];                                                                 \
             if (C && t >= 2 && t < 2 + CPW)                                                                                   \
                 __builtin_amdgcn_global_load_lds((gbl_cvoid*)(bsrc + boff + (size_t)(w * CPW + t - 2) * 1024 + lane_off),     \
                                                  (lds_void*)(smem + ((slot + 4) & 7) * 16384 + (w * CPW + t - 2) * 1024 + ((U) & 1) * 8192), 16, 0, 0); \
-            if (Q && t == 0) {                                                                                                \
+            if (Q && SHAPE >= 2 && t == 7 && ((U) & 1)) {                                                                     \
+                asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(bq[(U) & ~1][0]) : "v"(q_off + qoff), "s"(qw) : "memory"); \
+                asm volatile("global_load_dwordx4 %0, %1, %2 offset:256" : "=v"(bq[U][0]) : "v"(q_off + qoff), "s"(qw) : "memory"); \
+            }                                                                                                                 \
+            if (Q && SHAPE < 2 && t == 0) {                                                                                  \
                 _Pragma("unroll") for (int j = 0; j < QT; ++j)                                                                \
                     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(bq[U][j]) : "v"(lane_off + qoff + j * 1024u), "s"(qw) : "memory"); \
             }                                                                                                                 \
@@ -87,6 +110,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void model(const char* __restrict_
         GROUP(0) GROUP(1)
         if constexpr (DEPTH > 2) { GROUP(2) GROUP(3) }
         if constexpr (DEPTH > 4) { GROUP(4) GROUP(5) GROUP(6) GROUP(7) }
+        if constexpr (SHAPE >= 2) {   // a tile's end (48 groups): back to the 32x32 layout, one swap per register pair
+            tile_groups += DEPTH;
+            if (tile_groups == 48) {
+                tile_groups = 0;
+#pragma unroll
+                for (int f = 0; f < 16; ++f)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc4[2 * f][r]), __float_as_uint(acc4[2 * f + 1][r]), false, false);
+                        acc4[2 * f][r] = __uint_as_float(sw[0]); acc4[2 * f + 1][r] = __uint_as_float(sw[1]);
+                    }
+            }
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (threadIdx.x == 0) {
@@ -133,7 +169,8 @@ __global__ void fill_kernel(_Float16* p, size_t n) {
 }
 
 int main(int argc, char** argv) {
-    const bool streams_only = argc > 1;
+    const bool streams_only = argc > 1 && argv[1][0] == 's';
+    const bool shapes_only = argc > 1 && argv[1][0] == 'k';   // `f16_stage_model kernel`: the shipped tile's rows only
     const size_t bank_bytes = (size_t)64 << 20, q_bytes = (size_t)256 * 8 * 49152 * 3;
     std::vector<_Float16> h((bank_bytes + q_bytes) / 2);
     srand(1);
@@ -169,6 +206,12 @@ int main(int argc, char** argv) {
         run<8, 1, 1, false, false, false, false, 8>("16x16x32 bare", G);
         run<8, 1, 1, true, true, true, true, 8>("16x16x32 + reads + query loads + copies + barrier", G);
         run<8, 1, 1, true, false, true, true, 8>("16x16x32 + reads + copies + barrier (queries stationary)", G);
+        run<8, 1, 2, true, true, true, true, 8>("16x16x32 kernel loop: permuted reads, 2 query fragments per stage, swaps", G);
+        run<8, 1, 3, true, true, true, true, 8>("16x16x32 kernel loop, B operand stationary for 8 MFMAs", G);
+        run<8, 1, 4, true, true, true, true, 8>("16x16x32 kernel loop, fragment reads at lane x 16 B", G);
+        run<8, 1, 2, true, false, true, true, 8>("16x16x32 kernel loop (queries stationary)", G);
+        run<8, 1, 3, true, false, true, true, 8>("16x16x32 kernel loop, B stationary for 8 MFMAs (queries stationary)", G);
+        if (shapes_only) continue;
         printf("--- 4 waves x (64 q x 256 rows), 256 accumulators ---\n");
         run<4, 2, 0, false, false, false, false, 4>("32x32x16 bare", G / 2);
         run<4, 2, 0, true, true, true, true, 4>("32x32x16 + reads + query loads + copies + barrier", G / 2);
