@@ -289,6 +289,10 @@ int hb_last_search_path(const hb_index_t* ix, int* path, int* reason);
 int hb_exact_screen_replay(int setting, int pinned, int env_off, int k, int ceiling, int64_t rows, int64_t nq, int d, int64_t stages_per_wg,
                            int overflow, int have_copy, int declined, uint64_t free_bytes, uint64_t total_bytes, uint64_t bank_bytes,
                            uint64_t copy_bytes, int* why);
+/* hb_rerank_copy_replay: whether an index gets the re-rank's row copy (hb_index_set_rerank_copy), without a GPU (tests): the setting (0 automatic,
+ * 1 always, 2 never), the bytes of the fp32 tiles and of the copy, free / total device bytes -> 1 the copy is made / 0 none; a negative status for
+ * a setting outside 0..2, a size of 0 or more free than total bytes. */
+int hb_rerank_copy_replay(int setting, uint64_t bank_bytes, uint64_t need_bytes, uint64_t free_bytes, uint64_t total_bytes);
 /* hb_knn_plan_replay: the launcher's SHAPE PLAN for one imagined search without a GPU (tests; csrc/hbird_calibrate.cpp: hb_knn_plan_shape /
  * _clusters / _kernel) -- everything hb_index_search derives from the search's sizes and the index's override fields once the path is known.
  * in[0..22] (n_in >= 23): 0 f16 (the screen's final decision), 1 wide_first (adaptive use: one pass with k' = 256), 2 esc (0 a caller's search,

@@ -164,6 +164,18 @@ bool hb_screen_choose(const hb_screen_in& in, int* why) {
     return screen;
 }
 
+// Automatic (round 6, by measurement: profiles/r06/final/fp16_residency.json): what the copy saves is a few ms of re-rank per search (about 4 ms
+// for 21,904 queries x 64 candidates), whatever the bank's size, and what it costs is the bank once more.  At 300,000 x 768 that is 17 % of a
+// search for 0.9 GB; at 10 M x 768 1.5 % for 30.7 GB (30.7 GB of tiles + 15.4 GB of fp16 tiles + 30.7 GB of rows, of 288), at 20 M x 1024 and
+// 27.7 M x 768 0.4 % for 83-85 GB.  So only banks of up to 4e9 values (16 GB of fp32: 5.2 M x 768) get it -- a use_fp16 index of a bigger bank
+// holds 1.5 x the bank (fp32 tiles for the exact re-rank and the fp32 searches, fp16 tiles for the candidate pass), not 2.5 x -- and, as before,
+// only where the three copies stay within 55 % of the device with room to spare: the search's own workspace is allocated after the copy, and a
+// device shared with a model or another rank must not be filled to the brim by an optional copy.
+bool hb_rerank_copy_choose(int setting, uint64_t bank_b, uint64_t need_b, uint64_t free_b, uint64_t total_b) {
+    if (setting != 0) return setting == 1;
+    return bank_b <= (uint64_t)16e9 && bank_b + bank_b / 2 + need_b <= total_b / 100 * 55 && free_b > need_b + std::max<uint64_t>(total_b / 16, (uint64_t)2 << 30);
+}
+
 // ---- the shape plan of one search (hbird_calibrate.h) -----------------------------------------------------------------------------------
 long long hb_stages_per_wg(long long nqt, long long nbt, int workgroups, int stages_per_tile) {
     return nqt * nbt / std::max(1, workgroups) * stages_per_tile;
@@ -337,6 +349,11 @@ extern "C" int hb_exact_screen_replay(int setting, int pinned, int env_off, int 
     in.stages_per_wg = stages_per_wg; in.overflow = overflow != 0; in.have_copy = have_copy != 0; in.declined = declined != 0;
     in.mem_known = true; in.free_b = free_bytes; in.total_b = total_bytes; in.bank_b = bank_bytes; in.copy_b = copy_bytes;
     return hb_screen_choose(in, why) ? 1 : 0;
+}
+// the re-rank copy's admission for one imagined index (include/hbird_hip.h)
+extern "C" int hb_rerank_copy_replay(int setting, uint64_t bank_bytes, uint64_t need_bytes, uint64_t free_bytes, uint64_t total_bytes) {
+    if (setting < 0 || setting > 2 || bank_bytes == 0 || need_bytes == 0 || total_bytes == 0 || free_bytes > total_bytes) return -1;
+    return hb_rerank_copy_choose(setting, bank_bytes, need_bytes, free_bytes, total_bytes) ? 1 : 0;
 }
 // the launcher's shape plan for one imagined search (include/hbird_hip.h: the slots)
 extern "C" int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int n_out) {

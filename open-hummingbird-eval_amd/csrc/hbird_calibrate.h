@@ -90,6 +90,11 @@ struct hb_screen_in {
 };
 bool hb_screen_choose(const hb_screen_in& in, int* why);     // -> the screen (true) or the fp32 kernel; *why = HB_WHY_*
 
+// ---- the re-rank's row copy (hb_index_set_rerank_copy): whether an index gets the bank once more as fp32 rows -------------------------------
+// setting 1: always, 2: never, 0: by the bank's and the device's sizes (the rule and its measurements: hbird_calibrate.cpp).  The launcher
+// (hbird_knn.hip) asks the device and remembers a refusal for the capacity.
+bool hb_rerank_copy_choose(int setting, uint64_t bank_b, uint64_t need_b, uint64_t free_b, uint64_t total_b);
+
 // ---- the shape plan of one search (hb_launch_knn, hbird_knn.hip) ------------------------------------------------------------------------
 // Everything the launcher derives from the search's sizes and the index's override fields before it touches the device: which kernel runs,
 // on pools or lists, with which clusters, phased or not.  Plain values in, plain values out (CPU tests: hb_knn_plan_replay, tests/

@@ -161,10 +161,8 @@ extern "C" int hb_index_set_fp16_centre(hb_index_t* ix, int on) {
     if (on == ix->fp16_centre) return 0;
     HB_HIP(hipSetDevice(ix->device));
     HB_HIP(hipStreamSynchronize(ix->stream));
-    ix->drop_tiles16();
-    ix->f16_overflow = 0; ix->f16_declined_cap = -1;
-    if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, ix->stream));      // (the flag speaks of the values of the copy's form)
-    hb_centre_drop(ix);
+    ix->copy16.drop_form();
+    if (ix->copy16.flag) HB_HIP(hipMemsetAsync(ix->copy16.flag, 0, 4, ix->stream));      // (the flag speaks of the values of the copy's form)
     ix->fp16_centre = on; ix->last_centred = 0;
     ix->f16_adapt = hb_f16_adapt();      // (the failing shares belong to the form that was measured)
     return 0;
@@ -172,14 +170,14 @@ extern "C" int hb_index_set_fp16_centre(hb_index_t* ix, int on) {
 extern "C" int hb_index_fp16_centre_info(const hb_index_t* ix, double out[8]) {
     if (!ix || !out) return hb_fail("hb_index_fp16_centre_info: NULL pointer");
     for (int i = 0; i < 8; ++i) out[i] = 0.0;
-    const hb_centre_state& c = ix->centre;
+    const hb_centre_state& c = ix->copy16.centre;
     HB_HIP(hipSetDevice(ix->device));
     float sc[4] = {0, 0, 0, 0}, bmax = 0.0f;
     HB_HIP(hipStreamSynchronize(ix->stream));
     HB_HIP(hipMemcpy(&bmax, ix->bmax, 4, hipMemcpyDeviceToHost));
-    const bool active = ix->fp16_centre && c.active && ix->tiles16 && c.sc;
+    const bool active = ix->fp16_centre && c.active && ix->copy16.tiles && c.sc;
     if (active) HB_HIP(hipMemcpy(sc, c.sc, 16, hipMemcpyDeviceToHost));
-    out[0] = active ? 1.0 : 0.0; out[1] = sc[1]; out[2] = sc[0]; out[3] = bmax; out[4] = sc[3]; out[5] = active ? (double)c.rows : 0.0;
+    out[0] = active ? 1.0 : 0.0; out[1] = sc[1]; out[2] = sc[0]; out[3] = bmax; out[4] = sc[3]; out[5] = active ? (double)ix->copy16.centred_rows() : 0.0;
     out[6] = ix->fp16_centre; out[7] = ix->last_centred;
     return 0;
 }
@@ -357,17 +355,17 @@ extern "C" int hb_index_xcd_stats(const hb_index_t* ix, int fp16_kernel, double 
 extern "C" int hb_index_set_rerank_copy(hb_index_t* ix, int mode) {
     if (!ix) return hb_fail("hb_index_set_rerank_copy: NULL index handle");
     if (mode < 0 || mode > 2) return hb_fail("hb_index_set_rerank_copy: mode must be 0 (automatic), 1 (always) or 2 (never)");
-    ix->rerank_copy = mode; ix->rows32_declined_cap = -1;
-    if (mode == 2 && ix->rows32) {
+    ix->rerank_copy = mode; ix->row_copy.m.ask_again();
+    if (mode == 2 && ix->row_copy.rows) {
         (void)hipSetDevice(ix->device);
         HB_HIP(hipStreamSynchronize(ix->stream));
-        ix->drop_rows32();
+        ix->row_copy.drop();
     }
     return 0;
 }
 extern "C" int hb_index_rerank_copy_bytes(const hb_index_t* ix, int64_t* bytes) {
     if (!ix || !bytes) return hb_fail("hb_index_rerank_copy_bytes: NULL argument");
-    *bytes = ix->rows32 ? ix->rows32_cap_rows * (int64_t)ix->rows32_rs * 4 : 0;
+    *bytes = ix->row_copy.bytes();
     return 0;
 }
 extern "C" int hb_index_schedule_info(const hb_index_t* ix, int64_t out[8]) {
@@ -376,6 +374,15 @@ extern "C" int hb_index_schedule_info(const hb_index_t* ix, int64_t out[8]) {
     out[0] = s.G; out[1] = (int64_t)s.segs.size(); out[2] = s.n_slots; out[3] = s.panel; out[4] = s.max_slots_per_qt;
     out[5] = s.nqt; out[6] = s.nbt; out[7] = s.cq * 16 + s.cb;
     return 0;
+}
+
+int hb_index::bank_changed(hb_bank_event what) {
+    screen.state = HB_SCREEN_NONE;      // (hb_index_last_screen: the record spoke of the bank as it was)
+    if (what == HB_BANK_EMPTIED) {
+        copy16.emptied(); row_copy.m.emptied();      // (a centred copy derives its mean anew; allocations and declined marks stay with the capacity)
+        if (copy16.flag) HB_HIP(hipMemsetAsync(copy16.flag, 0, 4, stream));
+    }
+    return 0;      // (appended: the copies are behind ntotal, moved: they are not for cap_rows -- the next search that needs one sees either)
 }
 
 extern "C" int hb_index_reserve(hb_index_t* ix, int64_t n_rows) {
@@ -401,8 +408,7 @@ extern "C" int hb_index_reserve(hb_index_t* ix, int64_t n_rows) {
     HB_HIP(hipMemsetAsync(bnorm + ix->cap_rows, 0, (size_t)(cap - ix->cap_rows) * 4, s));
     HB_HIP(hipStreamSynchronize(s));
     ix->tiles = std::move(tiles); ix->binit = std::move(binit); ix->bnorm = std::move(bnorm); ix->cap_rows = cap;
-    ix->screen.state = HB_SCREEN_NONE;
-    return 0;
+    return ix->bank_changed(HB_BANK_MOVED);
 }
 
 extern "C" int hb_index_reset(hb_index_t* ix) {
@@ -416,13 +422,10 @@ extern "C" int hb_index_reset(hb_index_t* ix) {
         HB_HIP(hipStreamSynchronize(s));
     }
     HB_HIP(hipMemsetAsync(ix->bmax, 0, 4, s));
-    ix->ntotal = 0; ix->nlabels = 0; ix->lab_checked = 0; ix->f16_rows = 0; ix->f16_overflow = 0; ix->rows32_rows = 0;
+    ix->ntotal = 0; ix->nlabels = 0; ix->lab_checked = 0;
     ix->row_groups_n = 0; ix->n_groups = 0; ix->gmax = 0;      // the row-group table goes with the rows
-    ix->centre.rows = 0;      // (f16_rows = 0: a centred copy derives its mean anew from the rows of the next search)
-    ix->screen.state = HB_SCREEN_NONE;
     if (ix->lab_flag) HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, s));
-    if (ix->f16_flag) HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s));
-    return 0;
+    return ix->bank_changed(HB_BANK_EMPTIED);
 }
 
 static int stage_in(hb_index* ix, const void* host, size_t bytes, size_t offset) {
@@ -459,8 +462,8 @@ extern "C" int hb_index_add(hb_index_t* ix, const float* x, int64_t n, int x_on_
                                     normalize, 1, ix->stream)) return -1;
     }
     if (hb_launch_bnorm_max(ix->bnorm + ix->ntotal, n, ix->bmax, ix->stream)) return -1;
-    ix->ntotal += n; ix->screen.state = HB_SCREEN_NONE;
-    return 0;
+    ix->ntotal += n;
+    return ix->bank_changed(HB_BANK_APPENDED);
 }
 
 extern "C" int hb_index_set_label_denominator(hb_index_t* ix, int P) {
@@ -573,9 +576,6 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     if (!q) return hb_fail("hb_index_search: q is NULL");
     hb_range range(aggregate ? "hbird:search_aggregate" : "hbird:search");
     HB_HIP(hipSetDevice(ix->device));
-    const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
-    if (ix->q_tiles.ensure((size_t)nqp * ix->dp * 4, HB_GROW_EXACT)) return -1;
-    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
     // staging area in ix->tmp: [queries (host path)] [idx] [dist] [label_hat (host path)]
     const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4);
     const size_t b_idx = al256((size_t)nq * k * 8), b_dist = al256((size_t)nq * k * 4);
@@ -599,8 +599,7 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     if (b_lab) { d_lab = (float*)cur; cur += b_lab; }
     {
         hb_range r("hbird:query_tiles");
-        if (hb_launch_rows_to_tiles(qd, nq, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, ix->stream)) return -1;
-        if (hb_launch_query_aux(qd, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
+        if (hb_prepare_queries(ix, qd, nq)) return -1;
     }
     {
         hb_range r("hbird:knn");

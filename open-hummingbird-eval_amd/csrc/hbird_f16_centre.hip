@@ -243,15 +243,9 @@ __global__ __launch_bounds__(256) void centre_init16_kernel(const float* __restr
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-void hb_centre_drop(hb_index* ix) {
-    hb_centre_state& c = ix->centre;
-    c.mu.drop(); c.g.drop(); c.init16.drop(); c.sc.drop(); c.qaux.drop();
-    c.cap_rows = 0; c.active = 0; c.rows = 0; c.q_n = 0; c.q_level = -1;
-}
-
 // mu from the rows present now.  -> c.active (0: a non-finite or all-zero mean: the plain copy serves this bank)
 static int centre_derive_mean(hb_index* ix, hipStream_t s) {
-    hb_centre_state& c = ix->centre;
+    hb_centre_state& c = ix->copy16.centre;
     const int64_t nrt = (ix->ntotal + 31) / 32;
     const int64_t per = (nrt + HC_PARTS - 1) / HC_PARTS;
     const size_t b_valid = al256((size_t)nrt * 4), b_part = (size_t)HC_PARTS * ix->g8 * 8 * 8;
@@ -266,43 +260,36 @@ static int centre_derive_mean(hb_index* ix, hipStream_t s) {
     HB_HIP(hipMemcpyAsync(h, c.sc, 16, hipMemcpyDeviceToHost, s));
     HB_HIP(hipStreamSynchronize(s));      // (the kernels are done with tmp)
     c.active = std::isfinite(h[1]) && h[2] > 0.0f ? 1 : 0;
-    c.rows = 0;
     return 0;
 }
 
-// Bring the centred copy up to date (the caller has allocated ix->tiles16 for ix->cap_rows and zeroed it; ix->f16_rows rows are converted).
+// Bring the centred copy up to date (the caller has made the copy's tiles for ix->cap_rows and zeroed them, and marks the rows converted).
 // *centred_out = 0: this bank has no usable mean, the caller converts with hb_launch_tiles_to_f16 as without centring.
 int hb_centre_convert(hb_index* ix, hipStream_t s, int* centred_out) {
-    hb_centre_state& c = ix->centre;
+    hb_fp16_copy& copy = ix->copy16;
+    hb_centre_state& c = copy.centre;
     *centred_out = 0;
-    if (c.cap_rows != ix->cap_rows || !c.mu) {
-        // four locals until all are there: a failing allocation frees the earlier ones and leaves the index as it was
-        hb_dev<float> mu, g, init16, sc;
-        if (mu.ensure((size_t)std::max(ix->dp16, ix->g8 * 8) * 4, HB_GROW_EXACT) || g.ensure((size_t)ix->cap_rows * 4, HB_GROW_EXACT) ||
-            init16.ensure((size_t)ix->cap_rows * 4, HB_GROW_EXACT) || sc.ensure(16, HB_GROW_EXACT)) return -1;
-        hb_centre_drop(ix);
-        c.mu = std::move(mu); c.g = std::move(g); c.init16 = std::move(init16); c.sc = std::move(sc);
-        HB_HIP(hipMemsetAsync(c.g, 0, (size_t)ix->cap_rows * 4, s));
-        HB_HIP(hipMemsetD32Async((hipDeviceptr_t)c.init16, 0xFF800000u, (size_t)ix->cap_rows, s));
-        c.cap_rows = ix->cap_rows;
-        if (ix->f16_rows != 0) return hb_fail("hb_index_search: the centred fp16 copy lost its row arrays");
+    if (!copy.has_centre_arrays()) {      // (the row arrays go with the tiles: a new copy has none)
+        if (copy.make_centre_arrays((size_t)std::max(ix->dp16, ix->g8 * 8))) return -1;
+        HB_HIP(hipMemsetAsync(c.g, 0, (size_t)copy.m.cap * 4, s));
+        HB_HIP(hipMemsetD32Async((hipDeviceptr_t)c.init16, 0xFF800000u, (size_t)copy.m.cap, s));
     }
-    if (ix->f16_rows == 0 && centre_derive_mean(ix, s)) return -1;      // a new copy (first use, hb_index_reset, a capacity change): mu anew
+    if (copy.m.rows == 0 && centre_derive_mean(ix, s)) return -1;      // a new copy (first use, hb_index_reset, a capacity change): mu anew
     if (!c.active) return 0;
-    const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
-    const int64_t threads = (need_rt - rt0) * 32;
+    int64_t rt0 = 0, n_rt = 0;
+    copy.m.pending(ix->ntotal, &rt0, &n_rt);
+    const int64_t threads = n_rt * 32;
     if (threads > 0) {
-        centre_bank_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(ix->tiles, ix->g8, c.mu, ix->tiles16.as<_Float16>(), ix->dp16 / 16, rt0,
-                                                                                         need_rt - rt0, ix->ntotal, c.g, c.sc, ix->f16_flag);
+        centre_bank_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(ix->tiles, ix->g8, c.mu, copy.tiles.as<_Float16>(), ix->dp16 / 16, rt0, n_rt,
+                                                                                         ix->ntotal, c.g, c.sc, copy.flag);
         HB_HIP(hipGetLastError());
     }
-    c.rows = ix->ntotal;
     *centred_out = 1;
     return 0;
 }
 
 static int centre_qaux(hb_index* ix, int64_t nq, float** cq, float** qcn, double** part) {
-    hb_centre_state& c = ix->centre;
+    hb_centre_state& c = ix->copy16.centre;
     const size_t b_f = al256((size_t)nq * 4), need = 2 * b_f + (size_t)((nq + 63) / 64) * 8;
     if (c.qaux.ensure(need, HB_GROW_QUARTER)) return -1;
     *cq = c.qaux.as<float>(); *qcn = c.qaux.as<float>(b_f); *part = c.qaux.as<double>(2 * b_f);
@@ -312,7 +299,7 @@ static int centre_qaux(hb_index* ix, int64_t nq, float** cq, float** qcn, double
 // The query side of one pass.  first = a caller's search: t is derived from its queries and init16 from t; a nested second pass over the
 // uncertified queries (first = 0) keeps both and only converts its gathered queries.
 int hb_centre_queries(hb_index* ix, int64_t nq, int first, _Float16* q16, hb_centre_view* view, hipStream_t s) {
-    hb_centre_state& c = ix->centre;
+    hb_centre_state& c = ix->copy16.centre;
     float *cq = nullptr, *qcn = nullptr;
     double* part = nullptr;
     if (centre_qaux(ix, nq, &cq, &qcn, &part)) return -1;
@@ -334,18 +321,19 @@ int hb_centre_queries(hb_index* ix, int64_t nq, int first, _Float16* q16, hb_cen
 // What the conversion left (include/hbird_hip_centre.h): host bookkeeping and copies, no launch.
 int hb_centre_readout(hb_index* ix, float* mu, float* scalars, float* g, float* init16, uint16_t* bank16, float* cq, float* qcn, uint16_t* q16,
                       int64_t info[8]) {
-    const hb_centre_state& c = ix->centre;
+    const hb_fp16_copy& copy = ix->copy16;
+    const hb_centre_state& c = copy.centre;
     for (int i = 0; i < 8; ++i) info[i] = 0;
     info[4] = -1;
-    const int64_t n_g = (c.rows + 31) / 32 * 32, n_init = (c.rows + HB_BT - 1) / HB_BT * HB_BT;
-    if (!ix->fp16_centre || !c.active || c.rows <= 0 || !ix->tiles16 || !c.mu || !c.g || !c.init16 || !c.sc || c.cap_rows < n_init || ix->f16_cap_rows < n_g)
+    const int64_t rows = copy.centred_rows(), n_g = (rows + 31) / 32 * 32, n_init = (rows + HB_BT - 1) / HB_BT * HB_BT;      // (n_g <= n_init)
+    if (!ix->fp16_centre || rows <= 0 || !copy.tiles || !copy.has_centre_arrays() || copy.m.cap < n_init)
         return hb_fail("hb_index_last_centre: no active centred copy (centring off, no screened search yet, a bank without a usable mean, or a reset since)");
     const int n_mu = std::max(ix->dp16, ix->g8 * 8);
     // the query side: the last search of a caller ran centred and the bank has not changed since (the screen record goes with either)
     const bool q_ok = c.q_level >= 0 && ix->last_centred && ix->screen.state != HB_SCREEN_NONE && c.qaux.bytes >= 2 * al256((size_t)c.q_n * 4) &&
                       ix->q16.bytes >= (size_t)((c.q_n + HB_QT - 1) / HB_QT * HB_QT) * ix->dp16 * 2;
     const int64_t n = q_ok ? c.q_n : 0, n_qpad = (n + HB_QT - 1) / HB_QT * HB_QT;
-    info[0] = c.rows; info[1] = ix->dp16; info[2] = n_mu; info[3] = n; info[4] = q_ok ? c.q_level : -1; info[5] = n_g; info[6] = n_init; info[7] = n_qpad;
+    info[0] = rows; info[1] = ix->dp16; info[2] = n_mu; info[3] = n; info[4] = q_ok ? c.q_level : -1; info[5] = n_g; info[6] = n_init; info[7] = n_qpad;
     HB_HIP(hipSetDevice(ix->device));
     HB_HIP(hipStreamSynchronize(ix->stream));
     if ((cq || qcn || q16) && !q_ok)
@@ -354,7 +342,7 @@ int hb_centre_readout(hb_index* ix, float* mu, float* scalars, float* g, float* 
     if (scalars) HB_HIP(hipMemcpy(scalars, c.sc, 16, hipMemcpyDeviceToHost));
     if (g) HB_HIP(hipMemcpy(g, c.g, (size_t)n_g * 4, hipMemcpyDeviceToHost));
     if (init16) HB_HIP(hipMemcpy(init16, c.init16, (size_t)n_init * 4, hipMemcpyDeviceToHost));
-    if (bank16) HB_HIP(hipMemcpy(bank16, ix->tiles16, (size_t)n_g * ix->dp16 * 2, hipMemcpyDeviceToHost));
+    if (bank16) HB_HIP(hipMemcpy(bank16, copy.tiles, (size_t)n_g * ix->dp16 * 2, hipMemcpyDeviceToHost));
     const size_t b_f = al256((size_t)n * 4);      // (centre_qaux's carve-up)
     if (cq && n) HB_HIP(hipMemcpy(cq, c.qaux.as<float>(), (size_t)n * 4, hipMemcpyDeviceToHost));
     if (qcn && n) HB_HIP(hipMemcpy(qcn, c.qaux.as<float>(b_f), (size_t)n * 4, hipMemcpyDeviceToHost));

@@ -9,6 +9,7 @@
 #include "hbird_calibrate.h"
 #include "hbird_f16_centre.h"
 #include "hbird_devbuf.h"
+#include "hbird_mirror.h"
 
 // ---- tile geometry of the kNN kernel (see DESIGN.md "Data layout in HBM") -------------------
 #define HB_RT 32         // rows per fragment tile (MFMA 32x32x2)
@@ -18,6 +19,13 @@
 #define HB_BLK 256       // floats per fragment block (32 rows x 8 k) = 1 KiB
 
 #define HB_ID_NONE 0xFFFFFFFFu
+
+// hb_index::bank_changed: what happened to the bank
+enum hb_bank_event {
+    HB_BANK_APPENDED,      // rows were added within the capacity: the copies catch up at the next search
+    HB_BANK_EMPTIED,       // hb_index_reset: no rows, the same capacity
+    HB_BANK_MOVED          // hb_index_reserve: a new capacity (the next search that needs a copy releases the old one and makes it anew)
+};
 
 // hb_index::screen.state
 #define HB_SCREEN_NONE 0          // no level-0 fp16 candidate pass since the bank last changed
@@ -81,19 +89,14 @@ struct hb_index {
     int fp16 = HB_FP16_AUTO, dp16 = 0;                    // 0 = the fp32 kernel, 1 = always, 2 = where it pays, HB_FP16_AUTO = the certified screen for big exact searches (hb_screen_choose)
     int fp32_pinned = 0;                                 // sticky: the caller steered the fp32 kernel (variant, tuning, clusters, shares, search options): the automatic state stays on it
     int screen_env_off = 0;                              // HBIRD_EXACT_SCREEN=0 when the index was created
-    int64_t f16_declined_cap = -1;                       // automatic state: no room for the fp16 tiles at this capacity (or the allocation failed): not asked again per search
     int last_path = 0, last_reason = 0;                  // what served the last search of a caller (hb_last_search_path)
     hb_dev<unsigned> stamp_keep;                          // the candidate launch's stamps, kept aside while nested searches reuse `state`
-    hb_dev<void> tiles16; int64_t f16_cap_rows = 0, f16_rows = 0;
-    hb_dev<int> f16_flag; int f16_overflow = 0;       // a finite bank value overflowed fp16: the fp32 kernel serves this bank
-    // ... and, where memory allows, the bank once more as plain fp32 rows [row][rows32_rs] for the exact re-rank (hbird_knn_f16.hip)
-    hb_dev<float> rows32; int64_t rows32_cap_rows = 0, rows32_rows = 0; int rows32_rs = 0;
+    // the lazy copies of the bank (hbird_mirror.h), brought up to date by the first search that needs them and told of the bank by bank_changed
+    hb_fp16_copy copy16;                                 // the fp16 tiles of the candidate pass, with their mean-centred form (hbird_f16_centre.hip)
+    hb_row_copy row_copy;                                // the bank as fp32 rows for the exact re-rank, where memory allows
     int rerank_copy = 0;                                 // 0 = automatic, 1 = always, 2 = never (hb_index_set_rerank_copy)
-    int64_t rows32_declined_cap = -1;                    // automatic mode found no room for the copy at this capacity: not asked again per search
-    // the mean-centred form of that copy (hb_index_set_fp16_centre; hbird_f16_centre.hip): mu, two floats per row, four device scalars
-    int fp16_centre = 0;                                 // the setting: 0 = the plain copy (default), 1 = centred
+    int fp16_centre = 0;                                 // the setting: 0 = the plain fp16 copy (default), 1 = centred (hb_index_set_fp16_centre)
     int last_centred = 0;                                // the last search of a caller ran its candidate pass on the centred copy
-    hb_centre_state centre;
     hb_dev<void> q16;
     hb_dev<char> cand;
     hb_dev<float> bmax;                                  // device scalar: max bank-row norm
@@ -128,10 +131,11 @@ struct hb_index {
     int excl_screen = 0;                                 // the setting: 0 = the rungs serve every excluding search (default), 1 = the screen where it applies
     int64_t last_excl_screen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hb_index_last_exclusion_screen's slots
     hb_dev<char> excl_sub;                               // the queries the screen left to the rungs: their rows, groups, query rows and lists
-    // a lazy copy or a table goes together with the counters that describe it (the caller has synchronised the stream where work may still read it)
-    void drop_tiles16() { tiles16.drop(); f16_rows = 0; f16_cap_rows = 0; }
-    void drop_rows32() { rows32.drop(); rows32_cap_rows = 0; rows32_rows = 0; }
+    // the label table goes together with the counter that describes it (the caller has synchronised the stream where work may still read it)
     void drop_labels() { labels.drop(); labels16.drop(); lab_cap = 0; }
+    // The one place that invalidates the screen record and tells the lazy copies: hb_index_add, hb_index_add_from, hb_index_reset and
+    // hb_index_reserve each call it once (hbird_capi.hip)
+    int bank_changed(hb_bank_event what);
 };
 
 void hb_set_error(const std::string& msg);
@@ -152,6 +156,8 @@ int hb_launch_rows_to_tiles(const float* src, int64_t n_rows, int d, int dp, int
                             float* binit, float* bnorm, int metric, int normalize, int is_bank, hipStream_t s);
 int hb_launch_scores_to_l2(const float* qn2, int64_t nq, int k, float* dist_inout, hipStream_t s);
 int hb_launch_query_aux(const float* q, int64_t nq, int d, float* qn2, float* qnorm, hipStream_t s);
+// what a level-0 search reads of its queries: their fragment tiles in q_tiles, chain ||q||^2 and fp32 norms in q_aux (hbird_knn.hip)
+int hb_prepare_queries(hb_index* ix, const float* q_dev, int64_t nq);
 int hb_launch_tiles_to_rows(const float* tiles, int g8, int d, const int64_t* ids, int64_t n, int64_t id_base, int64_t ntotal,
                             float* out, hipStream_t s);
 int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);

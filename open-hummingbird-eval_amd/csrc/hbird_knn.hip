@@ -653,7 +653,7 @@ static int hb_launch_knn_bigk(hb_index* ix, const knn_call& c, const float* q_de
     return rc;
 }
 
-// ---- stage 1: which path serves the call, and the upkeep of the screen's two optional copies of the bank --------------------------------
+// ---- stage 1: which path serves the call, and the upkeep of the screen's two lazy copies of the bank (hbird_mirror.h) --------------------------------
 struct knn_path {
     bool f16 = false;          // the candidate pass (the final decision: the upkeep below may still turn it off)
     int why = HB_WHY_EXPLICIT_FP32;
@@ -678,20 +678,20 @@ static int knn_choose_path(hb_index* ix, const knn_call& c, int64_t nq, int k, k
     // fp32 kernels stamp and calibrate (below) --, on an index whose fp32 kernel the caller has not steered, and where the fp16 copy fits.
     hb_screen_in sin;
     sin.setting = c.fp16; sin.pinned = ix->fp32_pinned != 0; sin.env_off = ix->screen_env_off != 0; sin.k = k; sin.ceiling = ceil;
-    sin.rows = ix->ntotal; sin.nq = nq; sin.d = ix->d; sin.overflow = ix->f16_overflow != 0;
+    sin.rows = ix->ntotal; sin.nq = nq; sin.d = ix->d; sin.overflow = ix->copy16.overflow != 0;
     sin.stages_per_wg = hb_stages_per_wg((nq + HB_QT - 1) / HB_QT, (ix->ntotal + HB_BT - 1) / HB_BT, hb_knn_workgroups(ix->force_G, ix->num_cu), ix->g8);
-    sin.have_copy = ix->tiles16 != nullptr && ix->f16_cap_rows == ix->cap_rows;
-    sin.declined = ix->f16_declined_cap == ix->cap_rows;
+    sin.have_copy = ix->copy16.m.has(ix->cap_rows);
+    sin.declined = ix->copy16.m.declined_at(ix->cap_rows);
     sin.bank_b = (uint64_t)ix->cap_rows * ix->dp * 4; sin.copy_b = (uint64_t)ix->cap_rows * ix->dp16 * 2;
     p.automatic = c.fp16 == HB_FP16_AUTO;
     p.f16 = hb_screen_choose(sin, &p.why);
     if (p.f16 && p.automatic && !sin.have_copy && nq > 0 && ix->ntotal > 0) {      // the copy has to be made: only where it leaves the device room
-        ix->drop_tiles16();      // (the bank grew: the old copy goes first)
+        ix->copy16.drop();      // (the bank grew: the old copy goes first)
         size_t free_b = 0, total_b = 0;
         HB_HIP(hipMemGetInfo(&free_b, &total_b));
         sin.mem_known = true; sin.free_b = free_b; sin.total_b = total_b;
         p.f16 = hb_screen_choose(sin, &p.why);
-        if (!p.f16) ix->f16_declined_cap = ix->cap_rows;
+        if (!p.f16) ix->copy16.m.declined(ix->cap_rows);
     }
     // ADAPTIVE use (mode 2, round 6): on a bank whose neighbours sit closer together than fp16 can tell apart -- token worlds with little
     // noise: profiles/r06/final/fp16_cliff_*.json -- most certificates fail, and passes that certify nothing are pure overhead.  The index keeps
@@ -708,72 +708,61 @@ static int knn_choose_path(hb_index* ix, const knn_call& c, int64_t nq, int k, k
     return 0;
 }
 
-// bring the fp16 copy of the bank and the re-rank's row copy up to date; may turn f16 off (with its reason)
-static int knn_screen_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, hipStream_t s0, bool& f16, int& why) {
-    // bring the fp16 copy of the bank fragment tiles up to date.  A finite value beyond the fp16 range (|x| > 65504) turns
-    // into inf there and the scores into inf / NaN, which the exactness certificate cannot bound: such a bank stays on the
-    // fp32 kernel (every query counts as a fallback)
-    if (!ix->f16_flag) { if (ix->f16_flag.ensure(4, HB_GROW_EXACT)) return -1; HB_HIP(hipMemsetAsync(ix->f16_flag, 0, 4, s0)); }
-    if (ix->f16_cap_rows != ix->cap_rows) {
-        ix->drop_tiles16();      // (the bank grew, or the allocation is about to be repeated)
+// Bring the fp16 copy of the bank fragment tiles up to date; may turn f16 off (with its reason).  A finite value beyond the fp16 range
+// (|x| > 65504) turns into inf there and the scores into inf / NaN, which the exactness certificate cannot bound: such a bank stays on the
+// fp32 kernel (every query counts as a fallback)
+static int knn_fp16_copy_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, hipStream_t s0, bool& f16, int& why) {
+    hb_fp16_copy& copy = ix->copy16;
+    if (!copy.flag) { if (copy.flag.ensure(4, HB_GROW_EXACT)) return -1; HB_HIP(hipMemsetAsync(copy.flag, 0, 4, s0)); }
+    if (!copy.m.has(ix->cap_rows)) {      // (the bank grew, or the allocation is about to be repeated)
         // states 1 / 2: the caller asked for the copy, no memory for it is the search's error.  Automatic: the copy only buys speed, so an
         // allocation that fails all the same (the device filled up since hipMemGetInfo) is remembered for this capacity and the fp32 kernel answers
-        if (!automatic) { if (ix->tiles16.ensure((size_t)ix->cap_rows * ix->dp16 * 2, HB_GROW_EXACT)) return -1; }
-        else if (ix->tiles16.try_ensure((size_t)ix->cap_rows * ix->dp16 * 2, HB_GROW_EXACT)) {
-            ix->f16_declined_cap = ix->cap_rows;
+        if (copy.make(ix->cap_rows, (size_t)ix->dp16 * 2, automatic)) {
+            if (!automatic) return -1;
             f16 = false; why = HB_WHY_MEMORY;
             if (esc == 0) { ix->last_fp16_fallbacks = 0; ix->last_fp16_escalated = 0; }
-        }
-        if (ix->tiles16) {
-            HB_HIP(hipMemsetAsync(ix->tiles16, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0));
-            ix->f16_cap_rows = ix->cap_rows;
+        } else if (hipMemsetAsync(copy.tiles, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0) != hipSuccess) {
+            copy.drop();
+            return hb_fail("hb_index_search: zeroing the fp16 copy of the bank failed: " + std::string(hipGetErrorString(hipGetLastError())));
         }
     }
-    if (f16 && ix->f16_rows < ix->ntotal) {
-        const int64_t rt0 = ix->f16_rows / 32, need_rt = (ix->ntotal + 31) / 32;
+    if (f16 && copy.m.behind(ix->ntotal)) {
+        int64_t rt0 = 0, n_rt = 0;
+        copy.m.pending(ix->ntotal, &rt0, &n_rt);
         // (hb_index_set_fp16_centre: the rows as fl32(b - mu) with their per-row term, hbird_f16_centre.hip; a bank without a usable mean: the plain copy)
         int centred = 0;
         if (ix->fp16_centre && hb_centre_convert(ix, s0, &centred)) return -1;
-        if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, ix->tiles16.as<_Float16>(), ix->dp16 / 16, need_rt - rt0, rt0, ix->f16_flag, s0)) return -1;
-        ix->f16_rows = ix->ntotal;
-        HB_HIP(hipMemcpyAsync(&ix->f16_overflow, ix->f16_flag, 4, hipMemcpyDeviceToHost, s0));
+        if (!centred && hb_launch_tiles_to_f16(ix->tiles, ix->g8, copy.tiles.as<_Float16>(), ix->dp16 / 16, n_rt, rt0, copy.flag, s0)) return -1;
+        copy.m.converted(ix->ntotal);
+        HB_HIP(hipMemcpyAsync(&copy.overflow, copy.flag, 4, hipMemcpyDeviceToHost, s0));
         HB_HIP(hipStreamSynchronize(s0));
     }
-    if (f16 && ix->f16_overflow) {
+    if (f16 && copy.overflow) {
         f16 = false; why = HB_WHY_OVERFLOW;
         if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; }
-        if (automatic) ix->drop_tiles16();      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
+        if (automatic) copy.drop();      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
     }
-    // ... and the row-major fp32 copy for the re-rank (hbird_knn_f16.hip).  Automatic: by the bank's size (below; a 10 M x 768 bank:
-    // 30.7 GB of tiles + 15.4 GB of fp16 tiles + 30.7 GB of rows, of 288)
-    if (f16 && ix->rerank_copy != 2) {
-        const int rs = (ix->g8 * 8 + 31) / 32 * 32;
-        if (ix->rows32 && (ix->rows32_cap_rows != ix->cap_rows || ix->rows32_rs != rs)) ix->drop_rows32();
-        if (!ix->rows32 && (ix->rerank_copy == 1 || ix->rows32_declined_cap != ix->cap_rows)) {
-            const size_t need = (size_t)ix->cap_rows * rs * 4;
-            size_t free_b = 0, total_b = 0;
-            HB_HIP(hipMemGetInfo(&free_b, &total_b));
-            ix->rows32_declined_cap = ix->cap_rows;     // (cleared below when the copy is made)
-            // automatic (round 6, by measurement: profiles/r06/final/fp16_residency.json): what the copy saves is a few ms of re-rank per search
-            // (about 4 ms for 21,904 queries x 64 candidates), whatever the bank's size, and what it costs is the bank once more.  At 300,000
-            // x 768 that is 17 % of a search for 0.9 GB; at 10 M x 768 1.5 % for 30.7 GB, at 20 M x 1024 and 27.7 M x 768 0.4 % for 83-85 GB.
-            // So only banks of up to 4e9 values (16 GB of fp32: 5.2 M x 768) get it -- a use_fp16 index of a bigger bank holds 1.5 x the bank
-            // (fp32 tiles for the exact re-rank and the fp32 searches, fp16 tiles for the candidate pass), not 2.5 x -- and, as before, only
-            // where the three copies stay within 55 % of the device with room to spare: the search's own workspace is allocated after the
-            // copy, and a device shared with a model or another rank must not be filled to the brim by an optional copy.  An allocation that
-            // fails all the same just means no copy.
-            const size_t bank_b = (size_t)ix->cap_rows * ix->dp * 4;
-            if (ix->rerank_copy == 1 || (bank_b <= (size_t)16e9 && bank_b + bank_b / 2 + need <= total_b / 100 * 55 &&
-                                         free_b > need + std::max<size_t>(total_b / 16, (size_t)2 << 30))) {
-                if (!ix->rows32.try_ensure(need, HB_GROW_EXACT)) { ix->rows32_cap_rows = ix->cap_rows; ix->rows32_rs = rs; ix->rows32_rows = 0; ix->rows32_declined_cap = -1; }
-                else if (ix->rerank_copy == 1) return hb_fail("hb_index_search: no memory for the re-rank copy of the bank");
-            }
-        }
-        if (ix->rows32 && ix->rows32_rows < ix->ntotal) {
-            const int64_t rt0 = ix->rows32_rows / 32, need_rt = (ix->ntotal + 31) / 32;
-            if (hb_launch_tiles_to_row_copy(ix->tiles, ix->g8, ix->rows32, rs, need_rt - rt0, rt0, s0)) return -1;
-            ix->rows32_rows = ix->ntotal;
-        }
+    return 0;
+}
+// ... and the row-major fp32 copy for the re-rank (hbird_knn_f16.hip).  Whether an automatic index gets one: hb_rerank_copy_choose
+// (hbird_calibrate.cpp); a copy found not to fit is not asked about again until the capacity changes or the setting is set again
+static int knn_row_copy_upkeep(hb_index* ix, hipStream_t s0) {
+    if (ix->rerank_copy == 2) return 0;
+    hb_row_copy& copy = ix->row_copy;
+    const int rs = (ix->g8 * 8 + 31) / 32 * 32;
+    if (copy.rows && !copy.has(ix->cap_rows, rs)) copy.drop();
+    if (!copy.rows && (ix->rerank_copy == 1 || !copy.m.declined_at(ix->cap_rows))) {
+        size_t free_b = 0, total_b = 0;
+        HB_HIP(hipMemGetInfo(&free_b, &total_b));
+        copy.m.declined(ix->cap_rows);     // (cleared when the copy is made; an allocation that fails all the same just means no copy -- unless the caller asked for it)
+        if (hb_rerank_copy_choose(ix->rerank_copy, (uint64_t)ix->cap_rows * ix->dp * 4, (uint64_t)ix->cap_rows * rs * 4, free_b, total_b) &&
+            !copy.make(ix->cap_rows, rs) && ix->rerank_copy == 1) return hb_fail("hb_index_search: no memory for the re-rank copy of the bank");
+    }
+    if (copy.rows && copy.m.behind(ix->ntotal)) {
+        int64_t rt0 = 0, n_rt = 0;
+        copy.m.pending(ix->ntotal, &rt0, &n_rt);
+        if (hb_launch_tiles_to_row_copy(ix->tiles, ix->g8, copy.rows, rs, n_rt, rt0, s0)) return -1;
+        copy.m.converted(ix->ntotal);
     }
     return 0;
 }
@@ -1032,7 +1021,7 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     float* cand_dist = ix->cand.as<float>((size_t)nq * kc * 8);
     knn16_args h;
     h.wg_stamp = a.wg_stamp;
-    h.bank16 = ix->tiles16.as<const _Float16>(); h.binit = centred ? ix->centre.init16 : ix->binit; h.q16 = ix->q16.as<const _Float16>(); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
+    h.bank16 = ix->copy16.tiles.as<const _Float16>(); h.binit = centred ? ix->copy16.centre.init16 : ix->binit; h.q16 = ix->q16.as<const _Float16>(); h.segs = a.segs; h.wg_off = a.wg_off; h.wg_end = a.wg_end;
     h.state_s = a.state_s; h.state_i = a.state_i; h.g16 = ix->dp16 / 16; h.k = kc; h.klw = klw;
     h.state_cnt = a.state_cnt; h.state_thr = a.state_thr; h.gthr = a.gthr;
     h.wg_member = a.wg_member; h.prog = a.prog; h.cl = a.cl; h.lag = a.lag; h.cl_stats = a.cl_stats;
@@ -1051,10 +1040,10 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     const float* q_aux = c.q_aux;
     const hb_rerank_args ra{ix->binit, ix->d, q_dev, q_aux, cand_idx, cand_dist, q_aux + nq, ix->bmax, cert, kc, nq, k, id_base, ix->metric, out_metric,
                             ix->ntotal, out_idx, out_dist, hb_rerank_seeds{esc == 1 ? c.seed : nullptr, kth, flo}, cview};
-    const bool row_copy = ix->rows32 && ix->rerank_copy != 2 && ix->rows32_rows >= ix->ntotal;
+    const bool row_copy = ix->row_copy.rows && ix->rerank_copy != 2 && !ix->row_copy.m.behind(ix->ntotal);
     // an excluding search: the re-rank that drops every query's group among its candidates (hbird_exclude_screen.hip; from the tiles)
     if (c.groups ? hb_launch_excl_screen_rerank(ra, ix->tiles, ix->g8, ix->row_groups, ix->row_groups_n, c.groups, s)
-                 : hb_launch_rerank(ra, ix->tiles, ix->g8, row_copy ? ix->rows32 : nullptr, ix->rows32_rs, s)) return -1;
+                 : hb_launch_rerank(ra, ix->tiles, ix->g8, row_copy ? ix->row_copy.rows : nullptr, ix->row_copy.rs, s)) return -1;
     if (knn_read_time(ix, c)) return -1;
     // Queries whose certificate failed are searched again.  ESCALATION (round 6): first by a second fp16 pass with k' = 256 candidates
     // (the certificate compares the exact k-th best with the fp16 score of rank k': four times the ranks apart) whose pools start from
@@ -1122,8 +1111,9 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     if (esc == 0) ix->screen.state = HB_SCREEN_NONE;      // (hb_index_last_screen: whatever an earlier search left is about to go)
     knn_path path;
     if (knn_choose_path(ix, c, nq, k, &path)) return -1;
-    if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_screen_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;
-    path.centred = path.f16 && ix->fp16_centre && ix->centre.active;
+    if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_fp16_copy_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;
+    if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_row_copy_upkeep(ix, s)) return -1;
+    path.centred = path.f16 && ix->fp16_centre && ix->copy16.centre.active;
     if (c.groups && !path.f16) {      // an excluding search goes where a plain search at (nq, k) takes the candidate pass, and nowhere else
         if (esc != 0) return hb_fail("hb_index_search_excluding: the second pass of an excluding search left the fp16 screen");
         c.excl->served = 0;
@@ -1162,24 +1152,31 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     return knn_search_f32(ix, c, p, wl, ws, nq, k, id_base, out_metric, out_idx, out_dist, s);
 }
 
-// q_tiles / q_aux must already be prepared by the caller (hb_index_search).
-int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
+int hb_prepare_queries(hb_index* ix, const float* q_dev, int64_t nq) {
+    const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
+    if (ix->q_tiles.ensure((size_t)nqp * ix->dp * 4, HB_GROW_EXACT)) return -1;
+    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
+    if (hb_launch_rows_to_tiles(q_dev, nq, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, ix->stream)) return -1;
+    return hb_launch_query_aux(q_dev, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream);
+}
+// the level-0 call: a caller's search, by the index's settings, on the queries hb_prepare_queries took
+static knn_call knn_level0_call(const hb_index* ix) {
     knn_call c;
     c.fp16 = ix->fp16; c.timed = ix->time_kernels != 0; c.q_aux = ix->q_aux; c.score_out = ix->score_output != 0;
-    return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
+    return c;
+}
+
+// q_tiles / q_aux must already be prepared by the caller (hb_index_search).
+int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
+    return knn_search(ix, knn_level0_call(ix), q_dev, nq, k, id_base, out_idx, out_dist);
 }
 
 // An excluding search on the screen (hbird_internal.h): the level-0 call of a plain search at k -- query tiles and norms as hb_index_search
 // prepares them -- with the queries' groups in its context.  The caller has checked 1 <= k <= 128, nq > 0, ntotal > 0 and the group table.
 int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, const int32_t* qgroups, int64_t* out_idx, float* out_dist,
                             hb_excl_screen_result* res) {
-    const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
-    if (ix->q_tiles.ensure((size_t)nqp * ix->dp * 4, HB_GROW_EXACT)) return -1;
-    if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
-    if (hb_launch_rows_to_tiles(q_dev, nq, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, ix->stream)) return -1;
-    if (hb_launch_query_aux(q_dev, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream)) return -1;
-    knn_call c;
-    c.fp16 = ix->fp16; c.timed = ix->time_kernels != 0; c.q_aux = ix->q_aux; c.score_out = ix->score_output != 0;
+    if (hb_prepare_queries(ix, q_dev, nq)) return -1;
+    knn_call c = knn_level0_call(ix);
     c.groups = qgroups; c.excl = res;
     return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
 }

@@ -157,15 +157,13 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
     }
     // max bank-row norm over the new rows, as hb_index_add: the fp16 screen's certificate is bounded by it
     if (hb_launch_bnorm_max(dst->bnorm + row0, n, dst->bmax, s)) return -1;
-    dst->ntotal += n; dst->screen.state = HB_SCREEN_NONE;
+    dst->ntotal += n;
     if (labs) {
         // counts that were valid in the source stay valid: no conversion happened, so there is nothing new to check
         if (dst->lab_checked == dst->nlabels) dst->lab_checked = dst->nlabels + n;
         dst->nlabels += n;
     }
-    // (the lazy copies -- fp16 tiles, their centred form, rows32 -- follow at the next screened search, as after hb_index_add:
-    // f16_rows / centre.rows / rows32_rows < ntotal)
-    return 0;
+    return dst->bank_changed(HB_BANK_APPENDED);      // (the lazy copies follow at the next screened search, as after hb_index_add)
 }
 
 extern "C" int hb_index_select_rows(const hb_index_t* src, const int64_t* ids, int64_t n, int ids_on_device, hb_index_t** out) {

@@ -110,6 +110,7 @@ SIGNATURES = {
     "hb_f16_adapt_replay": (c_int, [c_int, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int)]),
     "hb_exact_screen_replay": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int, c_int, c_int,
                                        c_uint64, c_uint64, c_uint64, c_uint64, POINTER(c_int)]),
+    "hb_rerank_copy_replay": (c_int, [c_int, c_uint64, c_uint64, c_uint64, c_uint64]),
     "hb_knn_plan_replay": (c_int, [POINTER(c_int64), c_int, POINTER(c_int64), c_int]),
     "hb_certificate_bound_replay": (c_int, [POINTER(c_double), c_int, POINTER(c_double), c_int]),
     "hb_set_layout_form": (c_int, [c_int]),
@@ -187,7 +188,7 @@ def lib() -> ctypes.CDLL:
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()):
-            if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
+            if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree
             fn.restype = res

@@ -72,7 +72,16 @@ def test_the_read_out_is_host_bookkeeping_and_no_kernel_changed():
     assert knn.count("HB_SCREEN_VALID") == 1 and knn.count("HB_SCREEN_OVERWRITTEN") == 1 and knn.count("HB_SCREEN_NONE") == 1
     f16 = knn[knn.index("static int knn_search_f16"):knn.index("static int knn_search_f32")]
     assert "HB_SCREEN_VALID" in f16 and f16.index("HB_SCREEN_VALID") > f16.index("hb_launch_rerank")
-    assert capi.count("HB_SCREEN_NONE") >= 3      # reset, add, a capacity change (hb_index_add_from: hbird_select.hip)
+    # every change of the bank clears it in ONE place, hb_index::bank_changed: reset, add, a capacity change, and hb_index_add_from (hbird_select.hip)
+    hook = capi[capi.index("int hb_index::bank_changed("):]
+    hook = hook[:hook.index("\n}\n")]
+    assert capi.count("HB_SCREEN_NONE") == 1 and "screen.state = HB_SCREEN_NONE" in hook
+    for entry, event in (("hb_index_reset", "HB_BANK_EMPTIED"), ("hb_index_reserve", "HB_BANK_MOVED"), ("hb_index_add", "HB_BANK_APPENDED")):
+        body = capi[capi.index('extern "C" int %s(' % entry):]
+        assert body[:body.index("\n}\n")].count("bank_changed(%s)" % event) == 1, entry
+    select = open(os.path.join(csrc, "hbird_select.hip")).read()
+    body = select[select.index('extern "C" int hb_index_add_from('):]
+    assert body[:body.index("\n}\n")].count("bank_changed(HB_BANK_APPENDED)") == 1 and "HB_SCREEN_NONE" not in select
 
 
 # ---------------------------------------------------------------- the exact worlds

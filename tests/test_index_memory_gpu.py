@@ -1,6 +1,6 @@
 """Every device allocation of an index is a member of one owning type (csrc/hbird_devbuf.h), and hb_debug_live_allocations counts what is
 live, exact to the byte.  Indexes on a 16,384 x 64 bank are taken through every site that allocates, grows, moves or drops a buffer -- the
-fp16 candidate pass with its second pass and the fp32 search of what is left (fb, fb1, stamp_keep, cand, q16, tiles16, rows32), the centred
+fp16 candidate pass with its second pass and the fp32 search of what is left (fb, fb1, stamp_keep, cand, q16, copy16.tiles, row_copy.rows), the centred
 copy on and off, k > 256, a larger query batch, an append beyond the capacity, label rows as counts, as fp32 and of another width, an
 excluding search through its second rung, views, dropping the re-rank copy -- and every search is held, as int32 words of ids and
 distances, to an index pinned to the fp32 kernel that is taken through the same appends.  After close() on every index, views included,
