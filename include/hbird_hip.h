@@ -106,8 +106,9 @@ int hb_index_gather_labels(hb_index_t* ix, const int64_t* ids, int64_t n, int64_
  * configurations from one neighbour list per query -- are declared in hbird_hip_grid.h, which this header includes at its end. */
 /* Searches that exclude one group of bank rows per query (leave-one-image-out evaluation) -- hb_index_set_row_groups, hb_index_search_excluding,
  * hb_exclude_filter, hb_index_last_exclusion, hb_exclude_plan_replay -- are declared in hbird_hip_exclude.h, which this header includes at its end. */
-/* The read-out of the fp16 screen's last candidate pass -- hb_index_last_screen: lists, pass scores and first certificates, for tests of the
- * candidate kernel -- is declared in hbird_hip_screen.h, which this header includes at its end. */
+/* The read-outs of the fp16 screen -- hb_index_last_screen: lists, pass scores and first certificates of the last candidate pass, for tests of
+ * the candidate kernel; hb_index_last_screen_seeds: the seeds it handed on and the second pass' output; hb_index_last_fp16_copy: the plain fp16
+ * copy and its overflow flag -- are declared in hbird_hip_screen.h, which this header includes at its end. */
 /* Excluding searches served by that screen -- hb_index_set_exclude_screen, hb_index_last_exclusion_screen, hb_index_exclude_rerank: the query's
  * group is dropped among the candidates of a plain search at k, under the unchanged certificate -- are declared in hbird_hip_exclude_screen.h,
  * which this header includes at its end. */

@@ -210,6 +210,39 @@ extern "C" int hb_index_last_screen(hb_index_t* ix, int64_t* cand_rows, float* p
     if (certified) HB_HIP(hipMemcpy(certified, ix->fb, (size_t)r.nq, hipMemcpyDeviceToHost));
     return 0;
 }
+extern "C" int hb_index_last_screen_seeds(hb_index_t* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
+                                          float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]) {
+    if (!ix) return hb_fail("hb_index_last_screen_seeds: NULL index handle");
+    if (!info) return hb_fail("hb_index_last_screen_seeds: info is NULL");
+    return hb_screen_seeds_readout(ix, kth0, floor0, certified0, queries1, seed1, cand_rows1, pass_scores1, certified1, kth1, capacity_queries, capacity_queries1, info);
+}
+// The plain fp16 copy, its overflow flag and the query tiles of the last plain pass (include/hbird_hip_screen.h).  Host bookkeeping and copies only.
+extern "C" int hb_index_last_fp16_copy(hb_index_t* ix, uint16_t* bank16, uint16_t* q16, int64_t info[8]) {
+    if (!ix) return hb_fail("hb_index_last_fp16_copy: NULL index handle");
+    if (!info) return hb_fail("hb_index_last_fp16_copy: info is NULL");
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    info[6] = -1;
+    const hb_fp16_copy& copy = ix->copy16;
+    if (!copy.tiles || !copy.flag || !copy.m.has(ix->cap_rows))
+        return hb_fail("hb_index_last_fp16_copy: no fp16 copy for this bank (no screened search yet, a capacity change since, or an automatic index that dropped it)");
+    if (copy.centre.active)
+        return hb_fail("hb_index_last_fp16_copy: the fp16 copy is centred (hb_index_last_centre reads that form)");
+    const int64_t rows = copy.m.rows, n_g = (rows + 31) / 32 * 32;
+    if (n_g > copy.m.cap) return hb_fail("hb_index_last_fp16_copy: the copy holds more rows than it was allocated for");
+    const bool q_ok = copy.q_level >= 0 && !ix->last_centred && !ix->screen.none() && ix->q16 &&
+                      ix->q16.bytes >= (size_t)((copy.q_n + HB_QT - 1) / HB_QT * HB_QT) * ix->dp16 * 2;
+    const int64_t n = q_ok ? copy.q_n : 0, n_qpad = (n + HB_QT - 1) / HB_QT * HB_QT;
+    HB_HIP(hipSetDevice(ix->device));
+    HB_HIP(hipStreamSynchronize(ix->stream));
+    int flag = 0;
+    HB_HIP(hipMemcpy(&flag, copy.flag, 4, hipMemcpyDeviceToHost));
+    info[0] = rows; info[1] = ix->dp16; info[2] = n_g; info[3] = flag; info[4] = copy.overflow; info[5] = n; info[6] = q_ok ? copy.q_level : -1; info[7] = n_qpad;
+    if (q16 && !q_ok)
+        return hb_fail("hb_index_last_fp16_copy: the last search of a caller did not run the plain fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
+    if (bank16 && n_g) HB_HIP(hipMemcpy(bank16, copy.tiles, (size_t)n_g * ix->dp16 * 2, hipMemcpyDeviceToHost));
+    if (q16 && n) HB_HIP(hipMemcpy(q16, ix->q16, (size_t)n_qpad * ix->dp16 * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" int hb_last_search_path(const hb_index_t* ix, int* path, int* reason) {
     if (!ix || !path || !reason) return hb_fail("hb_last_search_path: NULL pointer");
     *path = ix->last_path; *reason = ix->last_reason;

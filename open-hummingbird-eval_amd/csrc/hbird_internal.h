@@ -109,7 +109,20 @@ struct hb_index {
     // what the level-0 candidate pass of the last search left in `cand` (lists, pass scores) and at the start of `fb` (first certificates), for
     // hb_index_last_screen: host bookkeeping only.  Valid from the end of knn_search_f16's level-0 tail until the next level-0 search, a second
     // pass that reuses `cand`, or a change of the bank (reset, add, capacity).
-    struct screen_record { int state = 0; int64_t nq = 0; int kc = 0, klw = 0, centred = 0; } screen;   // state: HB_SCREEN_*
+    // hb_index_last_screen_seeds reads on: the seeds behind the certificates in `fb` (whatever followed), and of a second pass its size and its
+    // own lists (`cand`, `fb1`), the queries sent to it and where their gathered seeds lie in `fb` -- the fp32 search of what is left takes
+    // `state` and the tail of `fb1` only, so all of it stays until the next search of a caller.
+    struct screen_record {
+        int state = 0; int64_t nq = 0; int kc = 0, klw = 0, centred = 0;      // state: HB_SCREEN_*
+        int excluding = 0;                      // the search dropped row groups (hb_index_search_excluding): no seeds read-out
+        int64_t n1 = 0;                         // queries of the second fp16 pass (0: none ran)
+        int kc1 = 0, klw1 = 0;
+        size_t o_seed1 = 0;                     // byte offset in `fb` of the second pass' gathered seeds [n1]
+        std::vector<int64_t> bad;               // the level-0 queries sent to the second pass, ascending
+        bool none() const { return state == HB_SCREEN_NONE; }
+        bool second_pass_ran() const { return state == HB_SCREEN_OVERWRITTEN; }
+        void new_search(bool excl) { excluding = excl ? 1 : 0; n1 = 0; kc1 = klw1 = 0; o_seed1 = 0; bad.clear(); }
+    } screen;
     hb_f16_adapt f16_adapt;                              // adaptive use of use_fp16 in mode 2 (hbird_calibrate.h): moving averages of the failing shares
     hb_dev<char> bigk;                                   // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
     hb_schedule sched_esc; hb_dev<char> sched_esc_dev;   // the nested searches' work list (the caller's stays cached)
@@ -161,6 +174,9 @@ int hb_prepare_queries(hb_index* ix, const float* q_dev, int64_t nq);
 int hb_launch_tiles_to_rows(const float* tiles, int g8, int d, const int64_t* ids, int64_t n, int64_t id_base, int64_t ntotal,
                             float* out, hipStream_t s);
 int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
+// hb_index_last_screen_seeds (hbird_knn.hip, beside the level workspaces it reads)
+int hb_screen_seeds_readout(hb_index* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
+                            float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]);
 int hb_launch_tiles_to_f16(const float* t32, int g8, _Float16* t16, int g16, int64_t n_row_tiles, int64_t rt0, int* overflow,
                            hipStream_t s);
 int hb_launch_tiles_to_row_copy(const float* t32, int g8, float* rows, int rs, int64_t n_row_tiles, int64_t rt0, hipStream_t s);

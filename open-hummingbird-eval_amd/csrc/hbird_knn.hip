@@ -992,7 +992,7 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
         c.excl->sent1 = nf;
     }
     if (!again16) ix->last_fp16_fallbacks = nf;
-    if (again16) ix->screen.state = HB_SCREEN_OVERWRITTEN;      // (the second pass merges into ix->cand)
+    if (again16) { ix->screen.state = HB_SCREEN_OVERWRITTEN; ix->screen.bad = bad; ix->screen.o_seed1 = o_seed; }      // (the second pass merges into ix->cand)
     if (!rc) rc = knn_search(ix, nested, d_q, nf, k, id_base, d_fi, d_fd);
     if (esc == 0) ix->last_fp16_escalated = nf;
     if (esc == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks);      // (an excluding search's failures say nothing about plain ones)
@@ -1059,6 +1059,8 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     const int64_t nf = (int64_t)bad.size();
     if (esc == 0) { ix->screen.nq = nq; ix->screen.kc = kc; ix->screen.klw = klw; ix->screen.centred = centred ? 1 : 0; ix->screen.state = HB_SCREEN_VALID; }      // (cand and the certificates are complete: the stream is idle)
     if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
+    if (esc == 1) { ix->screen.n1 = nq; ix->screen.kc1 = kc; ix->screen.klw1 = klw; }      // (hb_index_last_screen_seeds)
+    if (!centred) { ix->copy16.q_n = nq; ix->copy16.q_level = esc; }      // (hb_index_last_fp16_copy)
     if (esc == 0 && nf == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, 0, 0);
     if (c.groups) {
         if (esc == 0) { c.excl->served = 1; c.excl->kc = kc; c.excl->centred = centred ? 1 : 0; c.excl->certified0 = nq - nf; }
@@ -1108,7 +1110,7 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     if (k > 256) return hb_launch_knn_bigk(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
     hipStream_t s = ix->stream;
     const int esc = c.esc;
-    if (esc == 0) ix->screen.state = HB_SCREEN_NONE;      // (hb_index_last_screen: whatever an earlier search left is about to go)
+    if (esc == 0) { ix->screen.state = HB_SCREEN_NONE; ix->screen.new_search(c.groups != nullptr); }      // (hb_index_last_screen: whatever an earlier search left is about to go)
     knn_path path;
     if (knn_choose_path(ix, c, nq, k, &path)) return -1;
     if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_fp16_copy_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;
@@ -1179,4 +1181,47 @@ int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k,
     knn_call c = knn_level0_call(ix);
     c.groups = qgroups; c.excl = res;
     return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
+}
+
+// What the chain behind the first candidate pass left (hb_index_last_screen_seeds, include/hbird_hip_screen.h): host bookkeeping and copies, no
+// launch.  Level 0 lies in `fb` behind the certificates (knn_level_buf), the second pass' gathered seeds further back in `fb`, its lists in
+// `cand` and its own certificates and k-th scores in `fb1`.
+int hb_screen_seeds_readout(hb_index* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
+                            float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]) {
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    const hb_index::screen_record& r = ix->screen;
+    if (r.none() || !ix->fb)
+        return hb_fail("hb_index_last_screen_seeds: the last search did not take the fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
+    if (r.excluding) return hb_fail("hb_index_last_screen_seeds: the last search was an excluding one (hb_index_search_excluding): its seeds are not handed out");
+    const knn_level_buf l0(ix, 0, r.nq);
+    const int64_t n1 = r.second_pass_ran() ? r.n1 : 0;
+    if (ix->fb.bytes < l0.o_rows) return hb_fail("hb_index_last_screen_seeds: the level-0 workspace is smaller than its record says");
+    if (n1 > 0) {
+        const knn_level_buf l1(ix, 1, n1);
+        if ((int64_t)r.bad.size() != n1 || r.kc1 <= 0 || !ix->cand || !ix->fb1 || ix->cand.bytes < (size_t)n1 * r.kc1 * 12 || ix->fb1.bytes < l1.o_rows ||
+            r.o_seed1 < l0.o_rows || ix->fb.bytes < r.o_seed1 + (size_t)n1 * 4)
+            return hb_fail("hb_index_last_screen_seeds: the second pass' buffers are smaller than its record says");
+    }
+    info[0] = r.nq; info[1] = r.kc; info[2] = n1; info[3] = n1 ? r.kc1 : 0; info[4] = n1 ? r.klw1 : 0; info[5] = r.centred; info[6] = ix->last_fp16_fallbacks;
+    info[7] = r.klw;
+    HB_HIP(hipSetDevice(ix->device));
+    HB_HIP(hipStreamSynchronize(ix->stream));
+    const bool want0 = kth0 || floor0 || certified0, want1 = queries1 || seed1 || cand_rows1 || pass_scores1 || certified1 || kth1;
+    if (want0 && capacity_queries < r.nq)
+        return hb_fail("hb_index_last_screen_seeds: room for " + std::to_string(capacity_queries) + " queries, the last search had " + std::to_string(r.nq));
+    if (want1 && capacity_queries1 < n1)
+        return hb_fail("hb_index_last_screen_seeds: room for " + std::to_string(capacity_queries1) + " queries of the second pass, it had " + std::to_string(n1));
+    if (kth0) HB_HIP(hipMemcpy(kth0, l0.kth(), (size_t)r.nq * 4, hipMemcpyDeviceToHost));
+    if (floor0) HB_HIP(hipMemcpy(floor0, l0.flo(), (size_t)r.nq * 4, hipMemcpyDeviceToHost));
+    if (certified0) HB_HIP(hipMemcpy(certified0, ix->fb, (size_t)r.nq, hipMemcpyDeviceToHost));
+    if (n1 == 0) return 0;
+    const knn_level_buf l1(ix, 1, n1);
+    const size_t n = (size_t)n1 * r.kc1;
+    if (queries1) std::copy(r.bad.begin(), r.bad.end(), queries1);
+    if (seed1) HB_HIP(hipMemcpy(seed1, ix->fb + r.o_seed1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+    if (cand_rows1) HB_HIP(hipMemcpy(cand_rows1, ix->cand, n * 8, hipMemcpyDeviceToHost));
+    if (pass_scores1) HB_HIP(hipMemcpy(pass_scores1, ix->cand + n * 8, n * 4, hipMemcpyDeviceToHost));
+    if (certified1) HB_HIP(hipMemcpy(certified1, ix->fb1, (size_t)n1, hipMemcpyDeviceToHost));
+    if (kth1) HB_HIP(hipMemcpy(kth1, l1.kth(), (size_t)n1 * 4, hipMemcpyDeviceToHost));
+    return 0;
 }

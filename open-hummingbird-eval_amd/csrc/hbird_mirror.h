@@ -52,6 +52,9 @@ struct hb_fp16_copy {
     hb_bank_mirror m;
     hb_dev<int> flag; int overflow = 0;      // sticky device flag and its host image: a finite bank value overflowed fp16, the fp32 kernel serves this bank
     hb_centre_state centre;
+    // hb_index_last_fp16_copy: host bookkeeping of the last PLAIN candidate pass, whose query tiles lie in the index's q16
+    int64_t q_n = 0;                // its queries
+    int q_level = -1;               // 0: a caller's pass, 1: the second pass over its uncertified queries, -1: none yet
 
     // The tiles for a bank of `cap` rows of row_bytes each; what there was goes first.  quiet (the automatic state, where the copy only buys
     // speed): a failure is noted as "declined at cap" and reported to nobody; else it is the caller's error (hb_fail).  -> 0 / -1

@@ -10,7 +10,8 @@
 // What the re-rank leaves for an ESCALATION of the queries whose certificate fails (hb_launch_knn), and what it takes from the pass before:
 //   seed_in  [query] (second pass only): the fp16-score floor this pass ran under -- every row with an fp16 score >= it was offered to the
 //            pools, so a candidate list that is NOT full holds every such row: the rows outside score below the floor in fp16, hence below
-//            floor + E exactly, and the answer is exact when its k-th best exceeds that;
+//            floor + E exactly, and the answer is exact when its k-th best exceeds that: plain  kth > seed + E ;  centred, in the pass'
+//            units as the floor was formed:  kth - c_q > seed + E' ;
 //   kth_out  [query]: the exact k-th best score among this pass's candidates -- a lower bound of the true k-th best: the floor of an fp32
 //            search of this query (ties pass: floor_from_key);
 //   floor_out[query]: kth - 1.001 E, a hair lower: every row that can still enter the top k has an exact score >= kth, hence an fp16 score
@@ -33,7 +34,9 @@ struct hb_rerank_args {
 
 template <bool CENTRED>
 __device__ __forceinline__ bool hb_rerank_finish(const hb_rerank_seeds& sd, int64_t qi, bool ok, bool list_not_full, bool have_kth, float s, float E, float cq) {
-    if (sd.seed_in && list_not_full && have_kth && !ok) ok = CENTRED ? s > sd.seed_in[qi] + cq + E : s > sd.seed_in[qi] + E;
+    // (centred: compared in the pass' units, as floor_out was formed -- s - cq is rounded at ITS size, seed + cq at the size of c_q, whose ulp
+    // exceeds the 0.001 E' between floor and rule wherever |c_q| 2^-24 > 0.001 E': a complete first answer then passed or failed by rounding)
+    if (sd.seed_in && list_not_full && have_kth && !ok) ok = CENTRED ? s - cq > sd.seed_in[qi] + E : s > sd.seed_in[qi] + E;
     if (sd.kth_out) {
         const bool fin = have_kth && E < INFINITY && fabsf(s) < INFINITY && (!CENTRED || fabsf(cq) < INFINITY);      // (false for NaN as well)
         float f = CENTRED ? s - cq - 1.001f * E : s - 1.001f * E;

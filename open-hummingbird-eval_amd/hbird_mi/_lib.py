@@ -155,6 +155,9 @@ SIGNATURES_EXCLUDE = {
 # ... and include/hbird_hip_screen.h (the read-out of the fp16 screen's last candidate pass: lists, pass scores, first certificates)
 SIGNATURES_SCREEN = {
     "hb_index_last_screen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    # ... the seeds level 0 handed on and the second pass' output; the plain fp16 copy with its overflow flag
+    "hb_index_last_screen_seeds": (c_int, [c_void_p] + [c_void_p] * 9 + [c_int64, c_int64, POINTER(c_int64)]),
+    "hb_index_last_fp16_copy": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
 }
 
 # ... and include/hbird_hip_exclude_screen.h (excluding searches served by the fp16 screen, csrc/hbird_exclude_screen.hip)

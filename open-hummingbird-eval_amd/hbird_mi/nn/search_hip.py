@@ -661,6 +661,45 @@ class HipFlatIndex:
         _lib.check(lib.hb_index_last_screen(self._h, _ptr(rows), _ptr(scores), _ptr(cert), nq, info))
         return {"rows": rows, "scores": scores, "certified": cert, "nq": nq, "kc": kc, "centred": bool(info[2]), "klw": int(info[3])}
 
+    def last_screen_seeds(self) -> dict:
+        """What the chain behind the first candidate pass left (hb_index_last_screen_seeds, include/hbird_hip_screen.h), as numpy arrays.
+        Level 0: kth0 / floor0 float32 [nq], certified0 uint8 [nq].  Level 1, where a second fp16 pass ran (n1 > 0; else empty arrays):
+        queries1 int64 [n1] (ascending level-0 query numbers), seed1 float32 [n1] (as gathered on the device), rows1 int64 [n1, kc1] and
+        scores1 float32 [n1, kc1] (that pass' merged lists, conventions of last_screen), certified1 uint8 [n1], kth1 float32 [n1]; and nq,
+        kc0, klw0, n1, kc1, klw1, centred, n2 (queries that reached the fp32 kernel).  Raises when the last search did not take the fp16
+        path, was an excluding one, or after reset / add / a capacity change."""
+        lib = _lib.lib()
+        info = (ctypes.c_int64 * 8)()
+        _lib.check(lib.hb_index_last_screen_seeds(self._h, *([None] * 9), 0, 0, info))
+        nq, kc0, n1, kc1 = (int(info[i]) for i in range(4))
+        kth0, floor0, cert0 = np.empty(nq, dtype=np.float32), np.empty(nq, dtype=np.float32), np.empty(nq, dtype=np.uint8)
+        queries1, seed1 = np.empty(n1, dtype=np.int64), np.empty(n1, dtype=np.float32)
+        rows1, scores1 = np.empty((n1, kc1), dtype=np.int64), np.empty((n1, kc1), dtype=np.float32)
+        cert1, kth1 = np.empty(n1, dtype=np.uint8), np.empty(n1, dtype=np.float32)
+        lvl1 = [_ptr(a) if n1 else None for a in (queries1, seed1, rows1, scores1, cert1, kth1)]
+        _lib.check(lib.hb_index_last_screen_seeds(self._h, _ptr(kth0), _ptr(floor0), _ptr(cert0), *lvl1, nq, n1, info))
+        return {"nq": nq, "kc0": kc0, "klw0": int(info[7]), "n1": n1, "kc1": kc1, "klw1": int(info[4]), "centred": bool(info[5]), "n2": int(info[6]),
+                "kth0": kth0, "floor0": floor0, "certified0": cert0, "queries1": queries1, "seed1": seed1, "rows1": rows1, "scores1": scores1,
+                "certified1": cert1, "kth1": kth1}
+
+    def last_fp16_copy(self, queries: bool = True) -> dict:
+        """The plain fp16 copy (hb_index_last_fp16_copy, include/hbird_hip_screen.h): bank16 uint16 (the raw fp16 tiles of the converted row
+        tiles; layout in hbird_hip_centre.h), rows, dp16, flag (the device's sticky overflow flag) and flag_host (its host image); of the last
+        plain candidate pass n, level (0: the caller's, 1: the second pass; -1 and n = 0 when not valid) and, with queries=True, q16 uint16
+        (raw tiles of 256 ceil(n / 256) queries).  Raises while there is no plain copy, and with queries=True when the last search of a caller
+        did not run the plain pass or the bank has changed since."""
+        lib = _lib.lib()
+        info = (ctypes.c_int64 * 8)()
+        _lib.check(lib.hb_index_last_fp16_copy(self._h, None, None, info))
+        rows, dp16, n_g, _, _, n, _, n_qpad = (int(v) for v in info)
+        bank16 = np.empty(n_g * dp16, dtype=np.uint16)
+        q16 = np.empty(max(n_qpad * dp16, 1), dtype=np.uint16)
+        _lib.check(lib.hb_index_last_fp16_copy(self._h, _ptr(bank16) if n_g else None, _ptr(q16) if queries else None, info))
+        out = {"rows": rows, "dp16": dp16, "flag": int(info[3]), "flag_host": int(info[4]), "n": n, "level": int(info[6]), "bank16": bank16}
+        if queries:
+            out["q16"] = q16[:n_qpad * dp16]
+        return out
+
     def set_variant(self, variant: int):
         _lib.check(_lib.lib().hb_index_set_variant(self._h, int(variant)))
 

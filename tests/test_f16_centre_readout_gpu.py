@@ -17,7 +17,8 @@ tests/test_f16_centre_readout_cpu.py runs on its host model and on the wrong var
     query shapes     nq = 1, 70, 300; one query with a NaN component
     second pass      level 1, n = the failing queries, their c_q and ||q - t mu|| gathered in ascending order, t and init16 untouched
     zero mean        no centred copy: the read-out refuses
-    view             a select_rows view derives the mean of ITS rows"""
+    view             a select_rows view derives the mean of ITS rows
+    shards           a HipMultiIndex over two and three unequal row shards: every shard's conversion against ITS rows"""
 import numpy as np
 import pytest
 import torch
@@ -155,3 +156,38 @@ def test_zero_mean_bank_and_the_refusals(cuda_device):
     with pytest.raises(_lib.HbirdHipError, match="no active centred copy"):
         jx.last_centre(queries=False)
     jx.close()
+
+
+@pytest.mark.parametrize("parts", [2, 3])
+def test_every_shard_of_a_multi_index_converts_with_its_own_mean(cuda_device, parts):
+    """A HipMultiIndex over [0, 0] and [0, 0, 0], planned for 4,000 rows and given 5,003: unequal shards (2,000 + 3,003; 1,334 + 1,334 + 2,335),
+    the last one ending inside a row tile.  Each shard derives mu, g, cmax and its tiles from ITS rows and t, c_q, the query tiles from the
+    search's queries: last_centre() per shard against the same references as a single index; the merged result is the fp32 search's."""
+    from hbird_mi.nn.search_hip import HipMultiIndex
+    N, D = 5003, 136
+    for metric, kind in ((0, "float"), (1, "exact")):
+        W = R.world(kind, N, D, 70)
+        bank, q = torch.from_numpy(W["bank"]).to(cuda_device), torch.from_numpy(W["queries"]).to(cuda_device)
+        held = HipFlatIndex(D, metric, 0); held.set_fp16(0); held.add(bank)
+        want = held.search(q, R.K)
+        multi = HipMultiIndex(D, metric, [0] * parts, shard=True)
+        multi.reserve(4000); multi.add(bank); multi.set_fp16(1); multi.set_fp16_centre(True)
+        for ix in multi.indexes:
+            ix.set_fp16_escalation(False)         # (no second pass: every shard's query side stays the caller's)
+        got = multi.search(q, R.K)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1].view(torch.int32), want[1].view(torch.int32)), f"{parts} shards, metric={metric}"
+        sizes = [ix.ntotal for ix in multi.indexes]
+        per = (4000 + parts - 1) // parts
+        assert sizes == [per] * (parts - 1) + [N - per * (parts - 1)] and sizes[-1] % 32 != 0 and len(set(sizes)) > 1, sizes
+        lo, mus = 0, []
+        for s, ix in enumerate(multi.indexes):
+            C = ix.last_centre()
+            rows = W["bank"][lo:lo + sizes[s]]
+            assert (C["rows"], C["n"], C["level"]) == (sizes[s], 70, 0), (s, C["rows"], C["n"], C["level"])
+            bad = R.check_conversion(C, rows, metric, exact=W["exact"], what=f"shard {s}: ")
+            bad.update(R.check_queries(C, W["queries"], exact=W["exact"], what=f"shard {s}: "))
+            _no_complaints(bad, f"{parts} shards, metric={metric}, shard {s}")
+            mus.append(C["mu"].copy())
+            lo += sizes[s]
+        assert all(not np.array_equal(mus[0], m) for m in mus[1:]), "every shard derives its own mu"
+        multi.close(); held.close()
