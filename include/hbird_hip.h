@@ -109,9 +109,9 @@ int hb_index_gather_labels(hb_index_t* ix, const int64_t* ids, int64_t n, int64_
 /* The read-outs of the fp16 screen -- hb_index_last_screen: lists, pass scores and first certificates of the last candidate pass, for tests of
  * the candidate kernel; hb_index_last_screen_seeds: the seeds it handed on and the second pass' output; hb_index_last_fp16_copy: the plain fp16
  * copy and its overflow flag -- are declared in hbird_hip_screen.h, which this header includes at its end. */
-/* Excluding searches served by that screen -- hb_index_set_exclude_screen, hb_index_last_exclusion_screen, hb_index_exclude_rerank: the query's
- * group is dropped among the candidates of a plain search at k, under the unchanged certificate -- are declared in hbird_hip_exclude_screen.h,
- * which this header includes at its end. */
+/* Excluding searches served by that screen -- hb_index_set_exclude_screen, hb_index_last_exclusion_screen, hb_index_exclude_rerank,
+ * hb_index_last_exclusion_seeds: the query's group is dropped among the candidates of a plain search at k, under the unchanged certificate -- are
+ * declared in hbird_hip_exclude_screen.h, which this header includes at its end. */
 /* Sub-bank views -- hb_index_add_from, hb_index_select_rows: an index out of selected rows of another one, gathered on the device -- are
  * declared in hbird_hip_select.h, which this header includes at its end. */
 /* Multi-GPU aggregation tables: borrow device arrays labels[n, c] / norms[n] that cover the GLOBAL id range

@@ -27,7 +27,17 @@
  *   lies strictly above pass_scores[i][kc - 1] + E (or the list ends in -1 and the bank holds fewer than kc rows); out_kth / out_floor [nq]
  *   (each may be NULL): the k-th allowed exact score and that score - 1.001 E, -inf where fewer than k candidates are allowed.  All pointers
  *   are DEVICE pointers.  Runs on the index's stream and synchronises it.  Refuses, before any launch and with hb_last_error set: a NULL handle
- *   or pointer, a missing table or one that does not cover the bank, kc outside [k, 256] or not a multiple of 8, k < 1. */
+ *   or pointer, a missing table or one that does not cover the bank, kc outside [k, 256] or not a multiple of 8, k < 1.
+ * hb_index_last_exclusion_seeds(ix, groups1, left, capacity_queries1, capacity_left, info): what a served excluding search handed on besides the
+ *   values of hb_index_last_screen_seeds (hbird_hip_screen.h, which states their meaning for an excluding search) -- a group gathered for the wrong
+ *   query, or a failing query that never reaches the rungs, shows in no certificate:
+ *     info        {n1: queries of the second pass, 0 when none ran; n_left: queries handed to the rungs}
+ *     groups1[n1] the second pass' query groups as gathered on the device, in the order of hb_index_last_screen_seeds' queries1 (not recomputed)
+ *     left[n_left] the level-0 query numbers handed to the rungs, ascending: what failed the second pass, or level 0 where none ran
+ *   HOST pointers, each may be NULL; a first call with both NULL returns the sizes.  Synchronises the index's stream; launches nothing.
+ *   Fails (hb_last_error says which) on a NULL handle or a NULL info; when the last search of a caller was not an excluding one that the screen
+ *   served, when hb_index_reset, hb_index_add or a capacity change came after it, or when one of the leftover's rungs took the candidate pass
+ *   itself; when a capacity is smaller than the count it stands for. */
 #ifndef HBIRD_HIP_EXCLUDE_SCREEN_H
 #define HBIRD_HIP_EXCLUDE_SCREEN_H
 #define HB_EXCL_SCREEN_SERVED 0      /* reason codes of hb_index_last_exclusion_screen's out[1] */
@@ -41,4 +51,5 @@ int hb_index_last_exclusion_screen(const hb_index_t* ix, int64_t out[8]);
 int hb_index_exclude_rerank(hb_index_t* ix, const float* q, int64_t nq, const int64_t* cand_rows, const float* pass_scores, int kc,
                             const int32_t* qgroups, int k, int64_t id_base, int64_t* out_idx, float* out_dist,
                             unsigned char* out_certified, float* out_kth, float* out_floor);
+int hb_index_last_exclusion_seeds(hb_index_t* ix, int32_t* groups1, int64_t* left, int64_t capacity_queries1, int64_t capacity_left, int64_t info[2]);
 #endif /* HBIRD_HIP_EXCLUDE_SCREEN_H */

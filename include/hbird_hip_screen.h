@@ -42,8 +42,17 @@
  *   capacity_queries: the queries kth0 / floor0 / certified0 have room for; capacity_queries1: the same for the level-1 arrays (not looked at
  *   when none of them is asked for).  Synchronises the index's stream; launches nothing.
  *   Fails (hb_last_error says which) on a NULL handle or a NULL info; when the last search did not take the fp16 candidate pass, or
- *   hb_index_reset, hb_index_add or a capacity change came after it; when that search was an excluding one (hb_index_search_excluding); when a
- *   capacity is smaller than the count it stands for.
+ *   hb_index_reset, hb_index_add or a capacity change came after it; when a capacity is smaller than the count it stands for.
+ *   After an EXCLUDING search that the screen served (hb_index_search_excluding with hb_index_set_exclude_screen, hbird_hip_exclude_screen.h) both
+ *   read-outs answer as well, the leftover's rungs notwithstanding (they refuse if one of those rungs took the candidate pass itself), and mean:
+ *     kth0 / kth1          the k-th best exact score among the ALLOWED candidates of the list (-inf also where fewer than k are allowed);
+ *                          floor0 and the second pass' seed rule are formed from it
+ *     the lists            unmasked: cand_rows / cand_rows1 hold excluded rows too, and the certificates' threshold is the list's last entry,
+ *                          allowed or not; a full list with fewer than k allowed candidates is never certified
+ *     n2                   the queries handed to the rungs (hb_index_last_exclusion_seeds names them)
+ *   With the record the QUERY side of hb_index_last_fp16_copy (q16, n, level) and of hb_index_last_centre (hbird_hip_centre.h: cq, qcn, q16)
+ *   answers behind those rungs too, where it used to refuse once a rung had run: the rungs' fp32 searches write neither the fp16 query tiles
+ *   nor the centred pass' per-query values, so both still describe the search's last fp16 pass.
  *
  * hb_index_last_fp16_copy(ix, bank16, q16, info): the PLAIN (uncentred) fp16 copy the pass reads -- one round-to-nearest-even conversion per
  *   component is what the bound's h = 2^-11 assumes, and the overflow flag decides between "certificate valid" and "scores inf / NaN".

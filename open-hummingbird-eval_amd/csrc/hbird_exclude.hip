@@ -328,12 +328,19 @@ extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t
         const int64_t escalated0 = ix->last_fp16_escalated;
         const hb_f16_adapt adapt0 = ix->f16_adapt;
         const int64_t n_left = (int64_t)res.left.size();
+        // ... and so is the record of what its passes left for the read-outs (hb_index_last_screen, hb_index_last_screen_seeds,
+        // hb_index_last_exclusion_seeds): every rung is a search of a caller and wipes it.  The rungs search at kf > 128, the fp32 kernel, which
+        // writes none of `cand`, `fb`, `fb1`; should one of them take the candidate pass after all, the buffers are its own and the read-outs refuse.
+        hb_index::screen_record rec0 = ix->screen;
+        const int64_t passes0 = ix->screen_passes;
         ix->last_excl[0] = 0; ix->last_excl[1] = 0; ix->last_excl[2] = 0; ix->last_excl[3] = ix->gmax;
         int rc = 0;
         if (n_left > 0) rc = exclude_rungs_on(ix, res.left, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, s);
         ix->last_path = path0; ix->last_reason = reason0; ix->last_centred = centred0;
         ix->last_fp16_escalated = escalated0; ix->last_fp16_fallbacks = n_left;
         ix->f16_adapt = adapt0;
+        if (!rc && ix->screen_passes == passes0) { rec0.left = res.left; ix->screen = std::move(rec0); }
+        else { ix->screen.state = HB_SCREEN_NONE; ix->screen.new_search(false); }
         if (rc) return -1;
         int64_t* o = ix->last_excl_screen;
         o[0] = 1; o[2] = res.kc; o[3] = res.certified0; o[4] = res.sent1; o[5] = res.certified1; o[6] = n_left; o[7] = res.centred;

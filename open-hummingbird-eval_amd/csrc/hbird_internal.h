@@ -114,15 +114,19 @@ struct hb_index {
     // `state` and the tail of `fb1` only, so all of it stays until the next search of a caller.
     struct screen_record {
         int state = 0; int64_t nq = 0; int kc = 0, klw = 0, centred = 0;      // state: HB_SCREEN_*
-        int excluding = 0;                      // the search dropped row groups (hb_index_search_excluding): no seeds read-out
+        int excluding = 0;                      // the search dropped row groups (hb_index_search_excluding): the k-th scores are those of the ALLOWED candidates
         int64_t n1 = 0;                         // queries of the second fp16 pass (0: none ran)
         int kc1 = 0, klw1 = 0;
         size_t o_seed1 = 0;                     // byte offset in `fb` of the second pass' gathered seeds [n1]
+        size_t o_qg1 = 0;                       // ... and (excluding) of its gathered query groups [n1]
         std::vector<int64_t> bad;               // the level-0 queries sent to the second pass, ascending
+        std::vector<int64_t> left;              // (excluding) the level-0 queries handed to the rungs, ascending
         bool none() const { return state == HB_SCREEN_NONE; }
         bool second_pass_ran() const { return state == HB_SCREEN_OVERWRITTEN; }
-        void new_search(bool excl) { excluding = excl ? 1 : 0; n1 = 0; kc1 = klw1 = 0; o_seed1 = 0; bad.clear(); }
+        void new_search(bool excl) { excluding = excl ? 1 : 0; n1 = 0; kc1 = klw1 = 0; o_seed1 = o_qg1 = 0; bad.clear(); left.clear(); }
     } screen;
+    int64_t screen_passes = 0;                           // level-0 candidate passes run on this index: a served excluding search keeps its record across
+                                                         // the leftover's rungs only while none of them took one (hb_index_search_excluding)
     hb_f16_adapt f16_adapt;                              // adaptive use of use_fp16 in mode 2 (hbird_calibrate.h): moving averages of the failing shares
     hb_dev<char> bigk;                                   // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
     hb_schedule sched_esc; hb_dev<char> sched_esc_dev;   // the nested searches' work list (the caller's stays cached)

@@ -992,7 +992,7 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
         c.excl->sent1 = nf;
     }
     if (!again16) ix->last_fp16_fallbacks = nf;
-    if (again16) { ix->screen.state = HB_SCREEN_OVERWRITTEN; ix->screen.bad = bad; ix->screen.o_seed1 = o_seed; }      // (the second pass merges into ix->cand)
+    if (again16) { ix->screen.state = HB_SCREEN_OVERWRITTEN; ix->screen.bad = bad; ix->screen.o_seed1 = o_seed; ix->screen.o_qg1 = c.groups ? o_qg : 0; }      // (the second pass merges into ix->cand)
     if (!rc) rc = knn_search(ix, nested, d_q, nf, k, id_base, d_fi, d_fd);
     if (esc == 0) ix->last_fp16_escalated = nf;
     if (esc == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks);      // (an excluding search's failures say nothing about plain ones)
@@ -1057,7 +1057,7 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     std::vector<int64_t> bad;
     for (int64_t i = 0; i < nq; ++i) if (!hc[i]) bad.push_back(i);
     const int64_t nf = (int64_t)bad.size();
-    if (esc == 0) { ix->screen.nq = nq; ix->screen.kc = kc; ix->screen.klw = klw; ix->screen.centred = centred ? 1 : 0; ix->screen.state = HB_SCREEN_VALID; }      // (cand and the certificates are complete: the stream is idle)
+    if (esc == 0) { ix->screen.nq = nq; ix->screen.kc = kc; ix->screen.klw = klw; ix->screen.centred = centred ? 1 : 0; ix->screen.state = HB_SCREEN_VALID; ++ix->screen_passes; }      // (cand and the certificates are complete: the stream is idle)
     if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
     if (esc == 1) { ix->screen.n1 = nq; ix->screen.kc1 = kc; ix->screen.klw1 = klw; }      // (hb_index_last_screen_seeds)
     if (!centred) { ix->copy16.q_n = nq; ix->copy16.q_level = esc; }      // (hb_index_last_fp16_copy)
@@ -1185,14 +1185,14 @@ int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k,
 
 // What the chain behind the first candidate pass left (hb_index_last_screen_seeds, include/hbird_hip_screen.h): host bookkeeping and copies, no
 // launch.  Level 0 lies in `fb` behind the certificates (knn_level_buf), the second pass' gathered seeds further back in `fb`, its lists in
-// `cand` and its own certificates and k-th scores in `fb1`.
+// `cand` and its own certificates and k-th scores in `fb1`.  An excluding search the screen served leaves the same (its k-th scores over the allowed
+// candidates); hb_index_search_excluding puts the record back behind the leftover's rungs, whose fp32 searches touch none of these buffers.
 int hb_screen_seeds_readout(hb_index* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
                             float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]) {
     for (int i = 0; i < 8; ++i) info[i] = 0;
     const hb_index::screen_record& r = ix->screen;
     if (r.none() || !ix->fb)
         return hb_fail("hb_index_last_screen_seeds: the last search did not take the fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
-    if (r.excluding) return hb_fail("hb_index_last_screen_seeds: the last search was an excluding one (hb_index_search_excluding): its seeds are not handed out");
     const knn_level_buf l0(ix, 0, r.nq);
     const int64_t n1 = r.second_pass_ran() ? r.n1 : 0;
     if (ix->fb.bytes < l0.o_rows) return hb_fail("hb_index_last_screen_seeds: the level-0 workspace is smaller than its record says");

@@ -167,6 +167,7 @@ SIGNATURES_EXCLUDE_SCREEN = {
     "hb_index_last_exclusion_screen": (c_int, [c_void_p, POINTER(c_int64)]),
     "hb_index_exclude_rerank": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "hb_index_last_exclusion_seeds": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(c_int64)]),
 }
 
 

@@ -410,6 +410,18 @@ class HipFlatIndex:
                                                       int(id_base), _ptr(idx), _ptr(dist), _ptr(cert), _ptr(kth), _ptr(flo)), ValueError)
         return idx, dist, cert, kth, flo
 
+    def last_exclusion_seeds(self) -> dict:
+        """What an excluding search that the screen served handed on besides `last_screen_seeds` (hb_index_last_exclusion_seeds): groups1 int32
+        [n1], the second pass' query groups as gathered on the device (the order of queries1), and left int64 [n_left], the level-0 query numbers
+        handed to the rungs, ascending.  Raises when the last search was not a served excluding one, or after reset / add / a capacity change."""
+        lib = _lib.lib()
+        info = (ctypes.c_int64 * 2)()
+        _lib.check(lib.hb_index_last_exclusion_seeds(self._h, None, None, 0, 0, info))
+        n1, n_left = int(info[0]), int(info[1])
+        groups1, left = np.empty(n1, dtype=np.int32), np.empty(n_left, dtype=np.int64)
+        _lib.check(lib.hb_index_last_exclusion_seeds(self._h, _ptr(groups1) if n1 else None, _ptr(left) if n_left else None, n1, n_left, info))
+        return {"n1": n1, "n_left": n_left, "groups1": groups1, "left": left}
+
     def _excluding_lists(self, q, k, qgroups, id_base):
         on_dev, q = self._as_f32(q)
         qd = q if on_dev else torch.from_numpy(q).cuda(self.device)
@@ -666,8 +678,9 @@ class HipFlatIndex:
         Level 0: kth0 / floor0 float32 [nq], certified0 uint8 [nq].  Level 1, where a second fp16 pass ran (n1 > 0; else empty arrays):
         queries1 int64 [n1] (ascending level-0 query numbers), seed1 float32 [n1] (as gathered on the device), rows1 int64 [n1, kc1] and
         scores1 float32 [n1, kc1] (that pass' merged lists, conventions of last_screen), certified1 uint8 [n1], kth1 float32 [n1]; and nq,
-        kc0, klw0, n1, kc1, klw1, centred, n2 (queries that reached the fp32 kernel).  Raises when the last search did not take the fp16
-        path, was an excluding one, or after reset / add / a capacity change."""
+        kc0, klw0, n1, kc1, klw1, centred, n2 (queries that reached the fp32 kernel).  After an excluding search that the screen served: kth0 /
+        kth1 over the ALLOWED candidates of the unmasked lists, n2 the queries handed to the rungs (`last_exclusion_seeds`).  Raises when the
+        last search did not take the fp16 path, or after reset / add / a capacity change."""
         lib = _lib.lib()
         info = (ctypes.c_int64 * 8)()
         _lib.check(lib.hb_index_last_screen_seeds(self._h, *([None] * 9), 0, 0, info))
@@ -1220,7 +1233,7 @@ class HipMultiIndex:
         raise ValueError("HipMultiIndex: excluding searches are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")
 
     set_row_groups = search_excluding = search_aggregate_excluding = search_aggregate_grid_excluding = last_exclusion = _no_exclusion
-    set_exclusion_screen = last_exclusion_screen = _no_exclusion
+    set_exclusion_screen = last_exclusion_screen = last_exclusion_seeds = _no_exclusion
 
     def select_rows(self, ids):
         raise ValueError("HipMultiIndex.select_rows: views are single-index (one HipFlatIndex on one GPU); sharded and replicated banks have none")

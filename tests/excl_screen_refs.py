@@ -4,6 +4,11 @@ re-rank kernel (hb_index_exclude_rerank) must return for given candidate lists. 
 tests/test_exclude_screen_gpu.py holds the kernel and the route to these; tests/test_exclude_screen_cpu.py pins the model's counts and shows
 which wrong kernels the restatement catches.
 
+Further down: the references of what a served excluding search leaves BEHIND its passes (HipFlatIndex.last_screen / last_screen_seeds /
+last_exclusion_seeds) -- the chain of tests/f16_second_pass_refs.py with every k-th score taken over the allowed entries of the unmasked lists,
+the gathered groups, and the hand-over to the rungs -- and the cases that reach its regimes (ECASES).  tests/test_exclude_seeds_gpu.py holds the
+route to them, tests/test_exclude_seeds_cpu.py holds a host model to them and shows which wrong chains they catch.
+
 The restatement, per query: the candidates that are ALLOWED (row >= 0, and not: query group >= 0, row inside the table, same group), ranked by
 (exact score descending, row ascending); the first k are the answer, the tail is -1 / the missing value.  Certificate: the k-th allowed exact
 score strictly above (pass score of the LAST list entry, allowed or not) + E; a full list with fewer than k allowed candidates is never
@@ -11,11 +16,14 @@ certified; a list that ends in -1 is certified when the bank holds fewer than kc
 """
 from __future__ import annotations
 
+import collections
 import functools
 
 import numpy as np
 
+import f16_centre_refs as CR
 import f16_pass_refs as fr
+import f16_second_pass_refs as SR
 
 METRIC_NAME = {0: "dot_product", 1: "l2"}
 
@@ -257,3 +265,235 @@ def skip_cut_positions(cand, pass_scores, groups, qg, k, E, variant=None):
 
 
 WRONG_KERNELS = ("threshold_last_allowed", "excluded_counted", "cut_from_k_minus_1", "not_full_after_exclusion")
+
+
+# ---- what a served excluding search leaves behind its passes --------------------------------------------------------------------------------
+# The chain is that of f16_second_pass_refs.py (SR), and so are its checks: SR.check_seeds on the level-0 lists with the excluded entries
+# struck (-1: kth0 is the k-th best chain score among the ALLOWED candidates), SR.check_level1 with the allowed entries handed in for kth1 --
+# its list checks and its certificate rules read the unmasked lists, as the kernel does, and a k-th score of -inf (fewer than k allowed) pins
+# the flag at 0 on both branches.  New here: the first certificates (rerank_expected's rule through flag_band), the gathered groups, the queries
+# left to the rungs, and the answer.  Every value is a function of the previous stage's READ-OUT.
+EXCL_NAMES = ("flag0_one", "flag0_zero", "groups1", "left", "n2", "answer_ids", "answer_bits")
+# (the level-0 lists: the names of fr.check_float / fr.check_exact / fr.check_centred with this prefix -- check_level0_lists)
+LISTS0 = "lists0_"
+GROUP_ROWS = 150          # rows per group of the cases' tables: k + gmax = 180 > 128, the route serves the search
+ECase = collections.namedtuple("ECase", "name base table metric")
+# base: a case of SR.CASES (its world, k, metric, centred) or "image" (image_world, its own table); table: "block" (GROUP_ROWS consecutive
+# rows), "interleaved" (row % G) or "edited" (block; every 7th row in no group, every 3rd query excludes nothing, query 1 names the group
+# without rows).  qg[i]: the group of query i's best-scoring row.  Which regime each case reaches BY THE REFERENCE ALONE is recomputed and
+# held by tests/test_exclude_seeds_cpu.py (REGIMES there).
+ECASES = [
+    ECase("rounding100", "rounding100", "block", None),
+    ECase("rounding100-l2", "rounding100-l2", "interleaved", None),
+    ECase("rounding300", "rounding300", "block", None),
+    ECase("gather", "gather", "interleaved", None),
+    ECase("tight-tokens", "tight-tokens", "block", None),
+    ECase("one-failing", "one-failing", "interleaved", None),
+    ECase("centred-clusters-neg", "centred-clusters-neg", "block", None),
+    ECase("massive-128", "massive-128", "interleaved", None),
+    ECase("exact", "exact", "block", None),
+    ECase("exact-l2", "exact-l2", "interleaved", None),
+    ECase("non-finite", "non-finite", "block", None),
+    ECase("edited", "rounding100", "edited", None),
+    ECase("image", "image", "own", 0),
+    ECase("image-l2", "image", "own", 1),
+]
+ECASE = {c.name: c for c in ECASES}
+_SRCASE = {c.name: c for c in SR.CASES}
+
+
+@functools.lru_cache(maxsize=None)
+def excl_case(name):
+    """-> (c: the SR.Case the chain runs as, W: bank / queries [/ the exact world's fields], groups int32 [N], n_groups (one more than the table
+    names: a group without rows), qg int32 [nq]); read-only."""
+    ec = ECASE[name]
+    if ec.base == "image":
+        rows, groups, q, qg = image_world()
+        c = SR.Case(name, "image", 64, 6000, 240, 30, ec.metric, False, ())
+        return c, {"bank": rows, "queries": q}, groups, 37, qg
+    c = _SRCASE[ec.base]
+    W = SR.case_world(c)
+    G = -(-c.N // GROUP_ROWS)
+    groups = (np.arange(c.N) % G if ec.table == "interleaved" else np.arange(c.N) // GROUP_ROWS).astype(np.int32)
+    b64 = W["bank"].astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = W["queries"].astype(np.float64) @ b64.T - (0.5 * (b64 * b64).sum(axis=1) if c.metric == 1 else 0.0)
+    qg = groups[np.argmax(np.where(np.isfinite(s), s, -np.inf), axis=1)].astype(np.int32)
+    if ec.table == "edited":
+        groups[::7] = -1
+        qg[::3] = -1
+        qg[1] = G
+    for arr in (groups, qg):
+        arr.setflags(write=False)
+    return c, W, groups, G + 1, qg
+
+
+def bounds(q, bank, D, metric):
+    """(qn, bmax, E [nq]) of the PLAIN pass: SR.plain_bounds with E by the library's own constants (fr.replay_bounds) wherever the norm is finite."""
+    qn, bmax, E = SR.plain_bounds(q, bank, D, metric)
+    E = np.array(E, np.float64)
+    for i in np.flatnonzero(np.isfinite(qn)):
+        E[i] = fr.replay_bounds(D, metric, float(qn[i]), bmax)[0]
+    return qn, bmax, E
+
+
+# What each case is there for -- a subset of what it reaches BY THE REFERENCE ALONE (tests/test_exclude_seeds_cpu.py recomputes it) and on the
+# device (tests/test_exclude_seeds_gpu.py):
+#   finite_seed        a second-pass query seeded from the k-th ALLOWED exact score
+#   not_full_excluded  a second list that does not fill up, holds an excluded row and is certified by the seed rule
+#   full_failing       a full second list with at least k allowed candidates that fails: to the rungs
+#   fewer_than_k       a list with fewer than k allowed candidates (no seed; never certified)
+#   all_excluded       a full second list of 256 excluded rows
+#   n1_one / n1_many   one second-pass query / more than 256 (two query tiles of the second pass)
+#   centred            the centred form;  centred_neg: with c_q < 0 and seeded second-pass queries
+#   exact              an exact world with twins in the second lists (list bits)
+#   non_finite         a NaN query and one beyond the fp16 range: no seed, through both levels to the rungs
+#   no_group           queries that exclude nothing, a group without rows, rows in no group
+REGIMES = {
+    "rounding100": ("finite_seed", "not_full_excluded", "block", "dot"),
+    "rounding100-l2": ("finite_seed", "not_full_excluded", "interleaved", "l2"),
+    "rounding300": ("finite_seed", "full_failing", "block"),
+    "gather": ("finite_seed", "full_failing", "interleaved"),
+    "tight-tokens": ("n1_many", "full_failing"),
+    "one-failing": ("n1_one", "not_full_excluded"),
+    "centred-clusters-neg": ("centred", "centred_neg", "finite_seed", "not_full_excluded", "fewer_than_k"),
+    "massive-128": ("centred",),
+    "exact": ("exact",),
+    "exact-l2": ("exact", "l2"),
+    "non-finite": ("non_finite",),
+    "edited": ("no_group", "finite_seed"),
+    "image": ("fewer_than_k", "all_excluded"),
+    "image-l2": ("fewer_than_k", "all_excluded", "l2"),
+}
+ALL_REGIMES = {"finite_seed", "not_full_excluded", "full_failing", "fewer_than_k", "all_excluded", "n1_one", "n1_many", "centred", "centred_neg", "exact",
+               "non_finite", "no_group", "block", "interleaved", "dot", "l2"}
+
+
+def regimes_reached(name, S, left, fig, cq, E):
+    """The regimes a chain reached, from its read-out S, the queries left to the rungs and check_excl_chain's figures (cq / E: the centred
+    pass' c_q and bound, or None) -> set.  The same rule for the host model and for the device."""
+    c, W, groups, n_groups, qg = excl_case(name)
+    table = ECASE[name].table
+    out = {"block" if table in ("block", "edited") else table, "l2" if c.metric else "dot"}
+    flags = {"finite_seed": fig["finite_seeds"] > 0, "not_full_excluded": fig["not_full_certified_with_excluded"] > 0,
+             "full_failing": fig["full_failing_k_allowed"] > 0 and len(left) > 0, "fewer_than_k": fig["fewer_than_k0"] > 0,
+             "all_excluded": fig["full_all_excluded"] > 0, "n1_one": S["n1"] == 1, "n1_many": S["n1"] > 256,
+             "centred": c.centred and bool(np.isfinite(S["floor0"]).any()),
+             "centred_neg": c.centred and cq is not None and fig["finite_seeds"] > 0 and bool((cq < -100 * E).all()),
+             "exact": c.world == "exact" and S["n1"] > 0 and bool(W["dup"][S["rows1"][S["rows1"] >= 0]].any()),
+             "non_finite": c.world == "nonfinite" and S["n1"] > 0 and bool(np.isin([7, 23], left).all()) and bool(np.isneginf(S["kth0"][[7, 23]]).all())
+                           and bool(np.isneginf(S["seed1"][np.searchsorted(S["queries1"], [7, 23])]).all()),
+             "no_group": bool((qg == -1).any() and (groups == -1).any() and (qg == n_groups - 1).any())}
+    return out | {n for n, v in flags.items() if v}
+
+
+def check_level0_lists(rows, scores, q, bank, metric, k, exact=None, centre_info=None):
+    """The level-0 lists and pass scores of a served excluding search, which know nothing of groups: H1 / H2 as fr.check_float has them on a
+    float world (over the queries with finite fp16 operands), fr.check_exact's bits on an exact world, fr.check_centred's H1 / H2 for the
+    centred pass (centre_info: fp16_centre_info(), or the same fields of SR.centred_pass).  No flags: the excluding certificates are
+    check_excl_chain's.  -> ({LISTS0 + name: message}, figures)."""
+    kc = rows.shape[1]
+    if exact is not None:
+        bad, fig = fr.check_exact(rows, scores, exact, metric, kc), {}
+    elif centre_info is not None:
+        bad, fig = fr.check_centred(rows, scores, None, q, bank, metric, k, kc, centre_info)
+    else:
+        fin = SR.query_norms(q) <= fr.F16_LIMIT
+        bad, fig = fr.check_float(rows[fin], scores[fin], None, fr.float_reference(np.asarray(q, np.float32)[fin], bank, metric), k, kc)
+    return {LISTS0 + n: f"{LISTS0}{n}: {m}" for n, m in bad.items()}, {LISTS0 + n: v for n, v in fig.items()}
+
+
+def check_excl_chain(S, L0, X1, stats, groups, qg, q, bank, metric, k, E, ref=None, exact=None, cq=None, skip=None):
+    """Everything a served excluding search left -> ({name: message}, figures).  S: last_screen_seeds(); L0: last_screen() of the same search run
+    WITHOUT its second pass (the level-0 lists; a dict with rows / scores / certified); X1: last_exclusion_seeds(); stats: last_exclusion_screen()
+    or None; groups [N] / qg [nq]: the table and the queries' groups; the rest as SR.check_seeds / SR.check_level1 take it.
+    Names: SR.SEED_NAMES, SR.LEVEL1_NAMES, EXCL_NAMES (answers: check_answer)."""
+    nq, N = S["nq"], bank.shape[0]
+    rows0, kc0 = L0["rows"], L0["rows"].shape[1]
+    ok0 = allowed_mask(rows0, groups, qg)
+    bad, fig = SR.check_seeds(S, np.where(ok0, rows0, -1), L0["certified"], q, bank, metric, k, E, cq)
+    # the first certificates, from both sides outside the 0.1 % band, as a function of the read-out kth0 (held on bits above) and the list
+    qn = SR.query_norms(q)
+    add = cq.astype(np.float64) if cq is not None else 0.0
+    full0 = rows0[:, kc0 - 1] >= 0
+    with np.errstate(invalid="ignore"):
+        thr = L0["scores"][:, kc0 - 1].astype(np.float64) + add
+        one, zero, band = fr.flag_band(S["kth0"].astype(np.float64), thr, E, qn)
+        nonfin = ~(qn <= fr.F16_LIMIT) | ~np.isfinite(E) | ~np.isfinite(thr)
+    one, zero = one & ~nonfin & full0, zero | nonfin | ~full0 | (ok0.sum(axis=1) < k)       # (N >= kc0: a list that is not full has lost rows)
+    one &= ~zero
+    assert N >= kc0
+    fig["band_share0"] = float((~one & ~zero).mean())
+    f0 = S["certified0"].astype(bool)
+    if (one & ~f0).any():
+        i = int(np.flatnonzero(one & ~f0)[0])
+        SR._note(bad, "flag0_one", f"query {i} ({int(ok0[i].sum())} allowed of {kc0}): not certified although its k-th allowed exact score lies {(S['kth0'][i] - thr[i]) / E[i]:.4f} E above the last pass score")
+    if (zero & f0).any():
+        i = int(np.flatnonzero(zero & f0)[0])
+        SR._note(bad, "flag0_zero", f"query {i} ({int(ok0[i].sum())} allowed of {kc0}, list {'full' if full0[i] else 'not full'}): certified although its k-th allowed exact score ({S['kth0'][i]!r}) lies {(S['kth0'][i] - thr[i]) / E[i]:.4f} E above the last pass score")
+    # the gather of the groups, and the second pass with the groups AS GATHERED
+    n1 = S["n1"]
+    g1 = np.asarray(X1["groups1"])
+    want_g1 = np.asarray(qg)[S["queries1"]] if n1 else np.zeros(0, np.int32)
+    if g1.shape != want_g1.shape or (g1 != want_g1).any():
+        j = 0 if g1.shape != want_g1.shape else int(np.flatnonzero(g1 != want_g1)[0])
+        SR._note(bad, "groups1", f"{g1.size} groups gathered for {n1} second-pass queries; second-pass query {j}" + (f" (query {S['queries1'][j]}) got group {g1[j]}, its own is {want_g1[j]}" if g1.shape == want_g1.shape else ""))
+    ok1 = allowed_mask(S["rows1"], groups, g1 if g1.shape == want_g1.shape else want_g1) if n1 else np.zeros((0, SR.KC1), bool)
+    bad1, fig1 = SR.check_level1(S, q, bank, metric, k, E, ref=ref, exact=exact, cq=cq, skip=skip, allowed=ok1)
+    bad.update({n: m for n, m in bad1.items() if n not in bad})
+    fig.update(fig1)
+    # the hand-over to the rungs
+    want_left = S["queries1"][S["certified1"] == 0] if n1 else np.flatnonzero(S["certified0"] == 0)
+    left = np.asarray(X1["left"])
+    if left.shape != want_left.shape or (left != want_left).any():
+        SR._note(bad, "left", f"{left[:8]} ... ({left.size}) handed to the rungs, the last certificates failed for {want_left[:8]} ... ({want_left.size})")
+    if S["n2"] != left.size or (stats is not None and stats["rung_queries"] != left.size):
+        SR._note(bad, "n2", f"n2 = {S['n2']}, rung_queries = {None if stats is None else stats['rung_queries']}, {left.size} queries named")
+    n_have = (S["rows1"] >= 0).sum(axis=1) if n1 else np.zeros(0, int)
+    fig.update(n1=int(n1), n_left=int(left.size), excluded0=[int((~ok0 & (rows0 >= 0)).sum(axis=1).min()), int((~ok0 & (rows0 >= 0)).sum(axis=1).max())],
+               fewer_than_k0=int((ok0.sum(axis=1) < k).sum()), finite_seeds=int(np.isfinite(S["seed1"]).sum()),
+               not_full_certified_with_excluded=int(((n_have < SR.KC1) & (S["certified1"] == 1) & ((~ok1) & (S["rows1"] >= 0)).any(axis=1)).sum()) if n1 else 0,
+               full_failing_k_allowed=int(((n_have == SR.KC1) & (S["certified1"] == 0) & (ok1.sum(axis=1) >= k)).sum()) if n1 else 0,
+               full_all_excluded=int(((n_have == SR.KC1) & (ok1.sum(axis=1) == 0)).sum()) if n1 else 0,
+               not_full_rows=[int(n_have[n_have < SR.KC1].min()), int(n_have[n_have < SR.KC1].max())] if (n_have < SR.KC1).any() else [],
+               rule_margin_over_E=_rule_margins(S, n_have, E, cq) if n1 else [])
+    return bad, fig
+
+
+def _rule_margins(S, n_have, E, cq):
+    """[min, max] over the second-pass queries with a finite k-th score of (kth1 [- c_q] - threshold) / E, the threshold being the last pass
+    score of a full list and the seed of one that did not fill up: the certificates' distance from their decision."""
+    Q1 = S["queries1"]
+    add = cq[Q1].astype(np.float64) if cq is not None else 0.0
+    thr = np.where(n_have == SR.KC1, S["scores1"][:, SR.KC1 - 1].astype(np.float64), S["seed1"].astype(np.float64))
+    with np.errstate(invalid="ignore"):
+        m = (S["kth1"].astype(np.float64) - add - thr) / E[Q1] - 1.0
+    m = m[np.isfinite(m)]
+    return [float(m.min()), float(m.max())] if m.size else []
+
+
+def allowed_ranking(rank_ids, rank_dist, groups, qg, k, metric):
+    """The fp32 chain ranking (oracle.knn_chain_f32 at k + gmax or more) restricted to the allowed rows -> idx int64 [nq, k], dist float32 [nq, k]."""
+    nq = rank_ids.shape[0]
+    idx = np.full((nq, k), -1, np.int64)
+    dist = np.full((nq, k), np.inf if metric == 1 else -np.inf, np.float32)
+    g = np.asarray(groups)
+    for i in range(nq):
+        keep = np.flatnonzero((rank_ids[i] >= 0) & ~((qg[i] >= 0) & (g[np.maximum(rank_ids[i], 0)] == qg[i])))[:k]
+        idx[i, :keep.size], dist[i, :keep.size] = rank_ids[i, keep], rank_dist[i, keep]
+    return idx, dist
+
+
+def check_answer(got_idx, got_dist, want_idx, want_dist, which=None, what=""):
+    """ids and distance bits of the answer over the queries `which` (all) -> {name: message}"""
+    bad = {}
+    w = np.ones(len(got_idx), bool) if which is None else which
+    m = w & (got_idx != want_idx).any(axis=1)
+    if m.any():
+        i = int(np.flatnonzero(m)[0]); c = int(np.flatnonzero(got_idx[i] != want_idx[i])[0])
+        SR._note(bad, "answer_ids", f"{what}query {i}: neighbour {c} is row {got_idx[i, c]}, the fp32 chain ranking of the allowed rows has {want_idx[i, c]}")
+    m = w & ~CR.same_bits(got_dist, want_dist).all(axis=1) & ~m
+    if m.any():
+        i = int(np.flatnonzero(m)[0]); c = int(np.flatnonzero(~CR.same_bits(got_dist[i], want_dist[i]))[0])
+        SR._note(bad, "answer_bits", f"{what}query {i}: neighbour {c} (row {got_idx[i, c]}) at distance {got_dist[i, c]!r}, the chain gives {want_dist[i, c]!r}")
+    return bad

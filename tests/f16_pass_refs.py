@@ -328,7 +328,7 @@ def check_centred(got_rows, got_scores, got_flags, q, bank, metric, k, kc, info)
     """H1 / H2 / the flags of the CENTRED pass, in the form the re-rank uses (hbird_rerank_dev.h): with mu the bank's column mean (float64,
     here), t / cmax / ||mu|| from fp16_centre_info() and E' from the shipped constants:
         |pass + q.mu - s| <= E' for candidates,   s[r] <= pass[kc-1] + q.mu + E' for outside rows,
-    and the certificate decision outside its 0.1 % band.  No bits, no A-level tolerance: one ulp of mu between this mean and the library's
+    and the certificate decision outside its 0.1 % band (got_flags None: the lists only).  No bits, no A-level tolerance: one ulp of mu between this mean and the library's
     is 2^-14 of E'.  -> ({name: message}, figures)."""
     q64, b64 = np.asarray(q, np.float64), np.asarray(bank, np.float64)
     nq, D = q64.shape
@@ -366,6 +366,8 @@ def check_centred(got_rows, got_scores, got_flags, q, bank, metric, k, kc, info)
     if over.any():
         i, r = [int(v[0]) for v in np.nonzero(over)]
         note("H2", f"query {i}: row {r} is no candidate, its exact score exceeds the kc-th pass score + q.mu by {(s[i, r] - last[i]) / E[i]:.3f} E'")
+    if got_flags is None:      # (no decision to check: the lists of an excluding search, tests/excl_screen_refs.py)
+        return bad, fig
     kth64 = kth_best(cs, k)
     one, zero, band = flag_band(kth64, last, E, np.maximum(qn, qcn))
     fig["band_share"] = float(band.mean())

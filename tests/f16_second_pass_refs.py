@@ -158,10 +158,11 @@ def exact_level1_lists(W, metric, queries1, seed1):
     return rows, scores
 
 
-def check_level1(S, q, bank, metric, k, E, ref=None, exact=None, cq=None, skip=None):
+def check_level1(S, q, bank, metric, k, E, ref=None, exact=None, cq=None, skip=None, allowed=None):
     """The second pass' lists, certificates and k-th scores -> ({name: message}, figures).  ref: R.float_reference of (q, bank) for a float
     world (plain pass only); exact: the exact world W.  E [nq], cq [nq] or None as in check_seeds.  skip: bool [nq], queries whose lists are
-    not looked at (non-finite operands)."""
+    not looked at (non-finite operands).  allowed: bool [n1, 256] or None -- an excluding search (tests/excl_screen_refs.py): the entries of
+    rows1 that kth1 is taken over; the lists and the certificates' thresholds are those of the unmasked lists."""
     bad, fig = {}, {"acc_over_A": 0.0, "undecided_share": 0.0, "band_share1": 0.0, "not_full": 0, "full": 0}
     n1 = S["n1"]
     if n1 == 0:
@@ -245,7 +246,7 @@ def check_level1(S, q, bank, metric, k, E, ref=None, exact=None, cq=None, skip=N
         j = int(np.flatnonzero(zero & f)[0])
         _note(bad, "flag1_zero", f"second-pass query {j} (query {Q1[j]}, list of {n_have[j]}): certified although its exact k-th best lies {(kth64[j] - thr[j]) / E1[j]:.4f} E above the {'last pass score' if full[j] else 'seed'} (||q|| = {qn1[j]!r})")
     # kth1, on bits: as kth0, over the second pass' candidates
-    kth = kth_of(chain_scores(np.asarray(q, F32)[Q1], bank, rows, metric), k)
+    kth = kth_of(chain_scores(np.asarray(q, F32)[Q1], bank, rows if allowed is None else np.where(allowed, rows, -1), metric), k)
     want_inf = seedless(qn1, E1, None if cq is None else cq[Q1]) | ~np.isfinite(kth)
     got = S["kth1"]
     m = (np.isneginf(got) != want_inf) | (~want_inf & ~CR.same_bits(got, kth))
@@ -469,12 +470,40 @@ def finite_reference(q, bank, metric, skip):
     return {"s16": s16, "A": A}
 
 
+@functools.lru_cache(maxsize=None)
+def model_inputs(name):
+    """The inputs of the host model of a case (the CPU tests of both chains)
+    -> (W, kwargs of host_chain: pass_scores / E / cq, the float reference or None, the exact world or None)"""
+    c = next(x for x in CASES if x.name == name)
+    W = case_world(c)
+    if c.centred:
+        P = centred_pass(W["queries"], W["bank"], c.metric)
+        return W, {"pass_scores": P["pass_scores"], "E": P["E"], "cq": P["cq"]}, {"s16": P["pass_scores"], "A": P["A"]}, None
+    E = plain_bounds(W["queries"], W["bank"], c.D, c.metric)[2]
+    if c.world == "exact":
+        s2 = R.exact_scores2(W, c.metric)
+        return W, {"pass_scores": s2.astype(np.float64) * (0.5 * 4.0 ** W["scale_log2"]), "E": E}, None, W
+    if c.world == "nonfinite":
+        q16 = W["queries"].astype(np.float16).astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            ps = q16 @ W["bank"].astype(np.float16).astype(np.float64).T
+        skip = ~(query_norms(W["queries"]) <= R.F16_LIMIT)
+        return W, {"pass_scores": np.where(np.isfinite(ps), ps, -np.inf), "E": E}, finite_reference(W["queries"], W["bank"], c.metric, skip), None
+    ref = R.float_reference(W["queries"], W["bank"], c.metric)
+    return W, {"pass_scores": ref["s16"], "E": E}, ref, None
+
+
 # ---- the host model of the chain: level 0 -> seeds -> gather -> level 1 -> flags ------------------------------------------------------------------
-def host_chain(q, bank, metric, k, variant="", prev_floor=None, cq=None, E=None, pass_scores=None, seed_override=None):
+def host_chain(q, bank, metric, k, variant="", prev_floor=None, cq=None, E=None, pass_scores=None, seed_override=None, groups=None, qg=None):
     """What a RIGHT chain leaves (variant ''), as a last_screen_seeds() dict plus rows0, or a chain with one thing wrong.  The pass scores are
     the fp32 roundings of s16 (float worlds) or given (pass_scores [nq, N]: exact worlds, the centred pass).  E / cq as in check_seeds.
     variants: floor_half_E, floor_rank_k_minus_2, floor_without_cq, seeds_identity_order, stale_seeds (prev_floor), pool_drops_ties,
-    not_full_rule_on_full, seed_rule_without_cq, kth_from_pass_scores."""
+    not_full_rule_on_full, seed_rule_without_cq, kth_from_pass_scores.
+    groups [N] / qg [nq] (int32): the EXCLUDING chain (csrc/hbird_exclude_screen.hip; tests/excl_screen_refs.py) -- every k-th score is taken
+    over the ALLOWED entries of the unmasked lists, the second pass takes its queries' groups along, and what fails last is left to the rungs
+    (S gains groups1 and left).  Its variants: kth_counts_excluded (every k-th score over all entries), floor_counts_excluded (the floor only),
+    not_full_when_tail_excluded, groups_identity_order, groups_not_gathered, left_misses_one, left_holds_certified."""
+    excl = groups is not None
     q, bank = np.asarray(q, F32), np.asarray(bank, F32)
     nq, N = q.shape[0], bank.shape[0]
     kc0 = R.kc_of(k)
@@ -496,13 +525,19 @@ def host_chain(q, bank, metric, k, variant="", prev_floor=None, cq=None, E=None,
             out[i, :order.size] = sc[i, order]
         return rows, out
 
-    def level(qs, psl, rows, seed, Es, cqs, qns):
+    def level(qs, psl, rows, seed, Es, cqs, qns, qgs=None):
         n = rows.shape[1]
-        chain = chain_scores(qs, bank, rows, metric)
-        src = np.where(rows >= 0, np.take_along_axis(psl, np.maximum(rows, 0), axis=1) + cqs[:, None].astype(F32), F32(-np.inf)) if variant == "kth_from_pass_scores" else chain
+        chain_all = chain_scores(qs, bank, rows, metric)
+        ok = np.ones(rows.shape, bool)
+        if excl:      # (the kernel's rule: a row >= 0 of the query's group, the query naming one)
+            ok = ~((rows >= 0) & (qgs[:, None] >= 0) & (np.asarray(groups)[np.maximum(rows, 0)] == qgs[:, None]))
+        chain = chain_all if variant == "kth_counts_excluded" else np.where(ok, chain_all, F32(-np.inf)).astype(F32)
+        src = np.where((rows >= 0) & ok, np.take_along_axis(psl, np.maximum(rows, 0), axis=1) + cqs[:, None].astype(F32), F32(-np.inf)) if variant == "kth_from_pass_scores" else chain
         kk = k - 2 if variant == "floor_rank_k_minus_2" else k
         kth_true = kth_of(chain, k)
         kth_seed = kth_of(src, kk) if variant in ("kth_from_pass_scores", "floor_rank_k_minus_2") else kth_true
+        if variant == "floor_counts_excluded":
+            kth_seed = kth_of(chain_all, k)
         off = seedless(qns, Es, None if cq is None else cqs) | ~np.isfinite(kth_true)
         kth_out = np.where(off, F32(-np.inf), kth_of(src, k) if variant == "kth_from_pass_scores" else kth_true).astype(F32)
         f = 0.5 if variant == "floor_half_E" else 1.001
@@ -512,6 +547,8 @@ def host_chain(q, bank, metric, k, variant="", prev_floor=None, cq=None, E=None,
             fl = (fl - np.abs(fl) * 2.4e-7 - 1e-37).astype(F32)
         fl = np.where(off, F32(-np.inf), fl).astype(F32)
         full = rows[:, n - 1] >= 0
+        if variant == "not_full_when_tail_excluded":
+            full = full & ok[:, n - 1]
         last = psl[np.arange(rows.shape[0]), np.maximum(rows[:, n - 1], 0)].astype(np.float64)
         with np.errstate(invalid="ignore"):
             okq = (qns <= R.F16_LIMIT) & np.isfinite(kth_true)
@@ -523,11 +560,14 @@ def host_chain(q, bank, metric, k, variant="", prev_floor=None, cq=None, E=None,
         return kth_out, fl, cert.astype(np.uint8)
 
     rows0, _ = lists(ps, kc0)
-    kth0, floor0, cert0 = level(q, ps, rows0, None, E, cqv, qn)
+    qgv = np.asarray(qg, np.int32) if excl else None
+    kth0, floor0, cert0 = level(q, ps, rows0, None, E, cqv, qn, qgv)
     S = {"nq": nq, "kc0": kc0, "n1": 0, "kc1": 0, "centred": cq is not None, "kth0": kth0, "floor0": floor0, "certified0": cert0, "rows0": rows0,
          "queries1": np.zeros(0, np.int64), "seed1": np.zeros(0, F32), "rows1": np.zeros((0, 0), np.int64), "scores1": np.zeros((0, 0), F32),
          "certified1": np.zeros(0, np.uint8), "kth1": np.zeros(0, F32), "n2": int((cert0 == 0).sum())}
     Q1 = np.flatnonzero(cert0 == 0)
+    if excl:
+        S.update(scores0=np.where(rows0 >= 0, np.take_along_axis(ps, np.maximum(rows0, 0), axis=1), F32(-np.inf)).astype(F32), groups1=np.zeros(0, np.int32), left=Q1)
     if kc0 >= KC1 or N < 4096 or Q1.size == 0:
         return S
     seed = floor0[Q1]
@@ -540,8 +580,18 @@ def host_chain(q, bank, metric, k, variant="", prev_floor=None, cq=None, E=None,
         for j, v in seed_override.items():
             seed[j] = v
     rows1, sc1 = lists(ps[Q1], KC1, seed, drop_ties=variant == "pool_drops_ties")
-    kth1, _, cert1 = level(q[Q1], ps[Q1], rows1, seed, E[Q1], cqv[Q1], qn[Q1])
+    groups1 = None
+    if excl:
+        groups1 = qgv[:Q1.size] if variant == "groups_identity_order" else np.full(Q1.size, -1, np.int32) if variant == "groups_not_gathered" else qgv[Q1]
+    kth1, _, cert1 = level(q[Q1], ps[Q1], rows1, seed, E[Q1], cqv[Q1], qn[Q1], groups1)
     S.update(n1=int(Q1.size), kc1=KC1, queries1=Q1, seed1=seed.astype(F32), rows1=rows1, scores1=sc1, certified1=cert1, kth1=kth1, n2=int((cert1 == 0).sum()))
+    if excl:
+        left = Q1[cert1 == 0]
+        if variant == "left_misses_one":
+            left = left[1:]
+        if variant == "left_holds_certified":
+            left = np.sort(np.concatenate([left, Q1[cert1 == 1][:1]]))
+        S.update(groups1=groups1.astype(np.int32), left=left, n2=int(left.size))
     return S
 
 

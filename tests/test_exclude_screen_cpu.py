@@ -21,7 +21,7 @@ from hbird_mi import _lib
 from hbird_mi.nn.search_hip import HipFlatIndex, HipMultiIndex
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"hb_index_set_exclude_screen", "hb_index_last_exclusion_screen", "hb_index_exclude_rerank"}
+NAMES = {"hb_index_set_exclude_screen", "hb_index_last_exclusion_screen", "hb_index_exclude_rerank", "hb_index_last_exclusion_seeds"}
 V, I64 = ctypes.c_void_p, ctypes.c_int64
 
 
@@ -40,7 +40,8 @@ def test_entries_are_declared_in_the_new_header_only_exported_bound_and_document
                                                        "int kc", "const int32_t* qgroups", "int k", "int64_t id_base", "int64_t* out_idx", "float* out_dist",
                                                        "unsigned char* out_certified", "float* out_kth", "float* out_floor"])
     want = {"hb_index_set_exclude_screen": [V, ctypes.c_int], "hb_index_last_exclusion_screen": [V, ctypes.POINTER(I64)],
-            "hb_index_exclude_rerank": [V, V, I64, V, V, ctypes.c_int, V, ctypes.c_int, I64, V, V, V, V, V]}
+            "hb_index_exclude_rerank": [V, V, I64, V, V, ctypes.c_int, V, ctypes.c_int, I64, V, V, V, V, V],
+            "hb_index_last_exclusion_seeds": [V, V, V, I64, I64, ctypes.POINTER(I64)]}      # (its declaration: tests/test_exclude_seeds_cpu.py)
     others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CENTRE) | set(_lib.SIGNATURES_SELECT) | set(_lib.SIGNATURES_GRID) | set(_lib.SIGNATURES_EXCLUDE)
               | set(_lib.SIGNATURES_SCREEN))
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
@@ -52,12 +53,12 @@ def test_entries_are_declared_in_the_new_header_only_exported_bound_and_document
         assert name in main and not re.search(name + r"\s*\(", main), name       # hbird_hip.h names the entry and does not declare it
         assert name not in others
         assert f"`{name}`" in integration, name
-        for part in ("hbird_hip_exclude.h", "hbird_hip_screen.h"):
+        for part in ("hbird_hip_exclude.h", "hbird_hip_screen.h"):      # (hbird_hip_screen.h names the read-out of the rungs' queries, and declares none of these)
             assert not re.search(name + r"\s*\(", open(os.path.join(ROOT, "include", part)).read()), (name, part)
     mk = open(os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc", "Makefile")).read()
     assert "hbird_hip_exclude_screen.h" in re.search(r"^HDRS\s*=(.*)$", mk, flags=re.M).group(1)
     assert "hbird_exclude_screen.hip" in re.search(r"^SRCS\s*=(.*)$", mk, flags=re.M).group(1)
-    assert callable(HipFlatIndex.set_exclusion_screen) and callable(HipFlatIndex.last_exclusion_screen)
+    assert callable(HipFlatIndex.set_exclusion_screen) and callable(HipFlatIndex.last_exclusion_screen) and callable(HipFlatIndex.last_exclusion_seeds)
     assert HipMultiIndex.set_exclusion_screen is HipMultiIndex._no_exclusion and HipMultiIndex.last_exclusion_screen is HipMultiIndex._no_exclusion
 
 

@@ -164,7 +164,10 @@ def test_kernel_on_a_bank_smaller_than_its_lists(cuda_device, metric):
 
 
 # ---- 2. the route -----------------------------------------------------------------------------------------------------------------------
-def _levels_ok(s, nq, second_pass=True):
+def _levels_ok(s, nq, second_pass=True, model=None):
+    """model = (k, metric) of a PLAIN pass: the level counts EQUAL the host model's, (184, 31, 25) with the second pass and (184, 0, 56) without
+    (tests/test_exclude_screen_cpu.py pins them; no decision of the model lies within 5 % of E of its threshold).  The centred pass has a bound
+    of its own and no model here: its counts are held to their sums."""
     assert s["served"] == 1 and s["reason"] == "served"
     assert s["certified0"] >= 8 and s["rung_queries"] >= 8
     if second_pass:
@@ -172,6 +175,9 @@ def _levels_ok(s, nq, second_pass=True):
     else:
         assert s["second_pass"] == 0 and s["certified1"] == 0
     assert s["certified0"] + s["certified1"] + s["rung_queries"] == nq
+    if model is not None:
+        want = X.route_model(*model, escalation=second_pass)["counts"]
+        assert (s["certified0"], s["certified1"], s["rung_queries"]) == want == ((184, 31, 25) if second_pass else (184, 0, 56)), (s, want)
 
 
 @functools.lru_cache(maxsize=None)
@@ -205,7 +211,7 @@ def test_route_has_the_bits_of_the_rungs(cuda_device, metric, k):
     _same(host, want)
     assert path["path"] != "fp32"
     assert s["kc"] == R.kc_of(k) and s["centred"] == 0 and s_host == s
-    _levels_ok(s, len(q))
+    _levels_ok(s, len(q), model=(k, metric))
     assert le["gmax"] == 300 and le["kf"] == k + 300 and le["rungs"] >= 1       # the leftover's rung run
     if k == 30:
         view_want, _ = _by_views(ix, groups, q, qg, _view_search(30))
@@ -225,11 +231,12 @@ def test_route_variants_keep_the_bits(cuda_device, metric):
         ix.set_fp16_escalation(False)
         _same(ix.search_excluding(qd, 30, qgd), want)
         s = ix.last_exclusion_screen()
-        _levels_ok(s, len(q), second_pass=False)
+        _levels_ok(s, len(q), second_pass=False, model=(30, metric))
         ix.set_fp16_escalation(True)
         full = None
         _same(ix.search_excluding(qd, 30, qgd), want)
         full = ix.last_exclusion_screen()
+        _levels_ok(full, len(q), model=(30, metric))
         assert full["certified0"] == s["certified0"] and full["rung_queries"] < s["rung_queries"]
         # ordering scores and an id_base
         _lib.check(_lib.lib().hb_index_set_score_output(ix._h, 1))

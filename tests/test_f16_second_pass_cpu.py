@@ -19,26 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASE = {c.name: c for c in SR.CASES}
 
 
-@functools.lru_cache(maxsize=None)
-def _inputs(name):
-    """-> (W, kwargs of SR.host_chain: pass_scores / E / cq, the float reference or None, the exact world or None)"""
-    c = CASE[name]
-    W = SR.case_world(c)
-    if c.centred:
-        P = SR.centred_pass(W["queries"], W["bank"], c.metric)
-        return W, {"pass_scores": P["pass_scores"], "E": P["E"], "cq": P["cq"]}, {"s16": P["pass_scores"], "A": P["A"]}, None
-    E = SR.plain_bounds(W["queries"], W["bank"], c.D, c.metric)[2]
-    if c.world == "exact":
-        s2 = R.exact_scores2(W, c.metric)
-        return W, {"pass_scores": s2.astype(np.float64) * (0.5 * 4.0 ** W["scale_log2"]), "E": E}, None, W
-    if c.world == "nonfinite":
-        q16 = W["queries"].astype(np.float16).astype(np.float64)
-        with np.errstate(invalid="ignore"):
-            ps = q16 @ W["bank"].astype(np.float16).astype(np.float64).T
-        skip = ~(SR.query_norms(W["queries"]) <= R.F16_LIMIT)
-        return W, {"pass_scores": np.where(np.isfinite(ps), ps, -np.inf), "E": E}, SR.finite_reference(W["queries"], W["bank"], c.metric, skip), None
-    ref = R.float_reference(W["queries"], W["bank"], c.metric)
-    return W, {"pass_scores": ref["s16"], "E": E}, ref, None
+_inputs = SR.model_inputs      # (shared with tests/test_exclude_seeds_cpu.py)
 
 
 @functools.lru_cache(maxsize=None)
