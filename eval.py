@@ -42,6 +42,53 @@ def grid_key(k: int, beta: float) -> str:
     return f"k={int(k)},beta={float(beta)!r}"
 
 
+def _level(v: str) -> float:
+    f = float(v)
+    if not 0.0 < f < 1.0:
+        raise argparse.ArgumentTypeError("must lie strictly between 0 and 1")
+    return f
+
+
+def bootstrap_key(key) -> str:
+    """How a MiouBootstrap key -- (k, beta), with --memory-sizes (size, k, beta) -- is keyed in the result JSON."""
+    return grid_key(*key) if len(key) == 2 else f"memory_size={int(key[0])}," + grid_key(*key[1:])
+
+
+def headline_key(keys, n_neighbours: int, memory_size):
+    """The key behind the JSON's `miou`: the built bank's own size when listed (else the largest), the plain run's (k, 0.02) when the grid
+    holds it (else the grid's first)."""
+    keys = list(keys)
+    if len(keys[0]) == 3:
+        sizes = [k[0] for k in keys]
+        size = memory_size if memory_size in sizes else max(sizes)
+        keys = [k for k in keys if k[0] == size]
+    want = (int(n_neighbours), 0.02)
+    return next((k for k in keys if tuple(k[-2:]) == want), keys[0])
+
+
+def bootstrap_summary(mb, level: float, head) -> Dict[str, Any]:
+    """The JSON fields of --bootstrap out of a hbird_mi.bootstrap.MiouBootstrap."""
+    out: Dict[str, Any] = {"miou_ci": [float(v) for v in mb.interval(head, level)],
+                           "bootstrap": {"replicates": int(mb.samples.shape[0]), "seed": int(mb.seed), "level": float(level),
+                                         "n_images": int(mb.n_images), "matching_is_identity": bool(all(mb.matching_is_identity.values()))}}
+    if len(mb.keys) > 1:
+        best, tied = mb.best(level)
+        out["miou_grid_ci"] = {bootstrap_key(k): [float(v) for v in mb.interval(k, level)] for k in mb.keys}
+        out["grid_best"] = bootstrap_key(best)
+        out["grid_indistinguishable_from_best"] = [bootstrap_key(k) for k in tied]
+    return out
+
+
+def bootstrap_as_plain(mb, gridded: bool, sized: bool):
+    """The value hbird_evaluation returns WITHOUT bootstrap= for the same flags, out of mb.miou."""
+    if sized:
+        by = {}
+        for (size, k, b), v in mb.miou.items():
+            by.setdefault(size, {})[(k, b)] = v
+        return by if gridded else {size: next(iter(res.values())) for size, res in by.items()}
+    return dict(mb.miou) if gridded else next(iter(mb.miou.values()))
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Hummingbird retrieval evaluation on MI355X (hbird_mi.hbird_evaluation).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -77,6 +124,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--leave-one-out-screen", action="store_true",
                    help="with --leave-one-out: the certified fp16 screen serves the excluding searches where it applies (same scores; the cost of "
                         "plain searches at k instead of searches at k + the largest image's rows)")
+    p.add_argument("--bootstrap", type=_positive_int, default=None, metavar="R",
+                   help="R paired bootstrap replicates over the evaluated images (not in the reference): the result JSON gains miou_ci, and "
+                        "with a grid or --memory-sizes miou_grid_ci, grid_best and grid_indistinguishable_from_best")
+    p.add_argument("--bootstrap-seed", type=int, default=None, metavar="S", help="the resampler's seed (default: the library's)")
+    p.add_argument("--bootstrap-level", type=_level, default=0.95, metavar="L", help="coverage of the percentile intervals")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -169,7 +221,10 @@ def default_ftr_extr_fn(model, imgs):
 
 
 def main(argv: Optional[List[str]] = None) -> None:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.bootstrap_seed is not None and not args.bootstrap:
+        parser.error("--bootstrap-seed needs --bootstrap")
     logging.basicConfig(level=getattr(logging, args.log_level), force=True)
     nn_params = parse_nn_params(args.nn_param)
     set_seed(args.seed)
@@ -188,8 +243,13 @@ def main(argv: Optional[List[str]] = None) -> None:
                               **({"memory_sizes": args.memory_sizes} if args.memory_sizes else {}),
                               **({"leave_one_out": True, "leave_one_out_images": args.leave_one_out_images, "leave_one_out_screen": args.leave_one_out_screen}
                                  if args.leave_one_out else {}),
-                              **({"grid_k": args.grid_k, "grid_beta": args.grid_beta} if args.grid_k or args.grid_beta else {}))
+                              **({"grid_k": args.grid_k, "grid_beta": args.grid_beta} if args.grid_k or args.grid_beta else {}),
+                              **({"bootstrap": args.bootstrap, "bootstrap_seed": args.bootstrap_seed} if args.bootstrap else {}))
     from hbird_mi import hbird_eval as _he
+    boot_fields: Dict[str, Any] = {}
+    if args.bootstrap:
+        boot_fields = bootstrap_summary(result, args.bootstrap_level, headline_key(result.keys, args.n_neighbours, args.memory_size))
+        result = bootstrap_as_plain(result, bool(args.grid_k or args.grid_beta), bool(args.memory_sizes))
     by_size = grid = grid_by_size = None
     if args.grid_k or args.grid_beta:
         def headline(res):      # the configuration the plain run evaluates when the grid holds it, else the grid's first
@@ -214,6 +274,7 @@ def main(argv: Optional[List[str]] = None) -> None:
         summary["miou_grid"] = grid
     if grid_by_size is not None:
         summary["miou_grid_by_memory_size"] = grid_by_size
+    summary.update(boot_fields)
     print(json.dumps(summary))
     if args.out:
         with open(args.out, "w") as f:

@@ -170,6 +170,17 @@ SIGNATURES_EXCLUDE_SCREEN = {
     "hb_index_last_exclusion_seeds": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(c_int64)]),
 }
 
+# ... and include/hbird_hip_bootstrap.h (paired bootstrap over images for mIoU grids, csrc/hbird_bootstrap.hip); a header of its own, not
+# included by hbird_hip.h
+BOOTSTRAP_MAX_IMAGES = 32768          # HB_BOOTSTRAP_MAX_IMAGES
+BOOTSTRAP_MAX_REPLICATES = 1 << 20    # HB_BOOTSTRAP_MAX_REPLICATES
+SIGNATURES_BOOTSTRAP = {
+    "hb_image_class_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "hb_bootstrap_multiplicities": (c_int, [c_int, c_uint64, c_int64, c_int64, c_void_p, c_void_p]),
+    "hb_bootstrap_counts": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "hb_bootstrap_miou": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -191,7 +202,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

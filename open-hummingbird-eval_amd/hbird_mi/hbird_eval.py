@@ -22,6 +22,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
+from hbird_mi import bootstrap as hboot
 from hbird_mi import dist as hdist
 from hbird_mi import ops
 from hbird_mi import tiling
@@ -711,7 +712,7 @@ class HbirdEvaluation:
             self._row_groups_on_index = True
 
     def evaluate_leave_one_out(self, loader, eval_spatial_resolution: int, n_neighbours=None, betas=None, views=None, ignore_index: int = 255,
-                               max_images: Optional[int] = None, window=None, screen: Optional[bool] = None) -> Dict[tuple, float]:
+                               max_images: Optional[int] = None, window=None, screen: Optional[bool] = None, bootstrap=None):
         """`evaluate_grid` of the bank ON ITS OWN TRAINING IMAGES: `loader` yields the bank's images in the order of the build pass (the
         project's data modules do: shuffle=False), the i-th image seen queries with group i, and every search excludes the bank rows of the
         query's own image (`search_aggregate_grid_excluding`) -- so (k, beta, memory size) can be chosen without touching the validation split.
@@ -722,6 +723,7 @@ class HbirdEvaluation:
         `screen`: True / False switches excluding searches on the certified fp16 screen (`HipFlatIndex.set_exclusion_screen`) on / off on every
         bank of the pass, None leaves the indexes as they are; same floats either way.  `self.loo_screen_served` counts the pass's searches
         (batch x bank) that the screen served.
+        `bootstrap=R` or `(R, seed)`: as for `evaluate_grid` -- a `MiouBootstrap` over the images seen instead of the dict.
         ValueError when more images arrive than the bank was built from, for a bank without geometry (`row_groups`), under torch.distributed,
         with a multi-GPU index and with `window=`."""
         from hbird_mi.nn.search_hip import grid_plan
@@ -751,6 +753,9 @@ class HbirdEvaluation:
         plan = grid_plan(self.n_neighbours if n_neighbours is None else n_neighbours, self.beta if betas is None else betas)
         metrics = {key: [PredsmIoU(self.num_classes, self.num_classes, ignore_index=ignore_index, device=self.gpu_device,
                                    store_reordered_preds=False) for _ in plan.configs] for key in banks}
+        boot = hboot.parse_bootstrap(bootstrap)
+        collector = None if boot is None else hboot.ImageCountCollector(self.num_classes, len(banks) * len(plan.configs), ignore_index,
+                                                                        self.gpu_device, capacity=n_images if max_images is None else min(n_images, int(max_images)))
         self.feature_extractor = self.feature_extractor.to(self.device)
         S = eval_spatial_resolution
         limit = n_images if max_images is None else min(n_images, int(max_images))
@@ -771,12 +776,15 @@ class HbirdEvaluation:
                 q = feats.reshape(B * N, D).contiguous()
                 qgroups = torch.arange(seen, seen + B, dtype=torch.int32, device=q.device).repeat_interleave(N)
                 seen += B
-                for key, ev in banks.items():
+                for bank_i, (key, ev) in enumerate(banks.items()):
                     ev.index.use_current_stream()
                     lh = ev.index.search_aggregate_grid_excluding(q, plan.ks, plan.betas, qgroups, id_base=0)
                     self.loo_screen_served += ev.index.last_exclusion_screen()["served"]
                     for i, m in enumerate(metrics[key]):
-                        m.update_from_label_hat(y, lh[i].view(B, N, -1), S)
+                        self._count_batch(m, collector, bank_i * len(plan.configs) + i, y, lh[i].view(B, N, -1), S)
+        if collector is not None:
+            logger.info("Leave-one-out evaluation complete (%d images); bootstrapping.", seen)
+            return self._finish_bootstrap(banks, plan, metrics, collector, boot, views is None)
         out = {}
         for key in banks:
             for (k, beta), m in zip(plan.configs, metrics[key]):
@@ -886,7 +894,7 @@ class HbirdEvaluation:
         return jac
 
     def evaluate_grid(self, val_loader, eval_spatial_resolution: int, n_neighbours=None, betas=None, views=None, ignore_index: int = 255,
-                      window=None, return_knn_details: bool = False) -> Dict[tuple, float]:
+                      window=None, return_knn_details: bool = False, bootstrap=None):
         """`evaluate` for every (k, beta) of a grid out of ONE pass over the loader (not in the reference, where every value of n_neighbours
         or of the temperature costs a full evaluation).  Per batch the tokens are computed once and every bank is searched ONCE, at the largest
         k: the engine's lists are the exact top-k under one total order with deterministic score bits, so the best k are the first k entries
@@ -897,6 +905,9 @@ class HbirdEvaluation:
         `views={key: HbirdEvaluation}`: the banks to evaluate -- evaluators that share this one's extractor, the `memory_view`s of one bank
         (this evaluator itself may be among them); the batch's tokens serve every bank.  Without `views` the bank is this evaluator's.
         -> {(k, beta): mIoU}, with `views` {(key, k, beta): mIoU}.
+        `bootstrap=R` or `(R, seed)`: -> a `hbird_mi.bootstrap.MiouBootstrap` with those keys instead -- `.miou` is the dict above, `.samples`
+        R paired bootstrap replicates over the images of every configuration's identity-matching mIoU (per-image class counts collected from
+        the class maps, resampled on the device; DESIGN.md section 4, "Bootstrap intervals").  None (default): the dict, and the launches, of ever.
         Single index or a HipMultiIndex in one process.  ValueError under torch.distributed, with `window=` and with `return_knn_details`."""
         from hbird_mi.nn.search_hip import grid_plan
         if window is not None:
@@ -920,6 +931,9 @@ class HbirdEvaluation:
         plan = grid_plan(self.n_neighbours if n_neighbours is None else n_neighbours, self.beta if betas is None else betas)
         metrics = {key: [PredsmIoU(self.num_classes, self.num_classes, ignore_index=ignore_index, device=self.gpu_device,
                                    store_reordered_preds=False) for _ in plan.configs] for key in banks}
+        boot = hboot.parse_bootstrap(bootstrap)
+        collector = None if boot is None else hboot.ImageCountCollector.for_loader(val_loader, self.num_classes, len(banks) * len(plan.configs),
+                                                                                   ignore_index, self.gpu_device)
         self.feature_extractor = self.feature_extractor.to(self.device)
         S = eval_spatial_resolution
         logger.info("Starting grid evaluation loop: %d configurations, %d bank(s)...", len(plan.configs), len(banks))
@@ -929,11 +943,14 @@ class HbirdEvaluation:
                 feats = self._tokens(x)
                 B, N, D = feats.shape
                 q = feats.reshape(B * N, D).contiguous()
-                for key, ev in banks.items():
+                for bank_i, (key, ev) in enumerate(banks.items()):
                     ev.index.use_current_stream()
                     lh = ev.index.search_aggregate_grid(q, plan.ks, plan.betas, id_base=0)        # [configs, B * N, C]: one search
                     for i, m in enumerate(metrics[key]):
-                        m.update_from_label_hat(y, lh[i].view(B, N, -1), S)
+                        self._count_batch(m, collector, bank_i * len(plan.configs) + i, y, lh[i].view(B, N, -1), S)
+        if collector is not None:
+            logger.info("Grid evaluation complete; bootstrapping.")
+            return self._finish_bootstrap(banks, plan, metrics, collector, boot, views is None)
         out = {}
         for key in banks:
             for (k, beta), m in zip(plan.configs, metrics[key]):
@@ -941,6 +958,21 @@ class HbirdEvaluation:
                 out[(k, beta) if views is None else (key, k, beta)] = jac
         logger.info("Grid evaluation complete.")
         return out
+
+    @staticmethod
+    def _count_batch(m: PredsmIoU, collector, cfg: int, y: torch.Tensor, label_hat: torch.Tensor, S: int) -> None:
+        """One configuration's batch into its metric; with a collector (bootstrap=) the fused kernel also returns the class map, whose
+        per-image class counts go into the collector's table.  Without one: `update_from_label_hat`, the launches of ever."""
+        if collector is None:
+            m.update_from_label_hat(y, label_hat, S)
+            return
+        pred = ops.upsample_argmax_confusion(label_hat, S, y, m._conf_mat, m.ignore_index, want_map=True)
+        collector.add(cfg, y, pred)
+
+    @staticmethod
+    def _finish_bootstrap(banks, plan, metrics, collector, boot, plain_keys: bool):
+        keys = [(k, beta) if plain_keys else (key, k, beta) for key in banks for (k, beta) in plan.configs]
+        return hboot.finish(keys, [m for key in banks for m in metrics[key]], collector, boot[0], boot[1])
 
     # -- batch prefetch + stage timing of the evaluation loop ---------------------------------------------------------------------
     def _prefetched(self, batches, to_gpu: bool):
@@ -1130,7 +1162,8 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      frame_size: Optional[Tuple[int, int]] = None, window_stride: Optional[int] = None,
                      f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, grid_k=None, grid_beta=None,
                      leave_one_out: bool = False, leave_one_out_images: Optional[int] = None,
-                     leave_one_out_screen: bool = False, memory_sizes=None):
+                     leave_one_out_screen: bool = False, bootstrap: Optional[int] = None, bootstrap_seed: Optional[int] = None,
+                     memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -1150,7 +1183,13 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     with its own rows excluded (`HbirdEvaluation.evaluate_leave_one_out`), so n_neighbours, the temperature and the memory size can be chosen
     without tuning on the validation split; `leave_one_out_images=N` stops after N images; `leave_one_out_screen=True` lets the certified fp16 screen
     serve the excluding searches (`HipFlatIndex.set_exclusion_screen`: same scores, the cost of plain searches at k).  The return shape is that of the call it
-    accompanies: a float, {(k, beta): mIoU} with a grid, {size: ...} with `memory_sizes`.  Same restrictions as the grid."""
+    accompanies: a float, {(k, beta): mIoU} with a grid, {size: ...} with `memory_sizes`.  Same restrictions as the grid.
+    `bootstrap=R` (`bootstrap_seed=`: the resampler's seed, default `hbird_mi.bootstrap.DEFAULT_SEED`): the call returns a
+    `hbird_mi.bootstrap.MiouBootstrap` -- R paired bootstrap replicates over the evaluated images of every configuration's mIoU, with
+    intervals, paired differences and the configurations indistinguishable from the best.  Its keys are (k, beta), with `memory_sizes`
+    (size, k, beta); a run without a grid is a grid of one configuration.  Works with `leave_one_out`; same restrictions as the grid."""
+    if bootstrap is None and bootstrap_seed is not None:
+        raise ValueError("bootstrap_seed needs bootstrap")
     if leave_one_out and (return_knn_details or frame_size is not None):
         raise ValueError("leave_one_out is not available with return_knn_details or sliding windows (frame_size)")
     if memory_sizes is not None and memory_size is None:
@@ -1189,6 +1228,29 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     last_run_info.clear()
     last_run_info.update(bank_loaded=bool(evaluator.bank_loaded), bank_build_s=float(evaluator.bank_build_s),
                          bank_rows=int(evaluator.total_rows), train_batches_loaded=int(evaluator.batches_loaded))
+    if bootstrap is not None:
+        ks, bs = n_neighbours if grid_k is None else grid_k, evaluator.beta if grid_beta is None else grid_beta
+        sized = None
+        if memory_sizes is not None:
+            sized = {}
+            for size in memory_sizes:
+                size = int(size)
+                if size > memory_size or size in sized:
+                    continue
+                sized[size] = evaluator if size == memory_size else evaluator.memory_view(
+                    memory_size=size, rows_per_image=evaluator.num_sampled_features if evaluator.bank_loaded else None)
+        try:
+            if leave_one_out:
+                return evaluator.evaluate_leave_one_out(train_loader, eval_spatial_resolution, n_neighbours=ks, betas=bs, views=sized,
+                                                        ignore_index=effective_ignore, max_images=leave_one_out_images,
+                                                        screen=True if leave_one_out_screen else None, bootstrap=(bootstrap, bootstrap_seed))
+            return evaluator.evaluate_grid(val_loader, eval_spatial_resolution, n_neighbours=ks, betas=bs, views=sized,
+                                           ignore_index=effective_ignore, window=window, return_knn_details=return_knn_details,
+                                           bootstrap=(bootstrap, bootstrap_seed))
+        finally:
+            for ev in (sized or {}).values():
+                if ev is not evaluator:
+                    ev.index.close()
     if leave_one_out:
         gridded = grid_k is not None or grid_beta is not None
         loo = dict(n_neighbours=grid_k if grid_k is not None else n_neighbours, betas=grid_beta if grid_beta is not None else evaluator.beta,

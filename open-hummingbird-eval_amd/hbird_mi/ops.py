@@ -171,3 +171,69 @@ def confusion_update(conf: torch.Tensor, gt: torch.Tensor, pred: torch.Tensor, i
     has = ignore_index is not None
     _lib.check(_lib.lib().hb_confusion_update(_p(gt), _p(pred), gt.numel(), G, P, int(ignore_index) if has else 0,
                                               int(has), _p(conf), _stream(conf)))
+
+
+# ---- paired bootstrap over images (include/hbird_hip_bootstrap.h, csrc/hbird_bootstrap.hip) ---------------------------------------------
+def image_class_counts(gt: torch.Tensor, pred: torch.Tensor, num_classes: int, ignore_index, out: Optional[torch.Tensor] = None,
+                       row_stride: Optional[int] = None) -> torch.Tensor:
+    """gt, pred [B,1,h,w] int64 -> per-image (tp, fp, fn) under the identity matching, int32 [B, G, 3].
+    With `out` (a contiguous int32 CUDA tensor) image b's [G][3] block is written at out.view(-1)[b * row_stride:] and nothing else is
+    touched: the blocks of one configuration inside an image-major table."""
+    _need_cuda(gt, pred, out)
+    if gt.shape != pred.shape or gt.dim() != 4 or gt.shape[1] != 1:
+        raise ValueError(f"gt and pred must both be [B,1,h,w], got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    gt = gt.contiguous().to(torch.int64)
+    pred = pred.contiguous().to(torch.int64)
+    B, _, h, w = gt.shape
+    G = int(num_classes)
+    if out is None:
+        out = torch.empty((B, G, 3), dtype=torch.int32, device=gt.device)
+        row_stride = 3 * G
+    else:
+        if out.dtype != torch.int32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 tensor")
+        if row_stride is None:
+            raise ValueError("row_stride is required with out")
+        if B and (int(row_stride) < 3 * G or (B - 1) * int(row_stride) + 3 * G > out.numel()):
+            raise ValueError("out is too small for B blocks of 3 G counts at this row_stride")
+    has = ignore_index is not None
+    _lib.check(_lib.lib().hb_image_class_counts(_p(gt), _p(pred), B, int(h), int(w), G, int(ignore_index) if has else 0, int(has), _p(out),
+                                                int(row_stride), _stream(gt)))
+    return out
+
+
+def bootstrap_multiplicities(n_img: int, seed: int, R: int, r0: int = 0, device=None) -> torch.Tensor:
+    """Rows r0 .. r0 + R - 1 of the resampler's multiplicities W, int32 [R, n_img]: W[r][i] = #{j : draw(seed, r, j) == i}."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("hbird_mi.ops: CUDA tensors required (the HIP path has no CPU fallback)")
+    out = torch.empty((max(int(R), 0), max(int(n_img), 0)), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().hb_bootstrap_multiplicities(int(n_img), int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), int(R), _p(out), _stream(out)))
+    return out
+
+
+def bootstrap_counts(stats: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
+    """stats [n_img, cols] int32, W [R, n_img] int32 -> W @ stats in int64 [R, cols], exact."""
+    _need_cuda(stats, W)
+    if stats.dtype != torch.int32 or W.dtype != torch.int32 or stats.dim() != 2 or W.dim() != 2 or W.shape[1] != stats.shape[0]:
+        raise ValueError("bootstrap_counts: stats [n_img, cols] and W [R, n_img] must be int32 with matching n_img")
+    stats, W = stats.contiguous(), W.contiguous()
+    out = torch.empty((W.shape[0], stats.shape[1]), dtype=torch.int64, device=stats.device)
+    _lib.check(_lib.lib().hb_bootstrap_counts(_p(stats), stats.shape[0], stats.shape[1], _p(W), W.shape[0], _p(out), _stream(stats)))
+    return out
+
+
+def bootstrap_miou(stats: torch.Tensor, n_cfg: int, num_classes: int, seed: int, R: int, _chunk_replicates: int = 0):
+    """stats [n_img, n_cfg * 3 G] int32 -> (point float64 [n_cfg], samples float64 [R, n_cfg]): the identity-matching mIoU of every
+    configuration on all images and on R paired bootstrap replicates.  `_chunk_replicates` (tests): replicates per pass, 0 = automatic."""
+    _need_cuda(stats)
+    G, n_cfg = int(num_classes), int(n_cfg)
+    if stats.dtype != torch.int32 or stats.dim() != 2 or stats.shape[1] != n_cfg * 3 * G:
+        raise ValueError(f"bootstrap_miou: stats must be int32 [n_img, {n_cfg * 3 * G}], got {stats.dtype} {tuple(stats.shape)}")
+    stats = stats.contiguous()
+    point = torch.empty((n_cfg,), dtype=torch.float64, device=stats.device)
+    samples = torch.empty((int(R), n_cfg), dtype=torch.float64, device=stats.device)
+    _lib.check(_lib.lib().hb_bootstrap_miou(_p(stats), stats.shape[0], n_cfg, G, int(seed) & 0xFFFFFFFFFFFFFFFF, int(R), _p(point), _p(samples),
+                                            int(_chunk_replicates), _stream(stats)))
+    return point, samples
