@@ -656,6 +656,8 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
 extern "C" int hb_index_search(hb_index_t* ix, const float* q, int64_t nq, int k, int64_t id_base, int64_t* out_idx,
                                float* out_dist, int io_on_device) {
     if (!ix) return hb_fail("hb_index_search: NULL index handle");
+    // (k first: an [nq, 0] output of the binding has no address, and the caller's mistake is the k)
+    if (k < 1 || k > HB_MAX_K) return hb_fail("hb_index_search: k must be in [1, " + std::to_string(HB_MAX_K) + "] (faiss-gpu's own limit)");
     if (nq > 0 && (!out_idx || !out_dist)) return hb_fail("hb_index_search: output pointers are NULL");
     return search_impl(ix, q, nq, k, id_base, 0.f, nullptr, out_idx, out_dist, io_on_device, false);
 }

@@ -354,6 +354,8 @@ class HipFlatIndex:
         sg = src.row_groups
         if sg is None or ids.numel() == 0:
             return
+        if sg.numel() != src.ntotal:      # rows were added since set_row_groups: the table is behind the rows (an id beyond it must not index it)
+            return
         part = sg[ids.to(sg.device)]
         mine = self.row_groups
         if appended and mine is not None and mine.numel() + part.numel() == self.ntotal:
