@@ -163,7 +163,7 @@ extern "C" int hb_index_set_fp16_centre(hb_index_t* ix, int on) {
     HB_HIP(hipStreamSynchronize(ix->stream));
     ix->copy16.drop_form();
     if (ix->copy16.flag) HB_HIP(hipMemsetAsync(ix->copy16.flag, 0, 4, ix->stream));      // (the flag speaks of the values of the copy's form)
-    ix->fp16_centre = on; ix->last_centred = 0;
+    ix->fp16_centre = on; ix->last.form_changed();
     ix->f16_adapt = hb_f16_adapt();      // (the failing shares belong to the form that was measured)
     return 0;
 }
@@ -178,7 +178,7 @@ extern "C" int hb_index_fp16_centre_info(const hb_index_t* ix, double out[8]) {
     const bool active = ix->fp16_centre && c.active && ix->copy16.tiles && c.sc;
     if (active) HB_HIP(hipMemcpy(sc, c.sc, 16, hipMemcpyDeviceToHost));
     out[0] = active ? 1.0 : 0.0; out[1] = sc[1]; out[2] = sc[0]; out[3] = bmax; out[4] = sc[3]; out[5] = active ? (double)ix->copy16.centred_rows() : 0.0;
-    out[6] = ix->fp16_centre; out[7] = ix->last_centred;
+    out[6] = ix->fp16_centre; out[7] = ix->last.centred;
     return 0;
 }
 extern "C" int hb_index_last_centre(hb_index_t* ix, float* mu, float* scalars, float* g, float* init16, uint16_t* bank16, float* cq, float* qcn, uint16_t* q16,
@@ -187,65 +187,10 @@ extern "C" int hb_index_last_centre(hb_index_t* ix, float* mu, float* scalars, f
     if (!info) return hb_fail("hb_index_last_centre: info is NULL");
     return hb_centre_readout(ix, mu, scalars, g, init16, bank16, cq, qcn, q16, info);
 }
-// What the level-0 candidate pass of the last search left behind (include/hbird_hip_screen.h): the merged lists and pass scores in `cand`,
-// the first certificates at the start of `fb`.  Host bookkeeping and copies only.
-extern "C" int hb_index_last_screen(hb_index_t* ix, int64_t* cand_rows, float* pass_scores, unsigned char* certified, int64_t capacity_queries, int64_t info[4]) {
-    if (!ix) return hb_fail("hb_index_last_screen: NULL index handle");
-    if (!info) return hb_fail("hb_index_last_screen: info is NULL");
-    info[0] = info[1] = info[2] = info[3] = 0;
-    const hb_index::screen_record& r = ix->screen;
-    if (r.state == HB_SCREEN_OVERWRITTEN)
-        return hb_fail("hb_index_last_screen: the second fp16 pass of the last search has overwritten the first pass's candidates (hb_index_set_fp16_escalation(ix, 1) keeps them)");
-    if (r.state != HB_SCREEN_VALID || !ix->cand || !ix->fb)
-        return hb_fail("hb_index_last_screen: the last search did not take the fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
-    info[0] = r.nq; info[1] = r.kc; info[2] = r.centred; info[3] = r.klw;
-    HB_HIP(hipSetDevice(ix->device));
-    HB_HIP(hipStreamSynchronize(ix->stream));
-    if (!cand_rows && !pass_scores && !certified) return 0;
-    if (capacity_queries < r.nq)
-        return hb_fail("hb_index_last_screen: room for " + std::to_string(capacity_queries) + " queries, the last search had " + std::to_string(r.nq));
-    const size_t n = (size_t)r.nq * r.kc;
-    if (cand_rows) HB_HIP(hipMemcpy(cand_rows, ix->cand, n * 8, hipMemcpyDeviceToHost));
-    if (pass_scores) HB_HIP(hipMemcpy(pass_scores, ix->cand + n * 8, n * 4, hipMemcpyDeviceToHost));
-    if (certified) HB_HIP(hipMemcpy(certified, ix->fb, (size_t)r.nq, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int hb_index_last_screen_seeds(hb_index_t* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
-                                          float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]) {
-    if (!ix) return hb_fail("hb_index_last_screen_seeds: NULL index handle");
-    if (!info) return hb_fail("hb_index_last_screen_seeds: info is NULL");
-    return hb_screen_seeds_readout(ix, kth0, floor0, certified0, queries1, seed1, cand_rows1, pass_scores1, certified1, kth1, capacity_queries, capacity_queries1, info);
-}
-// The plain fp16 copy, its overflow flag and the query tiles of the last plain pass (include/hbird_hip_screen.h).  Host bookkeeping and copies only.
-extern "C" int hb_index_last_fp16_copy(hb_index_t* ix, uint16_t* bank16, uint16_t* q16, int64_t info[8]) {
-    if (!ix) return hb_fail("hb_index_last_fp16_copy: NULL index handle");
-    if (!info) return hb_fail("hb_index_last_fp16_copy: info is NULL");
-    for (int i = 0; i < 8; ++i) info[i] = 0;
-    info[6] = -1;
-    const hb_fp16_copy& copy = ix->copy16;
-    if (!copy.tiles || !copy.flag || !copy.m.has(ix->cap_rows))
-        return hb_fail("hb_index_last_fp16_copy: no fp16 copy for this bank (no screened search yet, a capacity change since, or an automatic index that dropped it)");
-    if (copy.centre.active)
-        return hb_fail("hb_index_last_fp16_copy: the fp16 copy is centred (hb_index_last_centre reads that form)");
-    const int64_t rows = copy.m.rows, n_g = (rows + 31) / 32 * 32;
-    if (n_g > copy.m.cap) return hb_fail("hb_index_last_fp16_copy: the copy holds more rows than it was allocated for");
-    const bool q_ok = copy.q_level >= 0 && !ix->last_centred && !ix->screen.none() && ix->q16 &&
-                      ix->q16.bytes >= (size_t)((copy.q_n + HB_QT - 1) / HB_QT * HB_QT) * ix->dp16 * 2;
-    const int64_t n = q_ok ? copy.q_n : 0, n_qpad = (n + HB_QT - 1) / HB_QT * HB_QT;
-    HB_HIP(hipSetDevice(ix->device));
-    HB_HIP(hipStreamSynchronize(ix->stream));
-    int flag = 0;
-    HB_HIP(hipMemcpy(&flag, copy.flag, 4, hipMemcpyDeviceToHost));
-    info[0] = rows; info[1] = ix->dp16; info[2] = n_g; info[3] = flag; info[4] = copy.overflow; info[5] = n; info[6] = q_ok ? copy.q_level : -1; info[7] = n_qpad;
-    if (q16 && !q_ok)
-        return hb_fail("hb_index_last_fp16_copy: the last search of a caller did not run the plain fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
-    if (bank16 && n_g) HB_HIP(hipMemcpy(bank16, copy.tiles, (size_t)n_g * ix->dp16 * 2, hipMemcpyDeviceToHost));
-    if (q16 && n) HB_HIP(hipMemcpy(q16, ix->q16, (size_t)n_qpad * ix->dp16 * 2, hipMemcpyDeviceToHost));
-    return 0;
-}
+// (hb_index_last_screen, hb_index_last_screen_seeds, hb_index_last_fp16_copy: hbird_readout.hip)
 extern "C" int hb_last_search_path(const hb_index_t* ix, int* path, int* reason) {
     if (!ix || !path || !reason) return hb_fail("hb_last_search_path: NULL pointer");
-    *path = ix->last_path; *reason = ix->last_reason;
+    *path = ix->last.path; *reason = ix->last.reason;
     return 0;
 }
 
@@ -257,12 +202,12 @@ extern "C" int hb_index_set_fp16_escalation(hb_index_t* ix, int mode) {
 }
 extern "C" int hb_index_last_fp16_escalated(const hb_index_t* ix, int64_t* n) {
     if (!ix || !n) return hb_fail("hb_index_last_fp16_escalated: NULL pointer");
-    *n = ix->last_fp16_escalated;
+    *n = ix->last.escalated;
     return 0;
 }
 extern "C" int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n) {
     if (!ix || !n) return hb_fail("hb_index_last_fp16_fallbacks: NULL pointer");
-    *n = ix->last_fp16_fallbacks;
+    *n = ix->last.fallbacks;
     return 0;
 }
 
@@ -410,7 +355,7 @@ extern "C" int hb_index_schedule_info(const hb_index_t* ix, int64_t out[8]) {
 }
 
 int hb_index::bank_changed(hb_bank_event what) {
-    screen.state = HB_SCREEN_NONE;      // (hb_index_last_screen: the record spoke of the bank as it was)
+    last.bank_changed();      // (the read-outs: the buffers spoke of the bank as it was)
     if (what == HB_BANK_EMPTIED) {
         copy16.emptied(); row_copy.m.emptied();      // (a centred copy derives its mean anew; allocations and declined marks stay with the capacity)
         if (copy16.flag) HB_HIP(hipMemsetAsync(copy16.flag, 0, 4, stream));
@@ -630,14 +575,7 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     if (t_idx) { d_idx = (int64_t*)cur; cur += b_idx; }
     if (t_dist) { d_dist = (float*)cur; cur += b_dist; }
     if (b_lab) { d_lab = (float*)cur; cur += b_lab; }
-    {
-        hb_range r("hbird:query_tiles");
-        if (hb_prepare_queries(ix, qd, nq)) return -1;
-    }
-    {
-        hb_range r("hbird:knn");
-        if (hb_launch_knn(ix, qd, nq, k, id_base, d_idx, d_dist)) return -1;
-    }
+    if (hb_search_device(ix, qd, nq, k, id_base, d_idx, d_dist, nullptr)) return -1;
     if (aggregate) {
         hb_range r("hbird:aggregate");
         if (grid) {

@@ -173,10 +173,15 @@ extern "C" int hb_index_last_exclusion(const hb_index_t* ix, int64_t out[4]) {
 
 // The rung route on device pointers: rung 0 at rungs[0] into the workspace's lists, the filter, and rung 1 on the queries it left incomplete.
 // ws: exclude_rungs_bytes(nq, rungs[0]) bytes -- [flags: incomplete count | 256 B] [complete, nq] [rung 0's lists]; rung 1 sizes ix->excl1 once
-// its queries are counted.  Writes last_excl.
+// its queries are counted.  Writes last_excl.  det == nullptr: the rungs ARE the search, and each commits its report like any search of a caller;
+// else (the leftover of a search the screen served) they run detached: their reports and adaptive policy go to *det, which nobody commits.
+static int rung_search(hb_index* ix, const float* qd, int64_t nq, int kf, int64_t id_base, int64_t* idx, float* dist, hb_detached* det) {
+    hb_range range("hbird:search");
+    return hb_search_device(ix, qd, nq, kf, id_base, idx, dist, det);
+}
 static size_t exclude_rungs_bytes(int64_t nq, int kf0) { return 256 + al256((size_t)nq * 4) + al256((size_t)nq * kf0 * 8) + al256((size_t)nq * kf0 * 4); }
 static int exclude_rungs(hb_index* ix, const float* qd, int64_t nq, int k, int64_t id_base, const int32_t* qgd, int64_t* d_oi, float* d_od,
-                         const int* rungs, int n_rungs, char* ws, hipStream_t s) {
+                         const int* rungs, int n_rungs, char* ws, hipStream_t s, hb_detached* det) {
     const int kf0 = rungs[0];
     int32_t* flags = reinterpret_cast<int32_t*>(ws);
     int32_t* complete = reinterpret_cast<int32_t*>(ws + 256);
@@ -187,7 +192,7 @@ static int exclude_rungs(hb_index* ix, const float* qd, int64_t nq, int k, int64
     const float pad = (ix->metric == HB_METRIC_L2 && !ix->score_output) ? INFINITY : -INFINITY;
     ix->last_excl[0] = 1; ix->last_excl[1] = 0; ix->last_excl[2] = kf0; ix->last_excl[3] = ix->gmax;
     // rung 0: hb_index_search's own path (k > 256: its ceiling passes) into the workspace lists, then the filter
-    if (hb_index_search(ix, qd, nq, kf0, id_base, l_idx, l_dist, 1)) return -1;
+    if (rung_search(ix, qd, nq, kf0, id_base, l_idx, l_dist, det)) return -1;
     if (hb_launch_exclude_filter(l_idx, l_dist, nq, kf0, id_base, ix->row_groups, ix->row_groups_n, qgd, k, pad, d_oi, d_od,
                                  n_rungs > 1 ? complete : nullptr, n_rungs > 1 ? flags : nullptr, s)) return -1;
     if (n_rungs > 1) {
@@ -212,7 +217,7 @@ static int exclude_rungs(hb_index* ix, const float* qd, int64_t nq, int k, int64
             exclude_compact_kernel<<<dim3(1), dim3(256), 0, s>>>(complete, qgd, nq, rows, qg1);
             HB_HIP(hipGetLastError());
             if (hb_launch_gather_rows(qd, nq, ix->d, rows, n1, q1, s)) return -1;
-            if (hb_index_search(ix, q1, n1, kf1, id_base, l1_idx, l1_dist, 1)) return -1;
+            if (rung_search(ix, q1, n1, kf1, id_base, l1_idx, l1_dist, det)) return -1;
             if (hb_launch_exclude_filter(l1_idx, l1_dist, n1, kf1, id_base, ix->row_groups, ix->row_groups_n, qg1, k, pad, f_idx, f_dist, nullptr,
                                          nullptr, s)) return -1;
             if (hb_launch_scatter_rows(rows, n1, k, f_idx, f_dist, d_oi, d_od, s)) return -1;
@@ -224,7 +229,7 @@ static int exclude_rungs(hb_index* ix, const float* qd, int64_t nq, int k, int64
 
 // The queries `left` (ascending) that the screen could not certify, through the rungs: compacted, gathered, searched, scattered into the outputs.
 static int exclude_rungs_on(hb_index* ix, const std::vector<int64_t>& left, const float* qd, int64_t nq, int k, int64_t id_base, const int32_t* qgd,
-                            int64_t* d_oi, float* d_od, const int* rungs, int n_rungs, hipStream_t s) {
+                            int64_t* d_oi, float* d_od, const int* rungs, int n_rungs, hipStream_t s, hb_detached* det) {
     const int64_t n = (int64_t)left.size();
     // [rows, n] [complete, nq] [their groups] [their query rows] [their lists] [the rungs' workspace]
     const size_t o_comp = al256((size_t)n * 8), o_qg = o_comp + al256((size_t)nq * 4), o_q = o_qg + al256((size_t)n * 4),
@@ -243,7 +248,7 @@ static int exclude_rungs_on(hb_index* ix, const std::vector<int64_t>& left, cons
     HB_HIP(hipGetLastError());
     if (hb_launch_gather_rows(qd, nq, ix->d, rows, n, q1, s)) return -1;
     HB_HIP(hipStreamSynchronize(s));      // (`done` goes out of use)
-    if (exclude_rungs(ix, q1, n, k, id_base, qg, oi, od, rungs, n_rungs, ix->excl_sub.as<char>(o_ws), s)) return -1;
+    if (exclude_rungs(ix, q1, n, k, id_base, qg, oi, od, rungs, n_rungs, ix->excl_sub.as<char>(o_ws), s, det)) return -1;
     return hb_launch_scatter_rows(rows, n, k, oi, od, d_oi, d_od, s);
 }
 
@@ -308,42 +313,32 @@ extern "C" int hb_index_search_excluding(hb_index_t* ix, const float* q, int64_t
         HB_HIP(hipStreamSynchronize(s));
         if (bad) return hb_fail("hb_index_search_excluding: a query names a group outside [-1, " + std::to_string(ix->n_groups) + ")");
     }
-    hb_excl_screen_result res;
+    hb_search_report rep;
     if (try_screen) {
-        if (hb_launch_knn_excluding(ix, qd, nq, k, id_base, qgd, d_oi, d_od, &res)) return -1;
-        if (!res.served) why_not = HB_EXCL_SCREEN_PATH;
+        if (hb_launch_knn_excluding(ix, qd, nq, k, id_base, qgd, d_oi, d_od, &rep)) return -1;
+        if (!rep.took_candidate_pass()) why_not = HB_EXCL_SCREEN_PATH;
     }
-    for (int i = 0; i < 8; ++i) ix->last_excl_screen[i] = 0;
-    ix->last_excl_screen[1] = why_not;
-    if (!res.served) {
+    int64_t* o = ix->last_excl_screen;
+    for (int i = 0; i < 8; ++i) o[i] = 0;
+    o[1] = why_not;
+    if (!rep.took_candidate_pass()) {
         if (try_screen) {      // the screen declined: the rungs' workspace after all, behind the staged inputs
             if (ix->excl.ensure_keep(b_head + b_rungs, HB_GROW_EXACT, b_head, s)) return -1;
             carve();
         }
-        if (exclude_rungs(ix, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, ix->excl.as<char>(b_head), s)) return -1;
+        if (exclude_rungs(ix, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, ix->excl.as<char>(b_head), s, nullptr)) return -1;
     } else {
-        // The rungs of the leftover are searches of their own; what describes THIS search is its level-0 pass, and the adaptive fp16 policy is left
-        // as that pass' choice left it (an excluding search's failures say nothing about plain searches)
-        const int path0 = ix->last_path, reason0 = ix->last_reason, centred0 = ix->last_centred;
-        const int64_t escalated0 = ix->last_fp16_escalated;
-        const hb_f16_adapt adapt0 = ix->f16_adapt;
-        const int64_t n_left = (int64_t)res.left.size();
-        // ... and so is the record of what its passes left for the read-outs (hb_index_last_screen, hb_index_last_screen_seeds,
-        // hb_index_last_exclusion_seeds): every rung is a search of a caller and wipes it.  The rungs search at kf > 128, the fp32 kernel, which
-        // writes none of `cand`, `fb`, `fb1`; should one of them take the candidate pass after all, the buffers are its own and the read-outs refuse.
-        hb_index::screen_record rec0 = ix->screen;
-        const int64_t passes0 = ix->screen_passes;
+        // What describes THIS search is the report of its passes.  The rungs of the leftover are searches of their own and run detached: their
+        // reports, and what they would teach the adaptive fp16 policy (an excluding search's failures say nothing about plain searches), go to a
+        // scratch pair that is never committed.  They search at kf > 128, the fp32 kernel, which writes none of `cand`, `fb`, `fb1`, `q16`; should
+        // one of them take the candidate pass after all, the buffers are its own and the read-outs refuse.
         ix->last_excl[0] = 0; ix->last_excl[1] = 0; ix->last_excl[2] = 0; ix->last_excl[3] = ix->gmax;
-        int rc = 0;
-        if (n_left > 0) rc = exclude_rungs_on(ix, res.left, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, s);
-        ix->last_path = path0; ix->last_reason = reason0; ix->last_centred = centred0;
-        ix->last_fp16_escalated = escalated0; ix->last_fp16_fallbacks = n_left;
-        ix->f16_adapt = adapt0;
-        if (!rc && ix->screen_passes == passes0) { rec0.left = res.left; ix->screen = std::move(rec0); }
-        else { ix->screen.state = HB_SCREEN_NONE; ix->screen.new_search(false); }
-        if (rc) return -1;
-        int64_t* o = ix->last_excl_screen;
-        o[0] = 1; o[2] = res.kc; o[3] = res.certified0; o[4] = res.sent1; o[5] = res.certified1; o[6] = n_left; o[7] = res.centred;
+        hb_detached scratch{hb_search_report(), ix->f16_adapt};
+        const int rc = rep.n_left() > 0 ? exclude_rungs_on(ix, rep.left, qd, nq, k, id_base, qgd, d_oi, d_od, rungs, n_rungs, s, &scratch) : 0;
+        if (scratch.rep.took_candidate_pass()) rep.buffers_reused();
+        if (ix->commit(std::move(rep), rc)) return -1;
+        const hb_search_report& r = ix->last;
+        o[0] = 1; o[2] = r.kc; o[3] = r.certified0(); o[4] = r.sent1(); o[5] = r.certified1(); o[6] = r.n_left(); o[7] = r.lists_centred;
     }
     if (!io_on_device) {
         HB_HIP(hipMemcpyAsync(out_idx, d_oi, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));

@@ -122,29 +122,7 @@ extern "C" int hb_index_last_exclusion_screen(const hb_index_t* ix, int64_t out[
     return 0;
 }
 
-// What an excluding search the screen served handed on besides its seeds (include/hbird_hip_exclude_screen.h): the second pass' query groups as
-// gathered into `fb`, and the queries left to the rungs.  Host bookkeeping and copies, no launch.
-extern "C" int hb_index_last_exclusion_seeds(hb_index_t* ix, int32_t* groups1, int64_t* left, int64_t capacity_queries1, int64_t capacity_left, int64_t info[2]) {
-    if (!ix) return hb_fail("hb_index_last_exclusion_seeds: NULL index handle");
-    if (!info) return hb_fail("hb_index_last_exclusion_seeds: info is NULL");
-    info[0] = info[1] = 0;
-    const hb_index::screen_record& r = ix->screen;
-    if (r.none() || !r.excluding || !ix->fb)
-        return hb_fail("hb_index_last_exclusion_seeds: the last search was not an excluding one served by the fp16 screen (or the bank has changed since: reset, add, capacity)");
-    const int64_t n1 = r.second_pass_ran() ? r.n1 : 0, n_left = (int64_t)r.left.size();
-    if (n1 > 0 && ((int64_t)r.bad.size() != n1 || r.o_qg1 == 0 || ix->fb.bytes < r.o_qg1 + (size_t)n1 * 4))
-        return hb_fail("hb_index_last_exclusion_seeds: the second pass' groups lie outside the workspace its record names");
-    info[0] = n1; info[1] = n_left;
-    HB_HIP(hipSetDevice(ix->device));
-    HB_HIP(hipStreamSynchronize(ix->stream));
-    if (groups1 && capacity_queries1 < n1)
-        return hb_fail("hb_index_last_exclusion_seeds: room for " + std::to_string(capacity_queries1) + " queries of the second pass, it had " + std::to_string(n1));
-    if (left && capacity_left < n_left)
-        return hb_fail("hb_index_last_exclusion_seeds: room for " + std::to_string(capacity_left) + " queries of the rungs, they had " + std::to_string(n_left));
-    if (groups1 && n1 > 0) HB_HIP(hipMemcpy(groups1, ix->fb + r.o_qg1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    if (left) std::copy(r.left.begin(), r.left.end(), left);
-    return 0;
-}
+// (hb_index_last_exclusion_seeds: hbird_readout.hip)
 
 extern "C" int hb_index_exclude_rerank(hb_index_t* ix, const float* q, int64_t nq, const int64_t* cand_rows, const float* pass_scores, int kc,
                                        const int32_t* qgroups, int k, int64_t id_base, int64_t* out_idx, float* out_dist,

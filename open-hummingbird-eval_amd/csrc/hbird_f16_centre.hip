@@ -313,8 +313,7 @@ int hb_centre_queries(hb_index* ix, int64_t nq, int first, _Float16* q16, hb_cen
     const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
     centre_query_kernel<<<dim3((unsigned)((nqp + 255) / 256)), dim3(256), 0, s>>>(ix->q_tiles, ix->g8, c.mu, c.sc, q16, ix->dp16 / 16, nqp / 32, nq, qcn);
     HB_HIP(hipGetLastError());
-    view->cq = cq; view->qcn = qcn; view->sc = c.sc;
-    c.q_n = nq; c.q_level = first ? 0 : 1;      // (hb_index_last_centre)
+    view->cq = cq; view->qcn = qcn; view->sc = c.sc;      // (whose queries and which level: the pass says so in its report, hb_index_last_centre reads it there)
     return 0;
 }
 
@@ -329,11 +328,12 @@ int hb_centre_readout(hb_index* ix, float* mu, float* scalars, float* g, float* 
     if (!ix->fp16_centre || rows <= 0 || !copy.tiles || !copy.has_centre_arrays() || copy.m.cap < n_init)
         return hb_fail("hb_index_last_centre: no active centred copy (centring off, no screened search yet, a bank without a usable mean, or a reset since)");
     const int n_mu = std::max(ix->dp16, ix->g8 * 8);
-    // the query side: the last search of a caller ran centred and the bank has not changed since (the screen record goes with either)
-    const bool q_ok = c.q_level >= 0 && ix->last_centred && ix->screen.state != HB_SCREEN_NONE && c.qaux.bytes >= 2 * al256((size_t)c.q_n * 4) &&
-                      ix->q16.bytes >= (size_t)((c.q_n + HB_QT - 1) / HB_QT * HB_QT) * ix->dp16 * 2;
-    const int64_t n = q_ok ? c.q_n : 0, n_qpad = (n + HB_QT - 1) / HB_QT * HB_QT;
-    info[0] = rows; info[1] = ix->dp16; info[2] = n_mu; info[3] = n; info[4] = q_ok ? c.q_level : -1; info[5] = n_g; info[6] = n_init; info[7] = n_qpad;
+    // the query side: the last search of a caller ran centred and the bank has not changed since (the report's question)
+    const hb_search_report& r = ix->last;
+    const bool q_ok = r.centred_queries_readable() && c.qaux.bytes >= 2 * al256((size_t)r.q16_n * 4) &&
+                      ix->q16.bytes >= (size_t)((r.q16_n + HB_QT - 1) / HB_QT * HB_QT) * ix->dp16 * 2;
+    const int64_t n = q_ok ? r.q16_n : 0, n_qpad = (n + HB_QT - 1) / HB_QT * HB_QT;
+    info[0] = rows; info[1] = ix->dp16; info[2] = n_mu; info[3] = n; info[4] = q_ok ? r.q16_level : -1; info[5] = n_g; info[6] = n_init; info[7] = n_qpad;
     HB_HIP(hipSetDevice(ix->device));
     HB_HIP(hipStreamSynchronize(ix->stream));
     if ((cq || qcn || q16) && !q_ok)

@@ -10,6 +10,7 @@
 #include "hbird_f16_centre.h"
 #include "hbird_devbuf.h"
 #include "hbird_mirror.h"
+#include "hbird_report.h"
 
 // ---- tile geometry of the kNN kernel (see DESIGN.md "Data layout in HBM") -------------------
 #define HB_RT 32         // rows per fragment tile (MFMA 32x32x2)
@@ -26,11 +27,6 @@ enum hb_bank_event {
     HB_BANK_EMPTIED,       // hb_index_reset: no rows, the same capacity
     HB_BANK_MOVED          // hb_index_reserve: a new capacity (the next search that needs a copy releases the old one and makes it anew)
 };
-
-// hb_index::screen.state
-#define HB_SCREEN_NONE 0          // no level-0 fp16 candidate pass since the bank last changed
-#define HB_SCREEN_VALID 1
-#define HB_SCREEN_OVERWRITTEN 2   // a second fp16 pass (esc == 1) has reused `cand`
 
 // Optional ROCTx range around a host-side phase (shows up under `rocprofv3 --marker-trace`).  The marker library
 // (librocprofiler-sdk-roctx.so, else libroctx64.so) is looked up at run time; without it the ranges are no-ops.
@@ -89,44 +85,24 @@ struct hb_index {
     int fp16 = HB_FP16_AUTO, dp16 = 0;                    // 0 = the fp32 kernel, 1 = always, 2 = where it pays, HB_FP16_AUTO = the certified screen for big exact searches (hb_screen_choose)
     int fp32_pinned = 0;                                 // sticky: the caller steered the fp32 kernel (variant, tuning, clusters, shares, search options): the automatic state stays on it
     int screen_env_off = 0;                              // HBIRD_EXACT_SCREEN=0 when the index was created
-    int last_path = 0, last_reason = 0;                  // what served the last search of a caller (hb_last_search_path)
     hb_dev<unsigned> stamp_keep;                          // the candidate launch's stamps, kept aside while nested searches reuse `state`
     // the lazy copies of the bank (hbird_mirror.h), brought up to date by the first search that needs them and told of the bank by bank_changed
     hb_fp16_copy copy16;                                 // the fp16 tiles of the candidate pass, with their mean-centred form (hbird_f16_centre.hip)
     hb_row_copy row_copy;                                // the bank as fp32 rows for the exact re-rank, where memory allows
     int rerank_copy = 0;                                 // 0 = automatic, 1 = always, 2 = never (hb_index_set_rerank_copy)
     int fp16_centre = 0;                                 // the setting: 0 = the plain fp16 copy (default), 1 = centred (hb_index_set_fp16_centre)
-    int last_centred = 0;                                // the last search of a caller ran its candidate pass on the centred copy
     hb_dev<void> q16;
     hb_dev<char> cand;
     hb_dev<float> bmax;                                  // device scalar: max bank-row norm
     hb_dev<char> mtmp;                                   // first-level lists of a two-level merge
     hb_dev<char> fb;                                     // workspace of the uncertified queries (a caller's search) ...
     hb_dev<char> fb1;                                    // ... and of their second fp16 pass
-    int64_t last_fp16_fallbacks = 0;                     // queries of the last use_fp16 search that the fp32 kernel had to answer ...
-    int64_t last_fp16_escalated = 0;                     // ... and queries whose first certificate failed (second fp16 pass, k' = 256, seeded floors)
     int fp16_escalation = 0;                             // 0 = on (automatic), 1 = off: uncertified queries go straight to the fp32 kernel (round 5)
-    // what the level-0 candidate pass of the last search left in `cand` (lists, pass scores) and at the start of `fb` (first certificates), for
-    // hb_index_last_screen: host bookkeeping only.  Valid from the end of knn_search_f16's level-0 tail until the next level-0 search, a second
-    // pass that reuses `cand`, or a change of the bank (reset, add, capacity).
-    // hb_index_last_screen_seeds reads on: the seeds behind the certificates in `fb` (whatever followed), and of a second pass its size and its
-    // own lists (`cand`, `fb1`), the queries sent to it and where their gathered seeds lie in `fb` -- the fp32 search of what is left takes
-    // `state` and the tail of `fb1` only, so all of it stays until the next search of a caller.
-    struct screen_record {
-        int state = 0; int64_t nq = 0; int kc = 0, klw = 0, centred = 0;      // state: HB_SCREEN_*
-        int excluding = 0;                      // the search dropped row groups (hb_index_search_excluding): the k-th scores are those of the ALLOWED candidates
-        int64_t n1 = 0;                         // queries of the second fp16 pass (0: none ran)
-        int kc1 = 0, klw1 = 0;
-        size_t o_seed1 = 0;                     // byte offset in `fb` of the second pass' gathered seeds [n1]
-        size_t o_qg1 = 0;                       // ... and (excluding) of its gathered query groups [n1]
-        std::vector<int64_t> bad;               // the level-0 queries sent to the second pass, ascending
-        std::vector<int64_t> left;              // (excluding) the level-0 queries handed to the rungs, ascending
-        bool none() const { return state == HB_SCREEN_NONE; }
-        bool second_pass_ran() const { return state == HB_SCREEN_OVERWRITTEN; }
-        void new_search(bool excl) { excluding = excl ? 1 : 0; n1 = 0; kc1 = klw1 = 0; o_seed1 = o_qg1 = 0; bad.clear(); left.clear(); }
-    } screen;
-    int64_t screen_passes = 0;                           // level-0 candidate passes run on this index: a served excluding search keeps its record across
-                                                         // the leftover's rungs only while none of them took one (hb_index_search_excluding)
+    // What the last search of a caller said about itself, and what of `cand`, `fb`, `fb1` and `q16` the read-outs may still hand out
+    // (hbird_report.h).  Searches write the report they are handed; it gets here by commit() alone, from the caller-level entries
+    // (hb_launch_knn, hb_index_search_excluding), and is told of the bank by bank_changed and of the copy's form by hb_index_set_fp16_centre.
+    hb_search_report last;
+    int commit(hb_search_report&& r, int rc) { last = rc ? hb_search_report() : std::move(r); return rc; }      // (a failed search: the empty report, every read-out refuses)
     hb_f16_adapt f16_adapt;                              // adaptive use of use_fp16 in mode 2 (hbird_calibrate.h): moving averages of the failing shares
     hb_dev<char> bigk;                                   // workspace of a search with k > 256 (hb_launch_knn_bigk): one pass's lists and the ceilings
     hb_schedule sched_esc; hb_dev<char> sched_esc_dev;   // the nested searches' work list (the caller's stays cached)
@@ -150,7 +126,7 @@ struct hb_index {
     hb_dev<char> excl_sub;                               // the queries the screen left to the rungs: their rows, groups, query rows and lists
     // the label table goes together with the counter that describes it (the caller has synchronised the stream where work may still read it)
     void drop_labels() { labels.drop(); labels16.drop(); lab_cap = 0; }
-    // The one place that invalidates the screen record and tells the lazy copies: hb_index_add, hb_index_add_from, hb_index_reset and
+    // The one place that tells the report and the lazy copies: hb_index_add, hb_index_add_from, hb_index_reset and
     // hb_index_reserve each call it once (hbird_capi.hip)
     int bank_changed(hb_bank_event what);
 };
@@ -173,14 +149,13 @@ int hb_launch_rows_to_tiles(const float* src, int64_t n_rows, int d, int dp, int
                             float* binit, float* bnorm, int metric, int normalize, int is_bank, hipStream_t s);
 int hb_launch_scores_to_l2(const float* qn2, int64_t nq, int k, float* dist_inout, hipStream_t s);
 int hb_launch_query_aux(const float* q, int64_t nq, int d, float* qn2, float* qnorm, hipStream_t s);
-// what a level-0 search reads of its queries: their fragment tiles in q_tiles, chain ||q||^2 and fp32 norms in q_aux (hbird_knn.hip)
-int hb_prepare_queries(hb_index* ix, const float* q_dev, int64_t nq);
 int hb_launch_tiles_to_rows(const float* tiles, int g8, int d, const int64_t* ids, int64_t n, int64_t id_base, int64_t ntotal,
                             float* out, hipStream_t s);
-int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
-// hb_index_last_screen_seeds (hbird_knn.hip, beside the level workspaces it reads)
-int hb_screen_seeds_readout(hb_index* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
-                            float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]);
+// One search on device pointers, under the hbird:query_tiles / hbird:knn ranges: the queries prepared, the launch (hbird_knn.hip).
+// detached == nullptr: a caller's search, which commits its report to the index.  Else the search writes the report and the adaptive fp16
+// policy it is handed and leaves the index's alone (the leftover's rungs of an excluding search the screen served).
+struct hb_detached { hb_search_report rep; hb_f16_adapt adapt; };
+int hb_search_device(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist, hb_detached* detached);
 int hb_launch_tiles_to_f16(const float* t32, int g8, _Float16* t16, int g16, int64_t n_row_tiles, int64_t rt0, int* overflow,
                            hipStream_t s);
 int hb_launch_tiles_to_row_copy(const float* t32, int g8, float* rows, int rs, int64_t n_row_tiles, int64_t rt0, hipStream_t s);
@@ -232,14 +207,10 @@ int hb_launch_excl_screen_rerank(const hb_rerank_args& a, const float* tiles, in
 int hb_launch_gather_groups(const int32_t* src, int64_t n_src, const int64_t* ids, int64_t n, int32_t* out, hipStream_t s);
 // One excluding search at k on the screen (hbird_knn.hip): the candidate pass of a plain search at k, the excluding re-rank, the second pass for
 // what fails.  What both levels leave uncertified comes back in `left` (ascending query numbers) for the rungs; their output rows hold no result.
-// served == 0: the index's own choice for (nq, k) is not the candidate pass -- nothing was searched or written.
-struct hb_excl_screen_result {
-    int served = 0, kc = 0, centred = 0;
-    int64_t certified0 = 0, sent1 = 0, certified1 = 0;
-    std::vector<int64_t> left;
-};
+// Writes *rep and commits nothing: hb_index_search_excluding does, once the rungs are through.  !rep->took_candidate_pass(): the index's own
+// choice for (nq, k) is not the candidate pass -- nothing was searched or written.  A failure commits the empty report.
 int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, const int32_t* qgroups, int64_t* out_idx, float* out_dist,
-                            hb_excl_screen_result* res);
+                            hb_search_report* rep);
 int hb_launch_patch_label_hist(const int64_t* y, int64_t B, int H, int W, int ps, int C, int map255, float* out,
                                hipStream_t s);
 int hb_launch_normalize_rows(const float* x, int64_t n, int d, float* out, hipStream_t s);

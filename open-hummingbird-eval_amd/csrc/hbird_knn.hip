@@ -615,10 +615,13 @@ struct knn_call {
     const float* q_aux = nullptr;      // [nq] chain ||q||^2 and [nq] fp32 norms of THIS call's queries
     bool score_out = false;            // the ordering score goes out as it is, whatever the metric
     // an excluding search on the screen (hb_launch_knn_excluding): per query the row group its re-rank drops among the candidates (nullptr: a
-    // plain search), where the levels report, and (second pass) the caller's query number of each of this call's queries
+    // plain search) and (second pass) the caller's query number of each of this call's queries
     const int32_t* groups = nullptr;
-    hb_excl_screen_result* excl = nullptr;
     const int64_t* excl_orig = nullptr;
+    // where the search reports and whose adaptive fp16 policy it follows and feeds: the caller-level entry's own (which it commits), or a
+    // detached pair that nobody commits.  Nested calls get the same pointers and write their level's part in sequence.
+    hb_search_report* rep = nullptr;
+    hb_f16_adapt* adapt = nullptr;
 };
 static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist);
 
@@ -660,6 +663,7 @@ struct knn_path {
     bool automatic = false, wide_first = false;
     int how16 = HB_F16_CHAIN;
     bool centred = false;      // this pass runs on the centred copy
+    int64_t fell_back = 0;     // (fp32) queries that count as fallbacks though no pass looked at them: the adaptive skip, an overflowed copy
 };
 static int knn_choose_path(hb_index* ix, const knn_call& c, int64_t nq, int k, knn_path* out) {
     knn_path& p = *out;
@@ -698,20 +702,20 @@ static int knn_choose_path(hb_index* ix, const knn_call& c, int64_t nq, int k, k
     // moving averages of the share of queries that failed the first certificate (r1) and of the share that reached the fp32 kernel (r12):
     // r12 > 1/2 -> the fp32 kernel right away; r1 > 1/2 -> the first pass is skipped, ONE pass with k' = 256 serves all queries; every 16th
     // search walks the whole chain again, so a bank (or a query stream) that changes is noticed.  Same bits on every path.
-    bool skipped = false;
     if (p.f16 && esc == 0 && (c.fp16 == 2 || p.automatic) && ix->fp16_escalation == 0) {       // (the policy itself: hbird_calibrate.cpp, with CPU tests)
-        p.how16 = hb_f16_choose(ix->f16_adapt);
-        if (p.how16 == HB_F16_FP32) { p.f16 = false; skipped = true; p.why = HB_WHY_ADAPTIVE; }
+        p.how16 = hb_f16_choose(*c.adapt);
+        if (p.how16 == HB_F16_FP32) { p.f16 = false; p.fell_back = nq; p.why = HB_WHY_ADAPTIVE; }
         else if (p.how16 == HB_F16_WIDE_FIRST) p.wide_first = true;
     }
-    if (!p.f16 && esc == 0) { ix->last_fp16_fallbacks = skipped ? nq : 0; ix->last_fp16_escalated = 0; }      // a plain fp32 search: nothing fell back (the counters are not left over from an earlier search)
     return 0;
 }
 
 // Bring the fp16 copy of the bank fragment tiles up to date; may turn f16 off (with its reason).  A finite value beyond the fp16 range
 // (|x| > 65504) turns into inf there and the scores into inf / NaN, which the exactness certificate cannot bound: such a bank stays on the
 // fp32 kernel (every query counts as a fallback)
-static int knn_fp16_copy_upkeep(hb_index* ix, bool automatic, int esc, int64_t nq, hipStream_t s0, bool& f16, int& why) {
+static int knn_fp16_copy_upkeep(hb_index* ix, bool automatic, int64_t nq, hipStream_t s0, knn_path& path) {
+    bool& f16 = path.f16;
+    int& why = path.why;
     hb_fp16_copy& copy = ix->copy16;
     if (!copy.flag) { if (copy.flag.ensure(4, HB_GROW_EXACT)) return -1; HB_HIP(hipMemsetAsync(copy.flag, 0, 4, s0)); }
     if (!copy.m.has(ix->cap_rows)) {      // (the bank grew, or the allocation is about to be repeated)
@@ -720,7 +724,6 @@ static int knn_fp16_copy_upkeep(hb_index* ix, bool automatic, int esc, int64_t n
         if (copy.make(ix->cap_rows, (size_t)ix->dp16 * 2, automatic)) {
             if (!automatic) return -1;
             f16 = false; why = HB_WHY_MEMORY;
-            if (esc == 0) { ix->last_fp16_fallbacks = 0; ix->last_fp16_escalated = 0; }
         } else if (hipMemsetAsync(copy.tiles, 0, (size_t)ix->cap_rows * ix->dp16 * 2, s0) != hipSuccess) {
             copy.drop();
             return hb_fail("hb_index_search: zeroing the fp16 copy of the bank failed: " + std::string(hipGetErrorString(hipGetLastError())));
@@ -738,8 +741,7 @@ static int knn_fp16_copy_upkeep(hb_index* ix, bool automatic, int esc, int64_t n
         HB_HIP(hipStreamSynchronize(s0));
     }
     if (f16 && copy.overflow) {
-        f16 = false; why = HB_WHY_OVERFLOW;
-        if (esc == 0) { ix->last_fp16_fallbacks = nq; ix->last_fp16_escalated = 0; }
+        f16 = false; why = HB_WHY_OVERFLOW; path.fell_back = nq;
         if (automatic) copy.drop();      // (nobody asked for this copy, and the flag is sticky: hb_screen_choose keeps the bank on the fp32 kernel without it)
     }
     return 0;
@@ -930,11 +932,10 @@ static int knn_read_time(hb_index* ix, const knn_call& c) {
 // workspace of one level: [certificates nq + 64][exact k-th scores nq][floors for a second pass nq] and, once the failures are
 // known, [their rows][queries][aux][floors][ids][distances]
 // -- a caller's search keeps it in fb, the second fp16 pass in fb1 (the fp32 search of what is left has no failures of its own)
-struct knn_level_buf {
+// (the layout itself: hb_level_layout, hbird_report.h, which the read-outs compute it from as well)
+struct knn_level_buf : hb_level_layout {
     hb_devbuf& buf;
-    size_t o_kth, o_flo, o_rows;
-    knn_level_buf(hb_index* ix, int esc, int64_t nq) : buf(esc == 0 ? ix->fb : ix->fb1), o_kth(al256((size_t)nq + 64)),
-                                                       o_flo(o_kth + al256((size_t)nq * 4)), o_rows(o_flo + al256((size_t)nq * 4)) {}
+    knn_level_buf(hb_index* ix, int esc, int64_t nq) : hb_level_layout(nq), buf(esc == 0 ? ix->fb : ix->fb1) {}
     float* kth() const { return buf.as<float>(o_kth); }
     float* flo() const { return buf.as<float>(o_flo); }
 };
@@ -953,7 +954,9 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     // An excluding search: a floor-seeded fp32 search knows nothing of groups, so what the second pass cannot take is handed back to the caller
     // (hb_index_search_excluding: the rungs, on these queries only)
     if (c.groups && !again16) {
-        for (int64_t b : bad) c.excl->left.push_back(c.excl_orig ? c.excl_orig[b] : b);
+        std::vector<int64_t> left;
+        for (int64_t b : bad) left.push_back(c.excl_orig ? c.excl_orig[b] : b);
+        c.rep->left_to_rungs(std::move(left));
         return 0;
     }
     const size_t o_q = o_rows + al256((size_t)nf * 8), o_aux = o_q + al256((size_t)nf * ix->d * 4), o_seed = o_aux + al256((size_t)nf * 8),
@@ -983,20 +986,19 @@ static int knn_research_failures(hb_index* ix, const knn_call& c, const knn_path
     }
     int rc = hb_launch_query_aux(d_q, nf, ix->d, d_aux, d_aux + nf, s);      // chain ||q||^2 of the re-searched queries (L2 distances)
     knn_call nested;
+    nested.rep = c.rep; nested.adapt = c.adapt;
     nested.esc = again16 ? 1 : 2; nested.seed = d_seed;
     nested.fp16 = again16 ? 1 : 0; nested.timed = false; nested.q_aux = d_aux; nested.score_out = c.score_out;
     if (c.groups) {      // (again16) the second pass drops the same groups: gathered with the queries
         int32_t* d_qg = fbuf.as<int32_t>(o_qg);
         if (!rc) rc = hb_launch_gather_groups(c.groups, nq, d_rows, nf, d_qg, s);
-        nested.groups = d_qg; nested.excl = c.excl; nested.excl_orig = bad.data();
-        c.excl->sent1 = nf;
+        nested.groups = d_qg; nested.excl_orig = bad.data();
     }
-    if (!again16) ix->last_fp16_fallbacks = nf;
-    if (again16) { ix->screen.state = HB_SCREEN_OVERWRITTEN; ix->screen.bad = bad; ix->screen.o_seed1 = o_seed; ix->screen.o_qg1 = c.groups ? o_qg : 0; }      // (the second pass merges into ix->cand)
+    if (again16) c.rep->sent_to_second_pass(bad, o_seed, c.groups ? o_qg : 0);      // (the second pass merges into ix->cand)
+    else c.rep->reached_fp32(nf, esc);
     if (!rc) rc = knn_search(ix, nested, d_q, nf, k, id_base, d_fi, d_fd);
-    if (esc == 0) ix->last_fp16_escalated = nf;
-    if (esc == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, nf, ix->last_fp16_fallbacks);      // (an excluding search's failures say nothing about plain ones)
     if (rc) return -1;
+    if (esc == 0 && !c.groups) hb_f16_observe(*c.adapt, path.how16, nq, nf, c.rep->fallbacks);      // (an excluding search's failures say nothing about plain ones)
     if (hb_launch_scatter_rows(d_rows, nf, k, d_fi, d_fd, out_idx, out_dist, s)) return -1;
     HB_HIP(hipStreamSynchronize(s));         // `bad` and the workspace are reused by the next call
     return 0;
@@ -1014,7 +1016,7 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     if (ix->q16.ensure((size_t)nqp * ix->dp16 * 2, HB_GROW_QUARTER)) return -1;
     // centred: fp16 tiles of q - t mu, c_q and ||q - t mu|| per query; a caller's search also derives t and, from it, the rows' init values
     hb_centre_view cview{nullptr, nullptr, nullptr};
-    if (centred) { if (hb_centre_queries(ix, nq, esc == 0, ix->q16.as<_Float16>(), &cview, s)) return -1; }
+    if (centred) { if (hb_centre_queries(ix, nq, esc == 0, ix->q16.as<_Float16>(), &cview, s)) return -1; }      // (whose queries these are: the level's transition below)
     else if (hb_launch_tiles_to_f16(ix->q_tiles, ix->g8, ix->q16.as<_Float16>(), ix->dp16 / 16, nqp / 32, 0, nullptr, s)) return -1;
     if (ix->cand.ensure((size_t)nq * kc * 12, HB_GROW_QUARTER)) return -1;
     int64_t* cand_idx = ix->cand.as<int64_t>();
@@ -1057,15 +1059,10 @@ static int knn_search_f16(hb_index* ix, const knn_call& c, const knn_path& path,
     std::vector<int64_t> bad;
     for (int64_t i = 0; i < nq; ++i) if (!hc[i]) bad.push_back(i);
     const int64_t nf = (int64_t)bad.size();
-    if (esc == 0) { ix->screen.nq = nq; ix->screen.kc = kc; ix->screen.klw = klw; ix->screen.centred = centred ? 1 : 0; ix->screen.state = HB_SCREEN_VALID; ++ix->screen_passes; }      // (cand and the certificates are complete: the stream is idle)
-    if (esc == 0) { ix->last_fp16_escalated = 0; ix->last_fp16_fallbacks = 0; }
-    if (esc == 1) { ix->screen.n1 = nq; ix->screen.kc1 = kc; ix->screen.klw1 = klw; }      // (hb_index_last_screen_seeds)
-    if (!centred) { ix->copy16.q_n = nq; ix->copy16.q_level = esc; }      // (hb_index_last_fp16_copy)
-    if (esc == 0 && nf == 0 && !c.groups) hb_f16_observe(ix->f16_adapt, path.how16, nq, 0, 0);
-    if (c.groups) {
-        if (esc == 0) { c.excl->served = 1; c.excl->kc = kc; c.excl->centred = centred ? 1 : 0; c.excl->certified0 = nq - nf; }
-        else c.excl->certified1 = nq - nf;
-    }
+    // (cand, q16 and the certificates are complete: the stream is idle)
+    if (esc == 0) c.rep->level0_finished(nq, kc, klw, centred, nf);
+    else c.rep->level1_finished(nq, kc, klw, centred, nf);
+    if (esc == 0 && nf == 0 && !c.groups) hb_f16_observe(*c.adapt, path.how16, nq, 0, 0);
     if (nf > 0 && knn_research_failures(ix, c, path, p, wl, ws, bad, q_dev, nq, k, id_base, out_idx, out_dist, s)) return -1;
     return 0;
 }
@@ -1110,18 +1107,17 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     if (k > 256) return hb_launch_knn_bigk(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
     hipStream_t s = ix->stream;
     const int esc = c.esc;
-    if (esc == 0) { ix->screen.state = HB_SCREEN_NONE; ix->screen.new_search(c.groups != nullptr); }      // (hb_index_last_screen: whatever an earlier search left is about to go)
+    if (esc == 0) c.rep->begin(c.groups != nullptr);
     knn_path path;
     if (knn_choose_path(ix, c, nq, k, &path)) return -1;
-    if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_fp16_copy_upkeep(ix, path.automatic, esc, nq, s, path.f16, path.why)) return -1;
+    if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_fp16_copy_upkeep(ix, path.automatic, nq, s, path)) return -1;
     if (path.f16 && nq > 0 && ix->ntotal > 0 && knn_row_copy_upkeep(ix, s)) return -1;
     path.centred = path.f16 && ix->fp16_centre && ix->copy16.centre.active;
     if (c.groups && !path.f16) {      // an excluding search goes where a plain search at (nq, k) takes the candidate pass, and nowhere else
         if (esc != 0) return hb_fail("hb_index_search_excluding: the second pass of an excluding search left the fp16 screen");
-        c.excl->served = 0;
-        return 0;
+        return 0;      // (the report says so: no candidate pass)
     }
-    if (esc == 0) { ix->last_path = !path.f16 ? HB_PATH_FP32 : path.wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN; ix->last_reason = path.why; ix->last_centred = path.centred ? 1 : 0; }
+    if (esc == 0) c.rep->path_chosen(!path.f16 ? HB_PATH_FP32 : path.wide_first ? HB_PATH_FP16_WIDE : HB_PATH_FP16_CHAIN, path.why, path.centred, path.fell_back);
     if (nq == 0) return 0;
     // score output (sharded searches): the ordering score goes out as it is, whatever the metric
     const int out_metric = c.score_out ? 0 : ix->metric;
@@ -1154,74 +1150,49 @@ static int knn_search(hb_index* ix, const knn_call& c, const float* q_dev, int64
     return knn_search_f32(ix, c, p, wl, ws, nq, k, id_base, out_metric, out_idx, out_dist, s);
 }
 
-int hb_prepare_queries(hb_index* ix, const float* q_dev, int64_t nq) {
+// what a level-0 search reads of its queries: their fragment tiles in q_tiles, chain ||q||^2 and fp32 norms in q_aux
+static int hb_prepare_queries(hb_index* ix, const float* q_dev, int64_t nq) {
     const int64_t nqp = (nq + HB_QT - 1) / HB_QT * HB_QT;
     if (ix->q_tiles.ensure((size_t)nqp * ix->dp * 4, HB_GROW_EXACT)) return -1;
     if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
     if (hb_launch_rows_to_tiles(q_dev, nq, ix->d, ix->dp, 0, ix->q_tiles, nullptr, nullptr, ix->metric, 0, 0, ix->stream)) return -1;
     return hb_launch_query_aux(q_dev, nq, ix->d, ix->q_aux, ix->q_aux + nq, ix->stream);
 }
-// the level-0 call: a caller's search, by the index's settings, on the queries hb_prepare_queries took
-static knn_call knn_level0_call(const hb_index* ix) {
+// the level-0 call: a caller's search, by the index's settings, on the queries hb_prepare_queries took; it reports into *rep
+static knn_call knn_level0_call(hb_index* ix, hb_search_report* rep, hb_f16_adapt* adapt) {
     knn_call c;
     c.fp16 = ix->fp16; c.timed = ix->time_kernels != 0; c.q_aux = ix->q_aux; c.score_out = ix->score_output != 0;
+    c.rep = rep; c.adapt = adapt;
     return c;
 }
 
-// q_tiles / q_aux must already be prepared by the caller (hb_index_search).
-int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist) {
-    return knn_search(ix, knn_level0_call(ix), q_dev, nq, k, id_base, out_idx, out_dist);
+// The caller-level entry of a plain search (q_tiles / q_aux prepared): the report is built here, handed down, and committed when the search is
+// over -- the empty one if it failed.  A detached search writes the pair it was given and commits nothing.
+static int hb_launch_knn(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist, hb_detached* detached) {
+    if (detached) return knn_search(ix, knn_level0_call(ix, &detached->rep, &detached->adapt), q_dev, nq, k, id_base, out_idx, out_dist);
+    hb_search_report rep;
+    const int rc = knn_search(ix, knn_level0_call(ix, &rep, &ix->f16_adapt), q_dev, nq, k, id_base, out_idx, out_dist);
+    return ix->commit(std::move(rep), rc);
+}
+
+int hb_search_device(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, int64_t* out_idx, float* out_dist, hb_detached* detached) {
+    {
+        hb_range r("hbird:query_tiles");
+        if (hb_prepare_queries(ix, q_dev, nq)) return -1;
+    }
+    hb_range r("hbird:knn");
+    return hb_launch_knn(ix, q_dev, nq, k, id_base, out_idx, out_dist, detached);
 }
 
 // An excluding search on the screen (hbird_internal.h): the level-0 call of a plain search at k -- query tiles and norms as hb_index_search
 // prepares them -- with the queries' groups in its context.  The caller has checked 1 <= k <= 128, nq > 0, ntotal > 0 and the group table.
 int hb_launch_knn_excluding(hb_index* ix, const float* q_dev, int64_t nq, int k, int64_t id_base, const int32_t* qgroups, int64_t* out_idx, float* out_dist,
-                            hb_excl_screen_result* res) {
-    if (hb_prepare_queries(ix, q_dev, nq)) return -1;
-    knn_call c = knn_level0_call(ix);
-    c.groups = qgroups; c.excl = res;
-    return knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
-}
-
-// What the chain behind the first candidate pass left (hb_index_last_screen_seeds, include/hbird_hip_screen.h): host bookkeeping and copies, no
-// launch.  Level 0 lies in `fb` behind the certificates (knn_level_buf), the second pass' gathered seeds further back in `fb`, its lists in
-// `cand` and its own certificates and k-th scores in `fb1`.  An excluding search the screen served leaves the same (its k-th scores over the allowed
-// candidates); hb_index_search_excluding puts the record back behind the leftover's rungs, whose fp32 searches touch none of these buffers.
-int hb_screen_seeds_readout(hb_index* ix, float* kth0, float* floor0, unsigned char* certified0, int64_t* queries1, float* seed1, int64_t* cand_rows1,
-                            float* pass_scores1, unsigned char* certified1, float* kth1, int64_t capacity_queries, int64_t capacity_queries1, int64_t info[8]) {
-    for (int i = 0; i < 8; ++i) info[i] = 0;
-    const hb_index::screen_record& r = ix->screen;
-    if (r.none() || !ix->fb)
-        return hb_fail("hb_index_last_screen_seeds: the last search did not take the fp16 candidate pass (or the bank has changed since: reset, add, capacity)");
-    const knn_level_buf l0(ix, 0, r.nq);
-    const int64_t n1 = r.second_pass_ran() ? r.n1 : 0;
-    if (ix->fb.bytes < l0.o_rows) return hb_fail("hb_index_last_screen_seeds: the level-0 workspace is smaller than its record says");
-    if (n1 > 0) {
-        const knn_level_buf l1(ix, 1, n1);
-        if ((int64_t)r.bad.size() != n1 || r.kc1 <= 0 || !ix->cand || !ix->fb1 || ix->cand.bytes < (size_t)n1 * r.kc1 * 12 || ix->fb1.bytes < l1.o_rows ||
-            r.o_seed1 < l0.o_rows || ix->fb.bytes < r.o_seed1 + (size_t)n1 * 4)
-            return hb_fail("hb_index_last_screen_seeds: the second pass' buffers are smaller than its record says");
+                            hb_search_report* rep) {
+    int rc = hb_prepare_queries(ix, q_dev, nq);
+    if (!rc) {
+        knn_call c = knn_level0_call(ix, rep, &ix->f16_adapt);
+        c.groups = qgroups;
+        rc = knn_search(ix, c, q_dev, nq, k, id_base, out_idx, out_dist);
     }
-    info[0] = r.nq; info[1] = r.kc; info[2] = n1; info[3] = n1 ? r.kc1 : 0; info[4] = n1 ? r.klw1 : 0; info[5] = r.centred; info[6] = ix->last_fp16_fallbacks;
-    info[7] = r.klw;
-    HB_HIP(hipSetDevice(ix->device));
-    HB_HIP(hipStreamSynchronize(ix->stream));
-    const bool want0 = kth0 || floor0 || certified0, want1 = queries1 || seed1 || cand_rows1 || pass_scores1 || certified1 || kth1;
-    if (want0 && capacity_queries < r.nq)
-        return hb_fail("hb_index_last_screen_seeds: room for " + std::to_string(capacity_queries) + " queries, the last search had " + std::to_string(r.nq));
-    if (want1 && capacity_queries1 < n1)
-        return hb_fail("hb_index_last_screen_seeds: room for " + std::to_string(capacity_queries1) + " queries of the second pass, it had " + std::to_string(n1));
-    if (kth0) HB_HIP(hipMemcpy(kth0, l0.kth(), (size_t)r.nq * 4, hipMemcpyDeviceToHost));
-    if (floor0) HB_HIP(hipMemcpy(floor0, l0.flo(), (size_t)r.nq * 4, hipMemcpyDeviceToHost));
-    if (certified0) HB_HIP(hipMemcpy(certified0, ix->fb, (size_t)r.nq, hipMemcpyDeviceToHost));
-    if (n1 == 0) return 0;
-    const knn_level_buf l1(ix, 1, n1);
-    const size_t n = (size_t)n1 * r.kc1;
-    if (queries1) std::copy(r.bad.begin(), r.bad.end(), queries1);
-    if (seed1) HB_HIP(hipMemcpy(seed1, ix->fb + r.o_seed1, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    if (cand_rows1) HB_HIP(hipMemcpy(cand_rows1, ix->cand, n * 8, hipMemcpyDeviceToHost));
-    if (pass_scores1) HB_HIP(hipMemcpy(pass_scores1, ix->cand + n * 8, n * 4, hipMemcpyDeviceToHost));
-    if (certified1) HB_HIP(hipMemcpy(certified1, ix->fb1, (size_t)n1, hipMemcpyDeviceToHost));
-    if (kth1) HB_HIP(hipMemcpy(kth1, l1.kth(), (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    return 0;
+    return rc ? ix->commit(hb_search_report(), rc) : 0;
 }

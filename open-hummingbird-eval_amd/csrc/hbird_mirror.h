@@ -36,13 +36,11 @@ struct hb_centre_state {
     hb_dev<float> sc;               // device scalars {cmax = max ||b - mu||, ||mu|| (rounded up), mu.mu, t of the last search}
     hb_dev<char> qaux;              // per search: [c_q nq][||q - t mu|| nq][partial sums of c_q]
     int active = 0;                 // the fp16 copy holds centred rows (0: no copy yet, or a non-finite / all-zero mean: the plain copy)
-    // hb_index_last_centre: host bookkeeping of the last centred pass (hb_centre_queries), whose c_q and ||q - t mu|| lie in qaux
-    int64_t q_n = 0;                // its queries
-    int q_level = -1;               // 0: a caller's pass, 1: the second pass over its uncertified queries, -1: none since the state was dropped
+    // (whose queries' c_q and ||q - t mu|| lie in qaux, and of which level: the search's report, hbird_report.h)
 
     void drop() {
         mu.drop(); g.drop(); init16.drop(); sc.drop(); qaux.drop();
-        active = 0; q_n = 0; q_level = -1;
+        active = 0;
     }
 };
 
@@ -52,9 +50,6 @@ struct hb_fp16_copy {
     hb_bank_mirror m;
     hb_dev<int> flag; int overflow = 0;      // sticky device flag and its host image: a finite bank value overflowed fp16, the fp32 kernel serves this bank
     hb_centre_state centre;
-    // hb_index_last_fp16_copy: host bookkeeping of the last PLAIN candidate pass, whose query tiles lie in the index's q16
-    int64_t q_n = 0;                // its queries
-    int q_level = -1;               // 0: a caller's pass, 1: the second pass over its uncertified queries, -1: none yet
 
     // The tiles for a bank of `cap` rows of row_bytes each; what there was goes first.  quiet (the automatic state, where the copy only buys
     // speed): a failure is noted as "declined at cap" and reported to nobody; else it is the caller's error (hb_fail).  -> 0 / -1

@@ -134,9 +134,9 @@ static void centre_arrays() {
         CHECK(f.make(512, ROW16, false) == 0 && !f.has_centre_arrays());
         CHECK(f.make_centre_arrays(128) == 0 && f.centre.g.bytes == 512 * 4 && f.centre.active == 0 && g_count == 5);
         // a change of the form: everything goes
-        f.centre.active = 1; f.centre.q_n = 7; f.centre.q_level = 0; f.overflow = 1; f.m.declined(512); f.m.converted(300);
+        f.centre.active = 1; f.overflow = 1; f.m.declined(512); f.m.converted(300);
         f.drop_form();
-        CHECK(mirror_is(f.m, 0, 0, -1) && f.overflow == 0 && f.centre.active == 0 && f.centre.q_n == 0 && f.centre.q_level == -1 && !f.centre.mu && g_count == 0);
+        CHECK(mirror_is(f.m, 0, 0, -1) && f.overflow == 0 && f.centre.active == 0 && !f.centre.mu && g_count == 0);
     }
     scenario_end("centre_arrays");
 }

@@ -187,11 +187,11 @@ def test_the_read_out_is_declared_exported_bound_and_documented():
 
 
 def test_the_read_out_is_copies_and_launches_nothing():
-    src = open(os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc", "hbird_exclude_screen.hip")).read()
+    src = open(os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc", "hbird_readout.hip")).read()      # (the read-outs' unit, whose shared helper synchronises)
+    assert "<<<" not in src and "hb_launch" not in src and "hipMemcpyAsync" not in src and src.count("hipStreamSynchronize") == 1
+    assert "HostToDevice" not in src and "hipMemset" not in src
     body = src[src.index('extern "C" int hb_index_last_exclusion_seeds('):]
     body = body[:body.index("\n}\n")]
-    assert "<<<" not in body and "hb_launch" not in body and "hipMemcpyAsync" not in body and "hipStreamSynchronize" in body
-    assert "HostToDevice" not in body and "hipMemset" not in body
-    seeds = open(os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc", "hbird_knn.hip")).read()
-    seeds = seeds[seeds.index("int hb_screen_seeds_readout("):]
+    assert "ro.sync()" in body and body.index("ro.sync()") < body.index("ro.copy(")
+    seeds = src[src.index('extern "C" int hb_index_last_screen_seeds('):]
     assert "excluding" not in seeds[:seeds.index("\n}\n")]          # the refusal is gone

@@ -63,20 +63,27 @@ def test_last_screen_refuses_a_null_handle_with_a_message():
 
 
 def test_the_read_out_is_host_bookkeeping_and_no_kernel_changed():
-    """The read-out adds no kernel and no launch: its code is copies; the flag is set and cleared where the issue of record says."""
+    """The read-out adds no kernel and no launch: its code is copies; the state is set and cleared where the issue of record says -- since the
+    report of a search became one type (csrc/hbird_report.h) by its transitions: the searches and the index name no state themselves."""
     csrc = os.path.join(ROOT, "open-hummingbird-eval_amd", "csrc")
     capi = open(os.path.join(csrc, "hbird_capi.hip")).read()
-    body = capi[capi.index('extern "C" int hb_index_last_screen'):]
+    unit = open(os.path.join(csrc, "hbird_readout.hip")).read()      # the read-outs' unit: no launch anywhere in it
+    assert "<<<" not in unit and "hb_launch" not in unit and unit.count("hipStreamSynchronize(ix->stream)") == 1
+    body = unit[unit.index('extern "C" int hb_index_last_screen('):]
     body = body[:body.index("\n}\n")]
-    assert "<<<" not in body and "hb_launch" not in body and "hipStreamSynchronize(ix->stream)" in body
+    assert "ro.sync()" in body and body.index("ro.sync()") < body.index("ro.copy(")
     knn = open(os.path.join(csrc, "hbird_knn.hip")).read()
-    assert knn.count("HB_SCREEN_VALID") == 1 and knn.count("HB_SCREEN_OVERWRITTEN") == 1 and knn.count("HB_SCREEN_NONE") == 1
+    report = open(os.path.join(csrc, "hbird_report.h")).read()
+    assert "HB_SCREEN_" not in knn and knn.count("level0_finished(") == 1 and knn.count("sent_to_second_pass(") == 1 and knn.count("->begin(") == 1
+    for transition, state in (("level0_finished", "HB_SCREEN_VALID"), ("sent_to_second_pass", "HB_SCREEN_OVERWRITTEN"), ("bank_changed", "HB_SCREEN_BANK_CHANGED")):
+        t = report[report.index("void %s(" % transition):]
+        assert "state = %s" % state in t[:t.index("}")], transition
     f16 = knn[knn.index("static int knn_search_f16"):knn.index("static int knn_search_f32")]
-    assert "HB_SCREEN_VALID" in f16 and f16.index("HB_SCREEN_VALID") > f16.index("hb_launch_rerank")
+    assert "level0_finished(" in f16 and f16.index("level0_finished(") > f16.index("hb_launch_rerank")
     # every change of the bank clears it in ONE place, hb_index::bank_changed: reset, add, a capacity change, and hb_index_add_from (hbird_select.hip)
     hook = capi[capi.index("int hb_index::bank_changed("):]
     hook = hook[:hook.index("\n}\n")]
-    assert capi.count("HB_SCREEN_NONE") == 1 and "screen.state = HB_SCREEN_NONE" in hook
+    assert "HB_SCREEN_" not in capi and capi.count("last.bank_changed()") == 1 and "last.bank_changed()" in hook
     for entry, event in (("hb_index_reset", "HB_BANK_EMPTIED"), ("hb_index_reserve", "HB_BANK_MOVED"), ("hb_index_add", "HB_BANK_APPENDED")):
         body = capi[capi.index('extern "C" int %s(' % entry):]
         assert body[:body.index("\n}\n")].count("bank_changed(%s)" % event) == 1, entry
