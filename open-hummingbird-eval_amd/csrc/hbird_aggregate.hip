@@ -48,25 +48,11 @@ __global__ __launch_bounds__(64) void aggregate_bigk_kernel(const void* __restri
 // The table an aggregation reads: the index's own rows (fp32 or counts), a borrowed table covering a global id range, or (norms_all)
 // the label-sharded form with everybody's norms and this index's own label rows.  `who` names the entry in the error message.
 int hb_k5_table_choose(const hb_index* ix, int64_t id_base, const float* norms_all, int64_t n_all, const char* who, hb_k5_table* t) {
-    t->u16 = ix->label_P > 0;
-    t->labels = t->u16 ? (const void*)ix->labels16 : (const void*)ix->labels;
-    t->P = ix->label_P; t->ls = ix->lab_stride();
-    t->nlabels = ix->nlabels; t->id_base = id_base;
-    t->bnorm = ix->bnorm; t->norm_base = id_base; t->nnorm = ix->nlabels;
-    const bool own_missing = !t->labels || ix->nlabels < ix->ntotal;
-    if (norms_all) {
-        if (own_missing) return hb_fail(std::string(who) + ": label rows missing (hb_index_add_labels)");
-        t->nlabels = ix->ntotal; t->bnorm = norms_all; t->norm_base = 0; t->nnorm = n_all;
-    } else if (ix->ext_labels || ix->ext_labels16) {
-        t->ls = ix->c;                               // borrowed tables are dense [n, C]
-        t->u16 = ix->ext_labels16 != nullptr;
-        t->labels = t->u16 ? (const void*)ix->ext_labels16 : (const void*)ix->ext_labels; t->P = ix->ext_P;
-        t->bnorm = ix->ext_bnorm; t->nlabels = t->nnorm = ix->ext_n; t->id_base = t->norm_base = ix->ext_base;
-    } else if (own_missing) return hb_fail(std::string(who) + ": label rows missing (hb_index_add_labels)");
-    if (!t->u16) t->P = 0;
+    if (ix->lab.view(id_base, ix->ntotal, ix->bnorm, norms_all, n_all, t) == HB_LABELS_ROWS_MISSING)
+        return hb_fail(std::string(who) + ": label rows missing (hb_index_add_labels)");
     // K5's wide gather: rows of whole 16-byte granules at a 16-byte aligned base, the three-instruction quotient's range, at most 64
     // lanes per row, and more classes than the (neighbour group, class) form takes
-    t->wide = t->u16 && (t->ls & 7) == 0 && (reinterpret_cast<uintptr_t>(t->labels) & 15) == 0 && t->P > 0 && t->P <= K5_LUT && ix->c > 32 && ix->c <= 512 ? 1 : 0;
+    t->wide = t->u16 && (t->ls & 7) == 0 && (reinterpret_cast<uintptr_t>(t->labels) & 15) == 0 && t->P > 0 && t->P <= K5_LUT && ix->lab.classes() > 32 && ix->lab.classes() <= 512 ? 1 : 0;
     return 0;
 }
 
@@ -77,7 +63,7 @@ int hb_launch_aggregate(const hb_index* ix, const float* qnorm, const int64_t* i
     hb_k5_table t;
     if (hb_k5_table_choose(ix, id_base, norms_all, n_all, norms_all ? "hb_index_aggregate_partial" : "hb_index_search_aggregate", &t)) return -1;
     const dim3 grid((unsigned)((nq + 3) / 4)), block(256);
-    (t.u16 ? aggregate_kernel<true> : aggregate_kernel<false>)<<<grid, block, 0, s>>>(t.labels, t.ls, t.wide, t.P, t.nlabels, ix->c, t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k, t.id_base, ix->metric, ix->q_aux, beta, out);
+    (t.u16 ? aggregate_kernel<true> : aggregate_kernel<false>)<<<grid, block, 0, s>>>(t.labels, t.ls, t.wide, t.P, t.nlabels, ix->lab.classes(), t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k, t.id_base, ix->metric, ix->q_aux, beta, out);
     HB_HIP(hipGetLastError());
     return 0;
 }
@@ -91,7 +77,7 @@ int hb_launch_aggregate_bigk(const hb_index* ix, const float* qnorm, const int64
     if (hb_k5_table_choose(ix, id_base, norms_all, n_all, norms_all ? "hb_bigk_aggregate_partial" : "hb_bigk_search_aggregate", &t)) return -1;
     if (t.nlabels > 0x7FFFFFFFLL) return hb_fail("hb_bigk_aggregate: label tables of more than 2^31 - 1 rows are not supported");
     const dim3 grid((unsigned)nq), block(64);
-    (t.u16 ? aggregate_bigk_kernel<true> : aggregate_bigk_kernel<false>)<<<grid, block, (size_t)k * 8, s>>>(t.labels, t.ls, t.wide, t.P, t.nlabels, ix->c, t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k, t.id_base, ix->metric, ix->q_aux, beta, out);
+    (t.u16 ? aggregate_bigk_kernel<true> : aggregate_bigk_kernel<false>)<<<grid, block, (size_t)k * 8, s>>>(t.labels, t.ls, t.wide, t.P, t.nlabels, ix->lab.classes(), t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k, t.id_base, ix->metric, ix->q_aux, beta, out);
     HB_HIP(hipGetLastError());
     return 0;
 }

@@ -123,14 +123,10 @@ extern "C" int hb_index_set_stream(hb_index_t* ix, void* s) {
     ix->stream = (hipStream_t)s;
     return 0;
 }
-// the two counters have no status channel: a NULL handle reads as -1 rows (and sets hb_last_error)
+// the two counters have no status channel: a NULL handle reads as -1 rows (and sets hb_last_error); hb_index_nlabels: hbird_labels.hip
 extern "C" int64_t hb_index_ntotal(const hb_index_t* ix) {
     if (!ix) { hb_set_error("hb_index_ntotal: NULL index handle"); return -1; }
     return ix->ntotal;
-}
-extern "C" int64_t hb_index_nlabels(const hb_index_t* ix) {
-    if (!ix) { hb_set_error("hb_index_nlabels: NULL index handle"); return -1; }
-    return ix->nlabels;
 }
 extern "C" int hb_index_set_timing(hb_index_t* ix, int enable) {
     if (!ix) return hb_fail("hb_index_set_timing: NULL index handle");
@@ -400,9 +396,9 @@ extern "C" int hb_index_reset(hb_index_t* ix) {
         HB_HIP(hipStreamSynchronize(s));
     }
     HB_HIP(hipMemsetAsync(ix->bmax, 0, 4, s));
-    ix->ntotal = 0; ix->nlabels = 0; ix->lab_checked = 0;
+    ix->ntotal = 0;
     ix->row_groups_n = 0; ix->n_groups = 0; ix->gmax = 0;      // the row-group table goes with the rows
-    if (ix->lab_flag) HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, s));
+    if (int* flag = ix->lab.emptied()) HB_HIP(hipMemsetAsync(flag, 0, 4, s));
     return ix->bank_changed(HB_BANK_EMPTIED);
 }
 
@@ -444,104 +440,6 @@ extern "C" int hb_index_add(hb_index_t* ix, const float* x, int64_t n, int x_on_
     return ix->bank_changed(HB_BANK_APPENDED);
 }
 
-extern "C" int hb_index_set_label_denominator(hb_index_t* ix, int P) {
-    if (!ix) return hb_fail("hb_index_set_label_denominator: NULL index handle");
-    if (P < 0 || P > 65535) return hb_fail("hb_index_set_label_denominator: the denominator must be in [0, 65535]");
-    if (ix->nlabels > 0 && P != ix->label_P) return hb_fail("hb_index_set_label_denominator: the index already holds label rows");
-    // fp32 values <-> uint16 counts: `lab_cap` describes the buffer of ONE form.  After hb_index_reset (which keeps allocations) a change
-    // of form would leave it describing the other form's buffer -- a null or smaller one: drop both and start from no capacity.
-    if ((P == 0) != (ix->label_P == 0) && (ix->labels || ix->labels16)) {
-        HB_HIP(hipSetDevice(ix->device));
-        HB_HIP(hipStreamSynchronize(ix->stream));
-        ix->drop_labels();
-    }
-    ix->label_P = P;
-    return 0;
-}
-extern "C" int hb_index_labels_to_fp32(hb_index_t* ix) {
-    if (!ix) return hb_fail("hb_index_labels_to_fp32: NULL index handle");
-    if (ix->label_P == 0) return 0;
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    hb_dev<float> nl;
-    const int64_t cap = std::max<int64_t>(ix->nlabels, ix->lab_cap);
-    if (ix->nlabels > 0) {
-        if (nl.ensure((size_t)cap * ix->c * 4, HB_GROW_EXACT)) return -1;
-        // one pass: count j of the value j / P -> (float)j / (float)P, the fp32 value K2 produced (hbird_eval.py:319-320)
-        if (hb_launch_gather_label_counts(ix->labels16, ix->nlabels, ix->c, ix->lab_stride(), ix->label_P, nullptr, ix->nlabels, nl, ix->stream)) return -1;
-    }
-    HB_HIP(hipStreamSynchronize(ix->stream));
-    ix->drop_labels();
-    ix->lab_cap = nl ? cap : 0; ix->labels = std::move(nl); ix->label_P = 0; ix->lab_checked = 0;
-    return 0;
-}
-extern "C" int hb_index_label_denominator(const hb_index_t* ix, int* P) {
-    if (!ix || !P) return hb_fail("hb_index_label_denominator: NULL pointer");
-    *P = ix->label_P;
-    return 0;
-}
-
-// one read-back (a stream synchronisation) after the label table grew: was every stored value a multiple of 1 / P?
-int hb_labels_checked(hb_index* ix) {
-    if (ix->label_P == 0 || ix->lab_checked >= ix->nlabels || !ix->lab_flag) return 0;
-    int bad = 0;
-    HB_HIP(hipMemcpyAsync(&bad, ix->lab_flag, 4, hipMemcpyDeviceToHost, ix->stream));
-    HB_HIP(hipStreamSynchronize(ix->stream));
-    if (bad) return hb_fail("label rows are not multiples of 1 / " + std::to_string(ix->label_P) +
-                            " (hb_index_set_label_denominator): store them as fp32 (denominator 0) instead");
-    ix->lab_checked = ix->nlabels;
-    return 0;
-}
-
-// The label table of `ix` for rows of c classes, with room for n more rows (hb_index_add_labels, hb_index_add_from): a table of another
-// width goes (an emptied index -- hb_index_reset keeps allocations -- takes rows of another width: `lab_cap` counts rows of the OLD width),
-// capacity follows the bank's, else grows x 1.5.  Sets ix->c.
-int hb_labels_ensure(hb_index* ix, int c, int64_t n) {
-    if (ix->c != c && ix->lab_cap > 0) {
-        HB_HIP(hipStreamSynchronize(ix->stream));
-        ix->drop_labels();
-    }
-    ix->c = c;
-    const size_t esz = ix->label_P ? 2 : 4;      // uint16 counts or fp32 values
-    const size_t ls = (size_t)ix->lab_stride();  // elements per stored row (counts: padded to 16 bytes)
-    if (ix->nlabels + n > ix->lab_cap) {
-        int64_t cap = std::max<int64_t>(ix->nlabels + n, std::max<int64_t>(ix->cap_rows, ix->lab_cap + ix->lab_cap / 2));
-        hb_devbuf& table = ix->label_P ? static_cast<hb_devbuf&>(ix->labels16) : ix->labels;
-        if (table.ensure_keep((size_t)cap * ls * esz, HB_GROW_EXACT, (size_t)ix->nlabels * ls * esz, ix->stream)) return -1;
-        ix->lab_cap = cap;
-    }
-    return 0;
-}
-
-extern "C" int hb_index_add_labels(hb_index_t* ix, const float* labels, int64_t n, int c, int on_device) {
-    if (!ix) return hb_fail("hb_index_add_labels: NULL index handle");
-    if (n < 0 || c <= 0) return hb_fail("hb_index_add_labels: bad shape");
-    if (n == 0) return 0;
-    HB_HIP(hipSetDevice(ix->device));
-    if (ix->c != 0 && ix->c != c && ix->nlabels > 0) return hb_fail("hb_index_add_labels: class count changed");
-    if (hb_labels_ensure(ix, c, n)) return -1;
-    const size_t ls = (size_t)ix->lab_stride();  // elements per stored row (counts: padded to 16 bytes)
-    if (ix->label_P) {
-        // values j / P (what K2 produces, hbird_eval.py:319-320) stored as the uint16 count j: half the table, the same fp32 value back
-        if (!ix->lab_flag) { if (ix->lab_flag.ensure(4, HB_GROW_EXACT)) return -1; HB_HIP(hipMemsetAsync(ix->lab_flag, 0, 4, ix->stream)); }
-        const float* src = labels;
-        if (!on_device) {
-            if (ix->tmp.ensure((size_t)n * c * 4, HB_GROW_EXACT)) return -1;
-            if (stage_in(ix, labels, (size_t)n * c * 4, 0)) return -1;
-            src = ix->tmp.as<const float>();
-        }
-        if (hb_launch_labels_to_counts(src, n, c, (int)ls, ix->label_P, ix->labels16 + ix->nlabels * (int64_t)ls, ix->lab_flag, ix->stream)) return -1;
-        if (!on_device) HB_HIP(hipStreamSynchronize(ix->stream));
-        ix->nlabels += n;
-        return 0;
-    }
-    HB_HIP(hipMemcpyAsync(ix->labels + ix->nlabels * (int64_t)c, labels, (size_t)n * c * 4,
-                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
-    if (!on_device) HB_HIP(hipStreamSynchronize(ix->stream));
-    ix->nlabels += n;
-    return 0;
-}
-
 static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t id_base, float beta, float* out_lab,
                        int64_t* out_idx, float* out_dist, int io_on_device, bool aggregate, bool bigk = false, const hb_grid_spec* grid = nullptr) {
     // bigk: the aggregation is aggregate_bigk_kernel's (hb_bigk_search_aggregate), whose k goes as far as the search's
@@ -557,7 +455,7 @@ static int search_impl(hb_index* ix, const float* q, int64_t nq, int k, int64_t 
     // staging area in ix->tmp: [queries (host path)] [idx] [dist] [label_hat (host path)]
     const size_t b_q = io_on_device ? 0 : al256((size_t)nq * ix->d * 4);
     const size_t b_idx = al256((size_t)nq * k * 8), b_dist = al256((size_t)nq * k * 4);
-    const size_t lab_bytes = (size_t)nq * ix->c * 4 * (grid ? (size_t)grid->nk * grid->nb : 1);
+    const size_t lab_bytes = (size_t)nq * ix->lab.classes() * 4 * (grid ? (size_t)grid->nk * grid->nb : 1);
     const size_t b_lab = (aggregate && !io_on_device) ? al256(lab_bytes) : 0;
     const bool t_idx = !io_on_device || !out_idx, t_dist = !io_on_device || !out_dist;
     const size_t need = b_q + (t_idx ? b_idx : 0) + (t_dist ? b_dist : 0) + b_lab;
@@ -601,9 +499,7 @@ extern "C" int hb_index_search(hb_index_t* ix, const float* q, int64_t nq, int k
 }
 
 // neither a borrowed label table nor own label rows for every bank row
-static bool labels_missing(const hb_index* ix) {
-    return !ix->ext_labels && !ix->ext_labels16 && ((!ix->labels && !ix->labels16) || ix->nlabels < ix->ntotal);
-}
+static bool labels_missing(const hb_index* ix) { return ix->lab.missing(ix->ntotal); }
 
 // What every aggregation on GIVEN lists does once its own arguments are checked (nq > 0): the labels' conversion check, the query norms,
 // then `launch(qnorm)`.  zero_if_empty: the output of a label-sharded entry, whose partial sums are zero on a shard without rows.
@@ -613,7 +509,7 @@ static int aggregate_on_lists(hb_index* ix, const char* range_name, const float*
     HB_HIP(hipSetDevice(ix->device));
     if (hb_labels_checked(ix)) return -1;
     if (zero_if_empty && ix->ntotal == 0) {   // an empty shard owns no neighbour
-        HB_HIP(hipMemsetAsync(zero_if_empty, 0, (size_t)nq * ix->c * 4, ix->stream));
+        HB_HIP(hipMemsetAsync(zero_if_empty, 0, (size_t)nq * ix->lab.classes() * 4, ix->stream));
         return 0;
     }
     if (ix->q_aux.ensure((size_t)nq * 2 * 4, HB_GROW_EXACT)) return -1;
@@ -760,81 +656,27 @@ extern "C" int hb_bigk_merge_topk_packed(const void* packed_parts, int64_t part_
                                         parts, nq, k, metric, part_bytes / 4, part_bytes / 8, out_idx, out_dist, (hipStream_t)stream);
 }
 
-static int gather_impl(hb_index* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out, int io_on_device,
-                       bool labels) {
-    const char* who = labels ? "hb_index_gather_labels" : "hb_index_reconstruct";
-    if (n < 0) return hb_fail(std::string(who) + ": n is negative");
+// (hb_index_gather_labels and the label-table entries: hbird_labels.hip)
+extern "C" int hb_index_reconstruct(hb_index_t* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out, int io_on_device) {
+    if (!ix) return hb_fail("hb_index_reconstruct: NULL index handle");
+    if (n < 0) return hb_fail("hb_index_reconstruct: n is negative");
     if (n == 0) return 0;
-    if (!ids || !out) return hb_fail(std::string(who) + ": ids / out is NULL");
+    if (!ids || !out) return hb_fail("hb_index_reconstruct: ids / out is NULL");
     HB_HIP(hipSetDevice(ix->device));
-    const int width = labels ? ix->c : ix->d;
-    if (labels && !ix->labels && !ix->labels16) return hb_fail("hb_index_gather_labels: no labels stored");
-    if (labels && hb_labels_checked(ix)) return -1;
     const int64_t* d_ids = ids;
     float* d_out = out;
     if (!io_on_device) {
         const size_t b_ids = al256((size_t)n * 8);
-        if (ix->tmp.ensure(b_ids + (size_t)n * width * 4, HB_GROW_EXACT)) return -1;
+        if (ix->tmp.ensure(b_ids + (size_t)n * ix->d * 4, HB_GROW_EXACT)) return -1;
         if (stage_in(ix, ids, (size_t)n * 8, 0)) return -1;
         d_ids = ix->tmp.as<const int64_t>();
         d_out = ix->tmp.as<float>(b_ids);
     }
-    if (labels) {
-        // shift global ids to local rows inside the kernel via src offset: ids are global, rows local
-        if (id_base != 0) return hb_fail("hb_index_gather_labels: id_base != 0 is not supported yet");
-        if (ix->label_P ? hb_launch_gather_label_counts(ix->labels16, ix->nlabels, width, ix->lab_stride(), ix->label_P, d_ids, n, d_out, ix->stream)
-                        : hb_launch_gather_rows(ix->labels, ix->nlabels, width, d_ids, n, d_out, ix->stream)) return -1;
-    } else {
-        if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->d, d_ids, n, id_base, ix->ntotal, d_out, ix->stream)) return -1;
-    }
+    if (hb_launch_tiles_to_rows(ix->tiles, ix->g8, ix->d, d_ids, n, id_base, ix->ntotal, d_out, ix->stream)) return -1;
     if (!io_on_device) {
-        HB_HIP(hipMemcpyAsync(out, d_out, (size_t)n * width * 4, hipMemcpyDeviceToHost, ix->stream));
+        HB_HIP(hipMemcpyAsync(out, d_out, (size_t)n * ix->d * 4, hipMemcpyDeviceToHost, ix->stream));
         HB_HIP(hipStreamSynchronize(ix->stream));
     }
-    return 0;
-}
-
-extern "C" int hb_index_reconstruct(hb_index_t* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out,
-                                    int io_on_device) {
-    if (!ix) return hb_fail("hb_index_reconstruct: NULL index handle");
-    return gather_impl(ix, ids, n, id_base, out, io_on_device, false);
-}
-extern "C" int hb_index_gather_labels(hb_index_t* ix, const int64_t* ids, int64_t n, int64_t id_base, float* out,
-                                      int io_on_device) {
-    if (!ix) return hb_fail("hb_index_gather_labels: NULL index handle");
-    return gather_impl(ix, ids, n, id_base, out, io_on_device, true);
-}
-
-extern "C" int hb_index_set_label_table(hb_index_t* ix, const float* labels, const float* bnorm, int64_t n, int c,
-                                        int64_t id_base) {
-    if (!ix) return hb_fail("hb_index_set_label_table: NULL index handle");
-    if (labels && (!bnorm || n <= 0 || c <= 0)) return hb_fail("hb_index_set_label_table: bad arguments");
-    ix->ext_labels = labels; ix->ext_labels16 = nullptr; ix->ext_P = 0;
-    ix->ext_bnorm = bnorm; ix->ext_n = labels ? n : 0; ix->ext_base = labels ? id_base : 0;
-    if (labels) ix->c = c;
-    return 0;
-}
-
-extern "C" int hb_index_set_label_count_table(hb_index_t* ix, const uint16_t* counts, const float* bnorm, int64_t n, int c, int P,
-                                              int64_t id_base) {
-    if (!ix) return hb_fail("hb_index_set_label_count_table: NULL index handle");
-    if (counts && (!bnorm || n <= 0 || c <= 0 || P <= 0 || P > 65535)) return hb_fail("hb_index_set_label_count_table: bad arguments");
-    ix->ext_labels = nullptr; ix->ext_labels16 = counts; ix->ext_P = counts ? P : 0;
-    ix->ext_bnorm = bnorm; ix->ext_n = counts ? n : 0; ix->ext_base = counts ? id_base : 0;
-    if (counts) ix->c = c;
-    return 0;
-}
-
-extern "C" int hb_index_copy_label_counts(hb_index_t* ix, uint16_t* out, int on_device) {
-    if (!ix) return hb_fail("hb_index_copy_label_counts: NULL index handle");
-    if (ix->label_P == 0) return hb_fail("hb_index_copy_label_counts: the labels are stored as fp32 (hb_index_set_label_denominator)");
-    if (ix->nlabels == 0) return 0;
-    HB_HIP(hipSetDevice(ix->device));
-    if (hb_labels_checked(ix)) return -1;
-    // (the stored rows are padded to 16 bytes; the caller gets dense [nlabels, C] rows)
-    HB_HIP(hipMemcpy2DAsync(out, (size_t)ix->c * 2, ix->labels16, (size_t)ix->lab_stride() * 2, (size_t)ix->c * 2, (size_t)ix->nlabels,
-                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ix->stream));
-    if (!on_device) HB_HIP(hipStreamSynchronize(ix->stream));
     return 0;
 }
 

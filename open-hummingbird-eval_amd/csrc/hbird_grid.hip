@@ -260,7 +260,7 @@ int hb_launch_aggregate_grid(const hb_index* ix, const float* qnorm, const int64
     if (t.nlabels > 0x7FFFFFFFLL) return hb_fail("hb_index_aggregate_grid: label tables of more than 2^31 - 1 rows are not supported");
     const dim3 grid((unsigned)nq);
     const int ncfg = gs.nk * gs.nb, kmax = gs.ks[gs.nk - 1];
-    launch_grid(ncfg, t.u16, grid, kmax, s, t.labels, t.ls, t.wide, t.P, t.nlabels, ix->c, t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k_list, t.id_base,
+    launch_grid(ncfg, t.u16, grid, kmax, s, t.labels, t.ls, t.wide, t.P, t.nlabels, ix->lab.classes(), t.bnorm, t.norm_base, t.nnorm, qnorm, idx, dist, nq, k_list, t.id_base,
                 ix->metric, (const float*)ix->q_aux, gs, out);
     HB_HIP(hipGetLastError());
     return 0;

@@ -11,6 +11,7 @@
 #include "hbird_devbuf.h"
 #include "hbird_mirror.h"
 #include "hbird_report.h"
+#include "hbird_labels.h"
 
 // ---- tile geometry of the kNN kernel (see DESIGN.md "Data layout in HBM") -------------------
 #define HB_RT 32         // rows per fragment tile (MFMA 32x32x2)
@@ -44,18 +45,8 @@ struct hb_index {
     hb_dev<float> tiles;                   // fragment-tiled bank  [cap_rows/32][g8][256]
     hb_dev<float> binit;                   // per-row accumulator init [cap_rows]
     hb_dev<float> bnorm;                   // per-row L2 norm (fp32)  [cap_rows]
-    hb_dev<float> labels;                  // [lab_cap][c] fp32 (label_P == 0) ...
-    hb_dev<uint16_t> labels16;             // ... or [lab_cap][lab_stride()] uint16 counts j of values j / label_P (hb_index_set_label_denominator): rows padded to 8 counts = 16 B
-    int label_P = 0;
-    hb_dev<int> lab_flag;                  // sticky device flag: a label value was not a multiple of 1 / label_P
-    int64_t lab_checked = 0;               // label rows whose conversion has been checked (one read-back after the table grew)
-    int c = 0;
-    int64_t nlabels = 0, lab_cap = 0;
-    int lab_stride() const { return label_P ? (c + 7) & ~7 : c; }   // elements per stored label row (counts: 16-byte rows for K5's wide gather)
+    hb_label_store lab;                    // the label table: own rows (fp32 or counts), their counters, the borrowed table (hbird_labels.h)
     int num_cu = 256;
-    // optional borrowed tables covering a GLOBAL id range (multi-GPU: all-gathered labels / norms)
-    const float* ext_labels = nullptr; const float* ext_bnorm = nullptr; int64_t ext_n = 0, ext_base = 0;
-    const uint16_t* ext_labels16 = nullptr; int ext_P = 0;   // the borrowed label table as counts (hb_index_set_label_count_table)
     // search workspace (grown on demand, reused)
     hb_dev<float> q_tiles;
     hb_dev<float> q_aux;                                 // qn2 (chain) and qnorm (fp32), 2*nq floats
@@ -124,8 +115,6 @@ struct hb_index {
     int excl_screen = 0;                                 // the setting: 0 = the rungs serve every excluding search (default), 1 = the screen where it applies
     int64_t last_excl_screen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hb_index_last_exclusion_screen's slots
     hb_dev<char> excl_sub;                               // the queries the screen left to the rungs: their rows, groups, query rows and lists
-    // the label table goes together with the counter that describes it (the caller has synchronised the stream where work may still read it)
-    void drop_labels() { labels.drop(); labels16.drop(); lab_cap = 0; }
     // The one place that tells the report and the lazy copies: hb_index_add, hb_index_add_from, hb_index_reset and
     // hb_index_reserve each call it once (hbird_capi.hip)
     int bank_changed(hb_bank_event what);
@@ -170,17 +159,11 @@ int hb_knn_f16_launch(const knn16_args& args, int grid, hipStream_t s);
 // label storage: fp32 values, or uint16 counts of values j / P (exactly the fp32 value: K2 computes (float)j / (float)P)
 int hb_launch_labels_to_counts(const float* src, int64_t rows, int c, int dst_stride, int P, uint16_t* dst, int* flag, hipStream_t s);
 int hb_launch_gather_label_counts(const uint16_t* src, int64_t src_rows, int c, int src_stride, int P, const int64_t* ids, int64_t n, float* out, hipStream_t s);
-int hb_labels_ensure(hb_index* ix, int c, int64_t n);   // the label table for rows of c classes with room for n more rows (sets ix->c)
-int hb_labels_checked(hb_index* ix);   // 0, or fails when a stored label was not a multiple of 1 / label_P
-// K5 (hbird_aggregate.hip, hbird_grid.hip; device code in hbird_k5_dev.h).  The table one launch reads, chosen in ONE place for all three
-// kernels: label rows (fp32: P = 0) of stride ls covering the global ids [id_base, id_base + nlabels), norms covering
-// [norm_base, norm_base + nnorm), and whether the 16-byte gather of count rows applies.  norms_all: the label-sharded form.
-struct hb_k5_table {
-    const void* labels; bool u16; int P, ls; int64_t nlabels;
-    const float* bnorm; int64_t norm_base, nnorm;
-    int64_t id_base;
-    int wide;
-};
+// (hbird_labels.hip) room for n more label rows of c classes, after the synchronisation a drop needs; the one read-back after the table grew
+int hb_labels_ensure(hb_index* ix, int c, int64_t n);
+int hb_labels_checked(hb_index* ix);   // 0, or fails when a stored label was not a multiple of 1 / P
+// K5 (hbird_aggregate.hip, hbird_grid.hip; device code in hbird_k5_dev.h).  The table one launch reads (hb_k5_table, hbird_labels.h): the
+// store's view, and whether the 16-byte gather of count rows applies.  norms_all: the label-sharded form.
 int hb_k5_table_choose(const hb_index* ix, int64_t id_base, const float* norms_all, int64_t n_all, const char* who, hb_k5_table* t);
 int hb_launch_aggregate(const hb_index* ix, const float* qnorm, const int64_t* idx, const float* dist, int64_t nq,
                         int k, int64_t id_base, float beta, float* out, hipStream_t s, const float* norms_all = nullptr, int64_t n_all = 0);

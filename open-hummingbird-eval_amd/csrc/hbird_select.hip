@@ -76,8 +76,6 @@ __global__ __launch_bounds__(256) void select_label_rows_kernel(const T* __restr
     dst[t] = src[sid * per_row + p];
 }
 
-static inline bool has_labels(const hb_index* ix) { return ix->nlabels > 0 && (ix->labels || ix->labels16); }
-
 extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const int64_t* ids, int64_t n, int ids_on_device) {
     if (!dst || !src) return hb_fail("hb_index_add_from: NULL index handle");
     if (n < 0) return hb_fail("hb_index_add_from: negative row count");
@@ -85,10 +83,10 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
     if (src->d != dst->d) return hb_fail("hb_index_add_from: the indexes differ in d (" + std::to_string(src->d) + " vs " + std::to_string(dst->d) + ")");
     if (src->metric != dst->metric) return hb_fail("hb_index_add_from: the indexes differ in metric");
     if (src->device != dst->device) return hb_fail("hb_index_add_from: the indexes live on different devices");
-    const bool labs = has_labels(src);
+    const bool labs = src->lab.own_rows();
     if (labs) {
-        if (dst->nlabels != dst->ntotal) return hb_fail("hb_index_add_from: the destination's label rows do not cover its rows (nlabels != ntotal)");
-        if (dst->ntotal > 0 && (dst->c != src->c || dst->label_P != src->label_P))
+        if (dst->lab.rows() != dst->ntotal) return hb_fail("hb_index_add_from: the destination's label rows do not cover its rows (nlabels != ntotal)");
+        if (dst->ntotal > 0 && (dst->lab.classes() != src->lab.classes() || dst->lab.denominator() != src->lab.denominator()))
             return hb_fail("hb_index_add_from: the destination holds label rows of another class count or label denominator");
     }
     if (n == 0) return 0;
@@ -114,13 +112,13 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
         d_ids = dst->tmp.as<const int64_t>(256);
     }
     HB_HIP(hipMemsetAsync(flag, 0, 4, s));
-    select_check_ids_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(d_ids, n, src->ntotal, labs ? src->nlabels : src->ntotal, flag);
+    select_check_ids_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(d_ids, n, src->ntotal, labs ? src->lab.rows() : src->ntotal, flag);
     HB_HIP(hipGetLastError());
     int bad = 0;
     HB_HIP(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
     HB_HIP(hipStreamSynchronize(s));
     if (bad & 1) return hb_fail("hb_index_add_from: an id lies outside [0, " + std::to_string(src->ntotal) + ") (the source's rows)");
-    if (bad & 2) return hb_fail("hb_index_add_from: an id lies beyond the source's " + std::to_string(src->nlabels) + " label rows");
+    if (bad & 2) return hb_fail("hb_index_add_from: an id lies beyond the source's " + std::to_string(src->lab.rows()) + " label rows");
     // nothing of the destination has changed so far; from here on the call only fails where hb_index_add would
     if (dst->ntotal + n > dst->cap_rows) {
         const int64_t want = std::max<int64_t>(dst->ntotal + n, dst->cap_rows + dst->cap_rows / 2);
@@ -128,13 +126,12 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
     }
     if (labs) {
         // an empty destination adopts the source's class count and label denominator (a failing allocation leaves them as they were)
-        const int old_c = dst->c, old_P = dst->label_P;
-        if (dst->ntotal == 0 && dst->label_P != src->label_P && hb_index_set_label_denominator(dst, src->label_P)) return -1;
-        if (hb_labels_ensure(dst, src->c, n)) {
-            const std::string msg = hb_last_error();
-            if (dst->nlabels == 0 && !dst->labels && !dst->labels16) { dst->c = old_c; dst->label_P = old_P; }
-            return hb_fail(msg);
+        hb_label_form old = dst->lab.form();
+        if (dst->ntotal == 0) {
+            if (dst->lab.adopt_drops(src->lab.classes(), src->lab.denominator())) HB_HIP(hipStreamSynchronize(s));
+            old = dst->lab.adopt(src->lab.classes(), src->lab.denominator());
         }
+        if (hb_labels_ensure(dst, src->lab.classes(), n)) { dst->lab.restore(old); return -1; }
     }
     const int64_t row0 = dst->ntotal;
     const int64_t n_rt = ((row0 + n - 1) >> 5) - (row0 >> 5) + 1;
@@ -142,27 +139,22 @@ extern "C" int hb_index_add_from(hb_index_t* dst, const hb_index_t* src, const i
                                                                          src->bnorm, dst->binit, dst->bnorm);
     HB_HIP(hipGetLastError());
     if (labs) {
-        const size_t row_bytes = (size_t)dst->lab_stride() * (dst->label_P ? 2 : 4);
+        const size_t row_bytes = dst->lab.row_bytes();
         if (row_bytes % 16 == 0) {
             const int per = (int)(row_bytes / 16);
-            const uint4* sp = dst->label_P ? src->labels16.as<const uint4>() : src->labels.as<const uint4>();
-            uint4* dp = (dst->label_P ? dst->labels16.as<uint4>() : dst->labels.as<uint4>()) + dst->nlabels * (int64_t)per;
-            select_label_rows_kernel<uint4><<<dim3((unsigned)((n * per + 255) / 256)), dim3(256), 0, s>>>(sp, src->nlabels, per, d_ids, n, dp);
+            select_label_rows_kernel<uint4><<<dim3((unsigned)((n * per + 255) / 256)), dim3(256), 0, s>>>(src->lab.own_base<const uint4>(), src->lab.rows(), per, d_ids, n,
+                                                                                                         dst->lab.own_tail<uint4>());
         } else {
-            const int per = dst->c;
-            select_label_rows_kernel<float><<<dim3((unsigned)((n * per + 255) / 256)), dim3(256), 0, s>>>(src->labels, src->nlabels, per, d_ids, n,
-                                                                                                         dst->labels + dst->nlabels * (int64_t)per);
+            const int per = dst->lab.classes();
+            select_label_rows_kernel<float><<<dim3((unsigned)((n * per + 255) / 256)), dim3(256), 0, s>>>(src->lab.own_base<const float>(), src->lab.rows(), per, d_ids, n,
+                                                                                                         dst->lab.own_tail<float>());
         }
         HB_HIP(hipGetLastError());
     }
     // max bank-row norm over the new rows, as hb_index_add: the fp16 screen's certificate is bounded by it
     if (hb_launch_bnorm_max(dst->bnorm + row0, n, dst->bmax, s)) return -1;
     dst->ntotal += n;
-    if (labs) {
-        // counts that were valid in the source stay valid: no conversion happened, so there is nothing new to check
-        if (dst->lab_checked == dst->nlabels) dst->lab_checked = dst->nlabels + n;
-        dst->nlabels += n;
-    }
+    if (labs) dst->lab.appended(n, false);      // (no conversion happened: nothing new to check)
     return dst->bank_changed(HB_BANK_APPENDED);      // (the lazy copies follow at the next screened search, as after hb_index_add)
 }
 
@@ -175,7 +167,7 @@ extern "C" int hb_index_select_rows(const hb_index_t* src, const int64_t* ids, i
     hb_index_t* v = nullptr;
     if (hb_index_create(src->d, src->metric, src->device, &v)) return -1;
     v->stream = src->stream;      // (the view's work is queued where the source's is; hb_index_set_stream moves it)
-    if (has_labels(src)) { v->label_P = src->label_P; v->c = src->c; }
+    if (src->lab.own_rows()) v->lab.adopt(src->lab.classes(), src->lab.denominator());
     if (hb_index_reserve(v, n) || hb_index_add_from(v, src, ids, n, ids_on_device)) {
         const std::string msg = hb_last_error();
         hb_index_free(v);

@@ -19,8 +19,8 @@ AGG_LUT = 2048                                     # K5_LUT of hbird_k5_dev.h
 
 def agg_table(form, C):
     """(uint16?, row stride in elements, 16-byte aligned base?, P) of a table form.
-    Own rows: hb_k5_table_choose (hbird_aggregate.hip) with lab_stride() = counts padded to 8 (hbird_internal.h), device allocations aligned.
-    Borrowed rows: its `ext_labels || ext_labels16` branch -- dense [n, C], stride C."""
+    Own rows: hb_label_store::view (hbird_labels.h, called by hb_k5_table_choose of hbird_aggregate.hip) with stride() = counts padded to 8,
+    device allocations aligned.  Borrowed rows: its `borrowed()` branch -- dense [n, C], stride C."""
     P = agg.FORM_P[form]
     if form == "own_f32":
         return False, C, True, 0
