@@ -181,6 +181,18 @@ SIGNATURES_BOOTSTRAP = {
     "hb_bootstrap_miou": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
+# ... and include/hbird_hip_kmeans.h (k-means over the resident bank, csrc/hbird_kmeans.hip: the clustering of the overclustering protocol), which
+# hbird_hip.h includes
+KMEANS_MAX_K = 2048              # HB_KMEANS_MAX_K
+KMEANS_CHUNK_ROWS = 131072       # HB_KMEANS_CHUNK_ROWS
+SIGNATURES_KMEANS = {
+    "hb_kmeans_assign": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "hb_kmeans_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "hb_kmeans_centroids": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+    "hb_kmeans_fit": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_double), POINTER(c_int),
+                              POINTER(c_int)]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -202,7 +214,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

@@ -974,6 +974,80 @@ class HbirdEvaluation:
         keys = [(k, beta) if plain_keys else (key, k, beta) for key in banks for (k, beta) in plan.configs]
         return hboot.finish(keys, [m for key in banks for m in metrics[key]], collector, boot[0], boot[1])
 
+    # -- overclustering: k-means over the bank, clusters matched to classes (hbird_mi/kmeans.py) -----------------------------------
+    OVERCLUSTERING_MATCHINGS = {"hungarian": dict(many_to_one=False, precision_based=False),
+                                "many_to_one": dict(many_to_one=True, precision_based=False),
+                                "many_to_one_precision": dict(many_to_one=True, precision_based=True)}
+
+    def _overclustering_checks(self, who: str) -> None:
+        if self.world > 1 or self.sharded:
+            raise ValueError(f"{who}: not available under torch.distributed (row shards or replicas): k-means runs on one index")
+        if not isinstance(self.index, HipFlatIndex):
+            raise ValueError(f"{who}: k-means runs on one HipFlatIndex -- a HipMultiIndex (row shards or replicas) is not supported yet")
+
+    def kmeans(self, n_clusters: int, seed: int = 0, max_iter: int = 20):
+        """`hbird_mi.kmeans.kmeans_fit` on this evaluator's bank (its stored rows are L2-normalised): a `KMeansResult`."""
+        from hbird_mi.kmeans import kmeans_fit
+        self._overclustering_checks("kmeans")
+        with torch.cuda.device(self.gpu_device):
+            return kmeans_fit(self.index, n_clusters, seed=seed, max_iter=max_iter)
+
+    def evaluate_overclustering(self, val_loader, eval_spatial_resolution: int, n_clusters, seed: int = 0, max_iter: int = 20,
+                                matching: Optional[str] = None, ignore_index: int = 255, window=None, return_knn_details: bool = False):
+        """The overclustering protocol (not in the reference's evaluator, whose `PredsmIoU` carries its matching modes): the bank's tokens are
+        clustered with k-means into K clusters, every validation token takes the cluster of its nearest centroid, the cluster map is upsampled
+        like a prediction and the clusters are matched to the ground-truth classes.  `n_clusters`: a K or a list (duplicates dropped, sorted);
+        one fit per K, then ONE validation pass.  Per batch: tokens -> `ops.normalize_rows` (L2 assignment depends on the norm; the retrieval
+        path hands its queries over un-normalised) -> per K `KMeansResult.assign` -> one-hot fp32 [B, N, K] (an id of -1: an all-zero row) ->
+        the fused upsample + argmax + confusion kernel into a `PredsmIoU(num_pred_classes=K, num_gt_classes=C)`.
+        `matching`: None picks Hungarian matching for K <= C and many-to-one on precision for K > C; "hungarian", "many_to_one" and
+        "many_to_one_precision" force one.  -> {K: mIoU}; `last_overclustering[K]` keeps the confusion matrix (int64 [C, K], CPU), the matching
+        used and the fit's n_iter / converged / history.  ValueError with sliding windows, with return_knn_details and under torch.distributed."""
+        from hbird_mi.kmeans import check_n_clusters
+        who = "evaluate_overclustering"
+        if window is not None:
+            raise ValueError(f"{who}: sliding windows (window=) are not supported")
+        if return_knn_details:
+            raise ValueError(f"{who}: return_knn_details is not supported (there are no neighbours)")
+        self._overclustering_checks(who)
+        if matching is not None and matching not in self.OVERCLUSTERING_MATCHINGS:
+            raise ValueError(f"{who}: matching={matching!r} (None, {', '.join(repr(m) for m in self.OVERCLUSTERING_MATCHINGS)})")
+        ks = [n_clusters] if not isinstance(n_clusters, (list, tuple)) else list(n_clusters)
+        if not ks:
+            raise ValueError(f"{who}: n_clusters is empty")
+        ks = sorted({check_n_clusters(k, self.index.ntotal, who) for k in ks})
+        C = self.num_classes
+        fits = {}
+        try:
+            for K in ks:
+                fits[K] = self.kmeans(K, seed=seed, max_iter=max_iter)
+                logger.info("k-means K=%d: %d iterations, converged=%s", K, fits[K].n_iter, fits[K].converged)
+            metrics = {K: PredsmIoU(K, C, ignore_index=ignore_index, device=self.gpu_device, store_reordered_preds=False) for K in ks}
+            self.feature_extractor = self.feature_extractor.to(self.device)
+            S = eval_spatial_resolution
+            with torch.no_grad(), torch.cuda.device(self.gpu_device):
+                for bi, (x, y) in tqdm(self._prefetched(enumerate(val_loader), True), desc="Overclustering evaluation loop"):
+                    y = (y.to(self.gpu_device) * 255).long()
+                    feats = self._tokens(x)
+                    B, N, D = feats.shape
+                    q = ops.normalize_rows(feats.reshape(B * N, D).contiguous())
+                    for K in ks:
+                        ids = fits[K].assign(q)
+                        one_hot = (ids.view(-1, 1) == torch.arange(K, device=ids.device).view(1, -1)).to(torch.float32)
+                        metrics[K].update_from_label_hat(y, one_hot.view(B, N, K), S)        # K6 + K7, num_pred = K
+            out, self.last_overclustering = {}, {}
+            for K in ks:
+                mode = matching if matching is not None else ("hungarian" if K <= C else "many_to_one_precision")
+                out[K] = metrics[K].compute(is_global_zero=True, sync_distributed=False, return_reordered=False,
+                                            **self.OVERCLUSTERING_MATCHINGS[mode])[0]
+                self.last_overclustering[K] = dict(confusion=metrics[K]._conf_mat.cpu(), matching=mode, n_iter=fits[K].n_iter,
+                                                   converged=fits[K].converged, history=fits[K].history)
+        finally:
+            for f in fits.values():
+                f.close()
+        logger.info("Overclustering evaluation complete.")
+        return out
+
     # -- batch prefetch + stage timing of the evaluation loop ---------------------------------------------------------------------
     def _prefetched(self, batches, to_gpu: bool):
         """(bi, (x, y)) of `batches`, one batch ahead: while the caller works on batch i, batch i + 1 is pulled from the loader (its
@@ -1163,7 +1237,7 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, grid_k=None, grid_beta=None,
                      leave_one_out: bool = False, leave_one_out_images: Optional[int] = None,
                      leave_one_out_screen: bool = False, bootstrap: Optional[int] = None, bootstrap_seed: Optional[int] = None,
-                     memory_sizes=None):
+                     overclustering=None, overclustering_seed: int = 0, overclustering_iters: int = 20, memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -1187,7 +1261,23 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     `bootstrap=R` (`bootstrap_seed=`: the resampler's seed, default `hbird_mi.bootstrap.DEFAULT_SEED`): the call returns a
     `hbird_mi.bootstrap.MiouBootstrap` -- R paired bootstrap replicates over the evaluated images of every configuration's mIoU, with
     intervals, paired differences and the configurations indistinguishable from the best.  Its keys are (k, beta), with `memory_sizes`
-    (size, k, beta); a run without a grid is a grid of one configuration.  Works with `leave_one_out`; same restrictions as the grid."""
+    (size, k, beta); a run without a grid is a grid of one configuration.  Works with `leave_one_out`; same restrictions as the grid.
+    `overclustering=[K, ...]` (`overclustering_seed=`, `overclustering_iters=`: the k-means initialisation's seed and its iteration limit): the
+    overclustering protocol instead of the retrieval one -- k-means over the bank, clusters matched to classes
+    (`HbirdEvaluation.evaluate_overclustering`); the call returns {K: mIoU}.  Not with a grid, `memory_sizes`, `leave_one_out` or `bootstrap`,
+    nor with sliding windows, return_knn_details or torch.distributed (ValueError)."""
+    if overclustering is not None:
+        for name, given in (("grid_k", grid_k is not None), ("grid_beta", grid_beta is not None), ("memory_sizes", memory_sizes is not None),
+                            ("leave_one_out", bool(leave_one_out)), ("bootstrap", bootstrap is not None),
+                            ("return_knn_details", bool(return_knn_details)), ("frame_size", frame_size is not None)):
+            if given:
+                raise ValueError(f"overclustering is not available with {name}")
+        from hbird_mi.kmeans import check_n_clusters
+        overclustering = [overclustering] if not isinstance(overclustering, (list, tuple)) else list(overclustering)
+        if not overclustering:
+            raise ValueError("overclustering is empty")
+        for k in overclustering:
+            check_n_clusters(k, who="overclustering")
     if bootstrap is None and bootstrap_seed is not None:
         raise ValueError("bootstrap_seed needs bootstrap")
     if leave_one_out and (return_knn_details or frame_size is not None):
@@ -1228,6 +1318,9 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     last_run_info.clear()
     last_run_info.update(bank_loaded=bool(evaluator.bank_loaded), bank_build_s=float(evaluator.bank_build_s),
                          bank_rows=int(evaluator.total_rows), train_batches_loaded=int(evaluator.batches_loaded))
+    if overclustering is not None:
+        return evaluator.evaluate_overclustering(val_loader, eval_spatial_resolution, overclustering, seed=overclustering_seed,
+                                                 max_iter=overclustering_iters, ignore_index=effective_ignore)
     if bootstrap is not None:
         ks, bs = n_neighbours if grid_k is None else grid_k, evaluator.beta if grid_beta is None else grid_beta
         sized = None
