@@ -135,6 +135,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "then carries miou_overclustering, keyed 'clusters=K'")
     p.add_argument("--overclustering-seed", type=int, default=0, metavar="S", help="seed of the k-means initialisation")
     p.add_argument("--overclustering-iters", type=_positive_int, default=20, metavar="N", help="iteration limit of k-means")
+    p.add_argument("--linear-probe", action="store_true",
+                   help="the linear-head protocol instead of the retrieval one (not in the reference's CLI): a softmax head fitted on the bank "
+                        "by L-BFGS, scored with the identity matching; the result JSON then carries miou_linear_probe and linear_probe_fit")
+    p.add_argument("--linear-probe-l2", type=float, default=1e-3, metavar="X", help="l2 weight of the fit (a definition, not tuned on real data)")
+    p.add_argument("--linear-probe-gtol", type=float, default=1e-5, metavar="X", help="the fit stops once the gradient's largest entry is this small")
+    p.add_argument("--linear-probe-iters", type=int, default=200, metavar="N", help="iteration limit of the fit")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -252,7 +258,9 @@ def main(argv: Optional[List[str]] = None) -> None:
                               **({"grid_k": args.grid_k, "grid_beta": args.grid_beta} if args.grid_k or args.grid_beta else {}),
                               **({"bootstrap": args.bootstrap, "bootstrap_seed": args.bootstrap_seed} if args.bootstrap else {}),
                               **({"overclustering": args.overclustering, "overclustering_seed": args.overclustering_seed,
-                                  "overclustering_iters": args.overclustering_iters} if args.overclustering else {}))
+                                  "overclustering_iters": args.overclustering_iters} if args.overclustering else {}),
+                              **({"linear_probe": True, "linear_probe_l2": args.linear_probe_l2, "linear_probe_gtol": args.linear_probe_gtol,
+                                  "linear_probe_iters": args.linear_probe_iters} if args.linear_probe else {}))
     from hbird_mi import hbird_eval as _he
     boot_fields: Dict[str, Any] = {}
     if args.bootstrap:
@@ -287,6 +295,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         summary["miou_grid_by_memory_size"] = grid_by_size
     if clusters is not None:
         summary["miou_overclustering"] = clusters
+    if args.linear_probe:      # (linear_probe_fit comes with last_run_info)
+        summary["miou_linear_probe"] = float(result)
     summary.update(boot_fields)
     print(json.dumps(summary))
     if args.out:

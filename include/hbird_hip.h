@@ -458,6 +458,7 @@ int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, i
 #include "hbird_hip_screen.h"
 #include "hbird_hip_exclude_screen.h"
 #include "hbird_hip_kmeans.h"
+#include "hbird_hip_linprobe.h"
 
 #ifdef __cplusplus
 }

@@ -193,6 +193,16 @@ SIGNATURES_KMEANS = {
                               POINTER(c_int)]),
 }
 
+# ... and include/hbird_hip_linprobe.h (the linear probe, csrc/hbird_linprobe.hip: a softmax segmentation head's logits, loss and gradient over
+# the resident bank), which hbird_hip.h includes
+LINPROBE_MAX_C = 256             # HB_LINPROBE_MAX_C
+LINPROBE_MAX_SEGS = 512          # HB_LINPROBE_MAX_SEGS
+SIGNATURES_LINPROBE = {
+    "hb_linprobe_partition": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int)]),
+    "hb_linprobe_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "hb_linprobe_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_double, POINTER(c_double), c_void_p, POINTER(c_int64), c_void_p]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -214,7 +224,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

@@ -1048,6 +1048,53 @@ class HbirdEvaluation:
         logger.info("Overclustering evaluation complete.")
         return out
 
+    # -- linear probe: a softmax head fitted on the bank's rows and label rows (hbird_mi/linear_probe.py) ------------------------------
+    def _linear_probe_checks(self, who: str) -> None:
+        if self.world > 1 or self.sharded:
+            raise ValueError(f"{who}: not available under torch.distributed (row shards or replicas): the linear probe runs on one index")
+        if not isinstance(self.index, HipFlatIndex):
+            raise ValueError(f"{who}: the linear probe runs on one HipFlatIndex -- a HipMultiIndex (row shards or replicas) is not supported yet")
+
+    def linear_probe(self, l2: float = 1e-3, gtol: float = 1e-5, max_iter: int = 200):
+        """`hbird_mi.linear_probe.linear_probe_fit` on this evaluator's bank (normalised rows, patch soft labels): a `LinearProbe`."""
+        from hbird_mi.linear_probe import linear_probe_fit
+        self._linear_probe_checks("linear_probe")
+        with torch.cuda.device(self.gpu_device):
+            return linear_probe_fit(self.index, l2=l2, gtol=gtol, max_iter=max_iter)
+
+    def evaluate_linear_probe(self, val_loader, eval_spatial_resolution: int, l2: float = 1e-3, gtol: float = 1e-5, max_iter: int = 200,
+                              ignore_index: int = 255, window=None, return_knn_details: bool = False) -> float:
+        """The linear-head protocol (the third figure this literature reports for a frozen encoder, beside retrieval and overclustering): ONE
+        fit of a softmax head on the bank, ONE validation pass.  Per batch: tokens -> `LinearProbe.logits` (normalised like the bank's rows)
+        -> [B, N, C] -> the unchanged fused upsample + argmax + confusion kernel (logits may be negative: class 0 starts the running maximum)
+        -> `PredsmIoU(C, C)`, scored with `compute(linear_probe=True)`, the identity matching.  -> mIoU; `last_linear_probe` keeps the
+        confusion matrix (int64 [C, C], CPU), the fit's state, n_iter, final loss, rows used and skipped, history, and the parameters Wb
+        (float32 [C, D + 1], CPU).  ValueError with sliding windows, with return_knn_details and under torch.distributed."""
+        who = "evaluate_linear_probe"
+        if window is not None:
+            raise ValueError(f"{who}: sliding windows (window=) are not supported")
+        if return_knn_details:
+            raise ValueError(f"{who}: return_knn_details is not supported (there are no neighbours)")
+        self._linear_probe_checks(who)
+        C = self.num_classes
+        probe = self.linear_probe(l2=l2, gtol=gtol, max_iter=max_iter)
+        logger.info("linear probe: %d iterations, %s, loss %.6f", probe.n_iter, probe.state, probe.history[-1]["loss"])
+        try:
+            metric = PredsmIoU(C, C, ignore_index=ignore_index, device=self.gpu_device, store_reordered_preds=False)
+            self.feature_extractor = self.feature_extractor.to(self.device)
+            S = eval_spatial_resolution
+            with torch.no_grad(), torch.cuda.device(self.gpu_device):
+                for bi, (x, y) in tqdm(self._prefetched(enumerate(val_loader), True), desc="Linear probe evaluation loop"):
+                    y = (y.to(self.gpu_device) * 255).long()
+                    metric.update_from_label_hat(y, probe.logits(self._tokens(x)), S)        # K6 + K7
+            miou = metric.compute(is_global_zero=True, sync_distributed=False, return_reordered=False, linear_probe=True)[0]
+            self.last_linear_probe = dict(confusion=metric._conf_mat.cpu(), state=probe.state, n_iter=probe.n_iter, loss=probe.history[-1]["loss"],
+                                          rows_used=probe.rows_used, rows_skipped=probe.rows_skipped, history=probe.history, Wb=probe.Wb.cpu())
+        finally:
+            probe.close()
+        logger.info("Linear probe evaluation complete.")
+        return miou
+
     # -- batch prefetch + stage timing of the evaluation loop ---------------------------------------------------------------------
     def _prefetched(self, batches, to_gpu: bool):
         """(bi, (x, y)) of `batches`, one batch ahead: while the caller works on batch i, batch i + 1 is pulled from the loader (its
@@ -1237,7 +1284,9 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
                      f_mem_p: Optional[str] = None, l_mem_p: Optional[str] = None, grid_k=None, grid_beta=None,
                      leave_one_out: bool = False, leave_one_out_images: Optional[int] = None,
                      leave_one_out_screen: bool = False, bootstrap: Optional[int] = None, bootstrap_seed: Optional[int] = None,
-                     overclustering=None, overclustering_seed: int = 0, overclustering_iters: int = 20, memory_sizes=None):
+                     overclustering=None, overclustering_seed: int = 0, overclustering_iters: int = 20,
+                     linear_probe: bool = False, linear_probe_l2: float = 1e-3, linear_probe_gtol: float = 1e-5, linear_probe_iters: int = 200,
+                     memory_sizes=None):
     """High-level entry point with the reference's signature (hbird_eval.py:640-660).
 
     Four trailing keywords are not in the reference: `frame_size=(H, W)` makes the datasets deliver H x W frames that
@@ -1265,7 +1314,18 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     `overclustering=[K, ...]` (`overclustering_seed=`, `overclustering_iters=`: the k-means initialisation's seed and its iteration limit): the
     overclustering protocol instead of the retrieval one -- k-means over the bank, clusters matched to classes
     (`HbirdEvaluation.evaluate_overclustering`); the call returns {K: mIoU}.  Not with a grid, `memory_sizes`, `leave_one_out` or `bootstrap`,
-    nor with sliding windows, return_knn_details or torch.distributed (ValueError)."""
+    nor with sliding windows, return_knn_details or torch.distributed (ValueError).
+    `linear_probe=True` (`linear_probe_l2=`, `linear_probe_gtol=`, `linear_probe_iters=`: the fit's l2 weight, gradient tolerance and iteration
+    limit -- definitions, not values tuned on real data): the linear-head protocol instead of the retrieval one -- a softmax head fitted on the
+    bank, scored with the identity matching (`HbirdEvaluation.evaluate_linear_probe`); the call returns its mIoU and `last_run_info` gains
+    `linear_probe_fit`.  Same exclusions as `overclustering`, and not together with it."""
+    if linear_probe:
+        for name, given in (("grid_k", grid_k is not None), ("grid_beta", grid_beta is not None), ("memory_sizes", memory_sizes is not None),
+                            ("leave_one_out", bool(leave_one_out)), ("bootstrap", bootstrap is not None),
+                            ("return_knn_details", bool(return_knn_details)), ("frame_size", frame_size is not None),
+                            ("overclustering", overclustering is not None)):
+            if given:
+                raise ValueError(f"linear_probe is not available with {name}")
     if overclustering is not None:
         for name, given in (("grid_k", grid_k is not None), ("grid_beta", grid_beta is not None), ("memory_sizes", memory_sizes is not None),
                             ("leave_one_out", bool(leave_one_out)), ("bootstrap", bootstrap is not None),
@@ -1318,6 +1378,13 @@ def hbird_evaluation(model, d_model: int, patch_size: int, dataset_name: str, da
     last_run_info.clear()
     last_run_info.update(bank_loaded=bool(evaluator.bank_loaded), bank_build_s=float(evaluator.bank_build_s),
                          bank_rows=int(evaluator.total_rows), train_batches_loaded=int(evaluator.batches_loaded))
+    if linear_probe:
+        miou = evaluator.evaluate_linear_probe(val_loader, eval_spatial_resolution, l2=linear_probe_l2, gtol=linear_probe_gtol,
+                                               max_iter=linear_probe_iters, ignore_index=effective_ignore)
+        fit = evaluator.last_linear_probe
+        last_run_info.update(linear_probe_fit=dict(state=fit["state"], iterations=int(fit["n_iter"]), loss=float(fit["loss"]),
+                                                   rows_used=int(fit["rows_used"]), rows_skipped=int(fit["rows_skipped"])))
+        return miou
     if overclustering is not None:
         return evaluator.evaluate_overclustering(val_loader, eval_spatial_resolution, overclustering, seed=overclustering_seed,
                                                  max_iter=overclustering_iters, ignore_index=effective_ignore)
