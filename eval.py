@@ -4,6 +4,7 @@
   python eval.py --dataset-name voc --data-dir /data/VOCSegmentation --d-model 384 --patch-size 16 \\
       --input-size 224 --batch-size 64 --device cuda --nn-method hip --checkpoint dino_vits16.pth --timm-model vit_small_patch16_224
   python eval.py --dataset-name synthetic --data-dir "" --d-model 3 --patch-size 8 --input-size 64 --device cuda   # self-check
+  python eval.py --task depth --dataset-name synthetic-depth --data-dir "" --d-model 3 --patch-size 8 --input-size 64   # depth self-check
 """
 from __future__ import annotations
 
@@ -141,6 +142,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--linear-probe-l2", type=float, default=1e-3, metavar="X", help="l2 weight of the fit (a definition, not tuned on real data)")
     p.add_argument("--linear-probe-gtol", type=float, default=1e-5, metavar="X", help="the fit stops once the gradient's largest entry is this small")
     p.add_argument("--linear-probe-iters", type=int, default=200, metavar="N", help="iteration limit of the fit")
+    p.add_argument("--task", choices=["segmentation", "depth"], default="segmentation",
+                   help="depth: monocular depth by retrieval (hbird_mi.depth; not in the reference's CLI) -- the bank stores each patch's local depth "
+                        "values, the result JSON carries rmse, abs_rel, sq_rel, rmse_log, silog, log10, d1, d2, d3 (means of per-image metrics), "
+                        "pooled, n_nopred and empty_images; --dataset-name synthetic-depth | depth-folder")
+    p.add_argument("--target-grid", type=_positive_int, default=1, metavar="R",
+                   help="--task depth: R x R depth cells per patch (R divides the patch size; the patch size itself is the full-resolution label patch)")
+    p.add_argument("--min-depth", type=_positive_float, default=1e-3, metavar="A", help="--task depth: smallest valid depth, metres")
+    p.add_argument("--max-depth", type=_positive_float, default=10.0, metavar="B", help="--task depth: largest valid depth, metres")
+    p.add_argument("--depth-scale", type=_positive_float, default=1000.0, metavar="X", help="--task depth: units per metre of 16-bit PNG depth files")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -202,7 +212,7 @@ class _PatchPool(torch.nn.Module):
 
 
 def build_model(args) -> torch.nn.Module:
-    if args.dataset_name.split("*")[0] == "synthetic" and not (args.timm_model or args.dinov2):
+    if args.dataset_name.split("*")[0] in ("synthetic", "synthetic-depth") and not (args.timm_model or args.dinov2):
         return _PatchPool(args.patch_size)
     if args.dinov2:
         model = torch.hub.load("facebookresearch/dinov2", f"dinov2_{args.dinov2}")          # eval.py:213 (needs a hub cache)
@@ -232,11 +242,44 @@ def default_ftr_extr_fn(model, imgs):
     return out, None
 
 
+DEPTH_EXCLUDES = ("frame_size", "window_stride", "memory_sizes", "grid_k", "grid_beta", "leave_one_out", "bootstrap", "overclustering",
+                  "linear_probe", "f_mem_p", "l_mem_p")
+
+
+def main_depth(parser, args) -> None:
+    """--task depth: hbird_mi.depth.hbird_depth_evaluation and its JSON."""
+    for name in DEPTH_EXCLUDES:
+        if getattr(args, name):
+            parser.error(f"--{name.replace('_', '-')} is not available with --task depth")
+    logging.basicConfig(level=getattr(logging, args.log_level), force=True)
+    set_seed(args.seed)
+    from hbird_mi import depth as hdepth
+    model = build_model(args)
+    t0 = time.time()
+    res = hdepth.hbird_depth_evaluation(model, d_model=args.d_model, patch_size=args.patch_size, dataset_name=args.dataset_name,
+                                        data_dir=args.data_dir, batch_size=args.batch_size, input_size=args.input_size,
+                                        augmentation_epoch=args.augmentation_epoch, device=args.device, n_neighbours=args.n_neighbours,
+                                        nn_method=args.nn_method, nn_params=parse_nn_params(args.nn_param), ftr_extr_fn=default_ftr_extr_fn,
+                                        memory_size=args.memory_size, num_workers=args.num_workers, target_grid=args.target_grid,
+                                        min_depth=args.min_depth, max_depth=args.max_depth, depth_scale=args.depth_scale,
+                                        train_fs_path=args.train_fs_path, val_fs_path=args.val_fs_path)
+    summary = {"task": "depth", **{k: float(v) for k, v in res.items()}, "pooled": res.pooled, "n_nopred": res.n_nopred,
+               "n_pixels": res.n_pixels, "n_images": len(res.per_image), "empty_images": res.empty_images, "target_grid": args.target_grid,
+               "min_depth": args.min_depth, "max_depth": args.max_depth, "seconds": round(time.time() - t0, 3), "nn_method": args.nn_method,
+               "dataset": args.dataset_name, "n_neighbours": args.n_neighbours, **hdepth.last_run_info}
+    print(json.dumps(summary))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f)
+
+
 def main(argv: Optional[List[str]] = None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.bootstrap_seed is not None and not args.bootstrap:
         parser.error("--bootstrap-seed needs --bootstrap")
+    if args.task == "depth":
+        return main_depth(parser, args)
     logging.basicConfig(level=getattr(logging, args.log_level), force=True)
     nn_params = parse_nn_params(args.nn_param)
     set_seed(args.seed)

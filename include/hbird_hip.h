@@ -459,6 +459,7 @@ int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, i
 #include "hbird_hip_exclude_screen.h"
 #include "hbird_hip_kmeans.h"
 #include "hbird_hip_linprobe.h"
+#include "hbird_hip_depth.h"
 
 #ifdef __cplusplus
 }

@@ -203,6 +203,17 @@ SIGNATURES_LINPROBE = {
     "hb_linprobe_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_double, POINTER(c_double), c_void_p, POINTER(c_int64), c_void_p]),
 }
 
+# ... and include/hbird_hip_depth.h (depth estimation by retrieval, csrc/hbird_depth.hip: depth maps to patch label rows, aggregated rows to a
+# depth map and per-image error sums), which hbird_hip.h includes
+DEPTH_NSUMS = 11                 # HB_DEPTH_NSUMS
+DEPTH_SUMS = ("n", "n_nopred", "sq", "abs_rel", "sq_rel", "log_sq", "log", "log10", "d1", "d2", "d3")      # HB_DEPTH_SUM_*: the slots in order
+DEPTH_MAX_PS = 64                # HB_DEPTH_MAX_PS
+DEPTH_MAX_GRID = 4096            # HB_DEPTH_MAX_GRID
+SIGNATURES_DEPTH = {
+    "hb_patch_depth_targets": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "hb_depth_upsample_metrics": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -224,7 +235,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

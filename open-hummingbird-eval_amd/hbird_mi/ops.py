@@ -237,3 +237,40 @@ def bootstrap_miou(stats: torch.Tensor, n_cfg: int, num_classes: int, seed: int,
     _lib.check(_lib.lib().hb_bootstrap_miou(_p(stats), stats.shape[0], n_cfg, G, int(seed) & 0xFFFFFFFFFFFFFFFF, int(R), _p(point), _p(samples),
                                             int(_chunk_replicates), _stream(stats)))
     return point, samples
+
+
+# ---- depth estimation by retrieval (include/hbird_hip_depth.h, csrc/hbird_depth.hip) -----------------------------------------------------
+def patch_depth_targets(y: torch.Tensor, patch_size: int, target_grid: int = 1, min_depth: float = 1e-3, max_depth: float = 10.0):
+    """y [B,H,W] fp32 metres -> (rows [B, H/ps, W/ps, 2 r^2] fp32: per-cell sums of valid depth and valid shares, both over the cell's area;
+    nonempty [B, H/ps, W/ps] int32: the patch holds a valid pixel)."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 3 or y.dtype != torch.float32:
+        raise ValueError(f"patch_depth_targets: y must be a float32 [B,H,W] tensor, got {getattr(y, 'dtype', type(y))} {tuple(getattr(y, 'shape', ()))}")
+    B, H, W = y.shape
+    ps, r = int(patch_size), int(target_grid)
+    if ps < 1 or r < 1 or H % ps or W % ps or ps % r:
+        raise ValueError(f"patch_depth_targets: patch_size={patch_size} must divide H={H} and W={W}, and target_grid={target_grid} the patch size")
+    _need_cuda(y)
+    y = y.contiguous()
+    rows = torch.empty((B, H // ps, W // ps, 2 * r * r), dtype=torch.float32, device=y.device)
+    nonempty = torch.empty((B, H // ps, W // ps), dtype=torch.int32, device=y.device)
+    _lib.check(_lib.lib().hb_patch_depth_targets(_p(y), B, H, W, ps, r, float(min_depth), float(max_depth), _p(rows), _p(nonempty), _stream(y)))
+    return rows, nonempty
+
+
+def depth_upsample_metrics(agg: torch.Tensor, S: int, target_grid: int, gt: torch.Tensor, min_depth: float = 1e-3, max_depth: float = 10.0,
+                           want_map: bool = False):
+    """agg [B, S*S, 2 r^2] (the aggregated rows) against gt [B,h,w] fp32 -> (sums [B, DEPTH_NSUMS] float64 in the order of _lib.DEPTH_SUMS,
+    pred [B,h,w] fp32 with NaN where there is no prediction -- or None unless `want_map`).  Synchronises the current stream."""
+    _need_cuda(agg, gt)
+    r = int(target_grid)
+    if agg.dim() != 3 or agg.dtype != torch.float32 or agg.shape[1] != S * S or agg.shape[2] != 2 * r * r:
+        raise ValueError(f"depth_upsample_metrics: agg must be float32 [B, {S * S}, {2 * r * r}], got {agg.dtype} {tuple(agg.shape)}")
+    if gt.dim() != 3 or gt.dtype != torch.float32 or gt.shape[0] != agg.shape[0]:
+        raise ValueError(f"depth_upsample_metrics: gt must be float32 [B,h,w] with B = {agg.shape[0]}, got {gt.dtype} {tuple(gt.shape)}")
+    agg, gt = agg.contiguous(), gt.contiguous()
+    B, h, w = gt.shape
+    sums = torch.empty((B, _lib.DEPTH_NSUMS), dtype=torch.float64, device=agg.device)
+    pred = torch.empty((B, h, w), dtype=torch.float32, device=agg.device) if want_map else None
+    _lib.check(_lib.lib().hb_depth_upsample_metrics(_p(agg), B, int(S), r, h, w, _p(gt), float(min_depth), float(max_depth), _p(sums), _p(pred),
+                                                    _stream(agg)))
+    return sums, pred
