@@ -5,6 +5,8 @@
       --input-size 224 --batch-size 64 --device cuda --nn-method hip --checkpoint dino_vits16.pth --timm-model vit_small_patch16_224
   python eval.py --dataset-name synthetic --data-dir "" --d-model 3 --patch-size 8 --input-size 64 --device cuda   # self-check
   python eval.py --task depth --dataset-name synthetic-depth --data-dir "" --d-model 3 --patch-size 8 --input-size 64   # depth self-check
+  python eval.py --task depth-grid --grid-k 1 5 30 --grid-beta 0.02 0.1 --bootstrap 1000 --dataset-name synthetic-depth --data-dir "" \\
+      --d-model 3 --patch-size 8 --input-size 64                                                                      # ... over a (k, beta) grid
 """
 from __future__ import annotations
 
@@ -142,10 +144,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--linear-probe-l2", type=float, default=1e-3, metavar="X", help="l2 weight of the fit (a definition, not tuned on real data)")
     p.add_argument("--linear-probe-gtol", type=float, default=1e-5, metavar="X", help="the fit stops once the gradient's largest entry is this small")
     p.add_argument("--linear-probe-iters", type=int, default=200, metavar="N", help="iteration limit of the fit")
-    p.add_argument("--task", choices=["segmentation", "depth"], default="segmentation",
+    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid"], default="segmentation",
                    help="depth: monocular depth by retrieval (hbird_mi.depth; not in the reference's CLI) -- the bank stores each patch's local depth "
                         "values, the result JSON carries rmse, abs_rel, sq_rel, rmse_log, silog, log10, d1, d2, d3 (means of per-image metrics), "
-                        "pooled, n_nopred and empty_images; --dataset-name synthetic-depth | depth-folder")
+                        "pooled, n_nopred and empty_images; --dataset-name synthetic-depth | depth-folder.  depth-grid: the same task over "
+                        "--grid-k / --grid-beta / --memory-sizes from one pass, with --leave-one-out and --bootstrap (hbird_depth_grid_evaluation); "
+                        "the result JSON carries depth_grid, keyed 'k=30,beta=0.02' (with --memory-sizes 'memory=N,k=30,beta=0.02')")
+    p.add_argument("--bootstrap-metric", choices=["rmse", "abs_rel", "sq_rel", "rmse_log", "silog", "log10", "d1", "d2", "d3"], default="rmse",
+                   help="--task depth-grid with --bootstrap: the metric grid_best and grid_indistinguishable_from_best are decided on")
     p.add_argument("--target-grid", type=_positive_int, default=1, metavar="R",
                    help="--task depth: R x R depth cells per patch (R divides the patch size; the patch size itself is the full-resolution label patch)")
     p.add_argument("--min-depth", type=_positive_float, default=1e-3, metavar="A", help="--task depth: smallest valid depth, metres")
@@ -273,6 +279,62 @@ def main_depth(parser, args) -> None:
             json.dump(summary, f)
 
 
+DEPTH_GRID_EXCLUDES = ("frame_size", "window_stride", "overclustering", "linear_probe", "f_mem_p", "l_mem_p")
+
+
+def depth_grid_key(key) -> str:
+    """How a configuration of --task depth-grid -- (k, beta), with --memory-sizes (size, k, beta) -- is keyed in the result JSON."""
+    return grid_key(*key) if len(key) == 2 else f"memory={int(key[0])}," + grid_key(*key[1:])
+
+
+def main_depth_grid(parser, args) -> None:
+    """--task depth-grid: hbird_mi.depth.hbird_depth_grid_evaluation and its JSON."""
+    for name in DEPTH_GRID_EXCLUDES:
+        if getattr(args, name):
+            parser.error(f"--{name.replace('_', '-')} is not available with --task depth-grid")
+    if (args.leave_one_out_images is not None or args.leave_one_out_screen) and not args.leave_one_out:
+        parser.error("--leave-one-out-images and --leave-one-out-screen need --leave-one-out")
+    if args.memory_sizes and args.memory_size is None:
+        parser.error("--memory-sizes needs --memory-size")
+    logging.basicConfig(level=getattr(logging, args.log_level), force=True)
+    set_seed(args.seed)
+    from hbird_mi import depth as hdepth
+    model = build_model(args)
+    t0 = time.time()
+    res = hdepth.hbird_depth_grid_evaluation(model, d_model=args.d_model, patch_size=args.patch_size, dataset_name=args.dataset_name,
+                                             data_dir=args.data_dir, batch_size=args.batch_size, input_size=args.input_size,
+                                             augmentation_epoch=args.augmentation_epoch, device=args.device, n_neighbours=args.n_neighbours,
+                                             nn_method=args.nn_method, nn_params=parse_nn_params(args.nn_param), ftr_extr_fn=default_ftr_extr_fn,
+                                             memory_size=args.memory_size, num_workers=args.num_workers, target_grid=args.target_grid,
+                                             min_depth=args.min_depth, max_depth=args.max_depth, depth_scale=args.depth_scale,
+                                             train_fs_path=args.train_fs_path, val_fs_path=args.val_fs_path, grid_k=args.grid_k,
+                                             grid_beta=args.grid_beta, memory_sizes=args.memory_sizes, leave_one_out=args.leave_one_out,
+                                             leave_one_out_images=args.leave_one_out_images, leave_one_out_screen=args.leave_one_out_screen,
+                                             bootstrap=args.bootstrap, bootstrap_seed=args.bootstrap_seed)
+    boot = res if args.bootstrap else None
+    metrics = boot.metrics if boot is not None else res
+    head = headline_key(list(metrics), args.n_neighbours, args.memory_size)
+    summary = {"task": "depth-grid", **{k: float(v) for k, v in metrics[head].items()}, "headline": depth_grid_key(head),
+               "depth_grid": {depth_grid_key(key): {**{k: float(v) for k, v in m.items()}, "pooled": m.pooled, "n_nopred": m.n_nopred,
+                                                    "empty_images": m.empty_images} for key, m in metrics.items()},
+               "n_images": len(metrics[head].per_image), "target_grid": args.target_grid, "min_depth": args.min_depth, "max_depth": args.max_depth,
+               "seconds": round(time.time() - t0, 3), "nn_method": args.nn_method, "dataset": args.dataset_name, "n_neighbours": args.n_neighbours,
+               **hdepth.last_run_info}
+    if args.leave_one_out:
+        summary["leave_one_out"] = True
+    if boot is not None:
+        level, metric = args.bootstrap_level, args.bootstrap_metric
+        best, tied = boot.best(metric, level)
+        summary.update({f"{m}_ci": [float(v) for v in boot.interval(head, m, level)] for m in ("rmse", "abs_rel", "d1")})
+        summary.update(grid_best=depth_grid_key(best), grid_indistinguishable_from_best=[depth_grid_key(k) for k in tied],
+                       bootstrap={"replicates": int(boot.samples[metric].shape[0]), "seed": int(boot.seed), "level": float(level),
+                                  "metric": metric, "n_images": int(boot.n_images)})
+    print(json.dumps(summary))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f)
+
+
 def main(argv: Optional[List[str]] = None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -280,6 +342,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         parser.error("--bootstrap-seed needs --bootstrap")
     if args.task == "depth":
         return main_depth(parser, args)
+    if args.task == "depth-grid":
+        return main_depth_grid(parser, args)
     logging.basicConfig(level=getattr(logging, args.log_level), force=True)
     nn_params = parse_nn_params(args.nn_param)
     set_seed(args.seed)

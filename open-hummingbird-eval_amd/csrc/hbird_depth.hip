@@ -2,14 +2,13 @@
 // depth map + deterministic per-image error sums (depth_upsample_metrics, depth_row_sums).  Plain VALU, memory-bound; no MFMA.
 #include "../../include/hbird_hip.h"
 #include "hbird_internal.h"
+#include "hbird_depth_dev.h"
 #include <algorithm>
 #include <cmath>
 
 // Every value below is specified step by step (the cell sums, K6's interpolation, the float64 terms), so contraction into FMAs is switched
 // off for this file, as in hbird_post.hip.
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ bool depth_valid(float v, float lo, float hi) { return __builtin_isfinite(v) && v >= lo && v <= hi; }
 
 // One wave per patch, four patches per workgroup.  The wave's lanes walk the patch's pixels row by row (runs of ps neighbouring floats) into
 // LDS and vote on "any pixel valid"; then lane = cell adds its s x s pixels from LDS in row-major order -- the stated chain, whatever r is.
@@ -52,10 +51,6 @@ __global__ __launch_bounds__(256) void depth_targets_kernel(const float* __restr
     }
 }
 
-static const char* depth_bounds_error(float lo, float hi) {
-    return (std::isfinite(lo) && std::isfinite(hi) && lo > 0.0f && lo <= hi) ? nullptr : "the bounds must be finite with 0 < min_depth <= max_depth";
-}
-
 extern "C" int hb_patch_depth_targets(const float* y, int64_t B, int H, int W, int ps, int r, float min_depth, float max_depth, float* rows_out,
                                       int* nonempty_out, void* stream) {
     const std::string who = "hb_patch_depth_targets: ";
@@ -76,24 +71,7 @@ extern "C" int hb_patch_depth_targets(const float* y, int64_t B, int H, int W, i
 }
 
 // ---- prediction and sums ---------------------------------------------------------------------------------------------------------------
-// K6's source index and bands (hbird_post.hip), on the cell grid of side G = S r.
-__host__ __device__ __forceinline__ int depth_src0(float scale, int dst, int G) {
-    const float f = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
-    const int i = (int)floorf(f);
-    return i < G - 1 ? i : G - 1;
-}
-// first output index whose upper source index is >= j (the source index is monotone: bands are contiguous)
-__host__ __device__ __forceinline__ int depth_band_begin(float scale, int j, int G, int n) {
-    if (j <= 0) return 0;
-    if (j > G - 1) return n;
-    int g = (int)(((float)j + 0.5f) / scale - 0.5f);
-    g = g < 0 ? 0 : (g > n ? n : g);
-    while (g > 0 && depth_src0(scale, g - 1, G) >= j) --g;
-    while (g < n && depth_src0(scale, g, G) < j) ++g;
-    return g;
-}
-
-#define DEPTH_ROWS 16      // output rows of a band per workgroup
+// (K6's source index and bands on the cell grid, and DEPTH_ROWS: hbird_depth_dev.h)
 // One workgroup = (image, band j, chunk of <= DEPTH_ROWS rows of the band, one column chunk of the summation rule).  It stages the columns
 // it needs of the source cell rows j and j + 1 of both grids in LDS ([4][ncols]); one lane per output column forms top / bot of N and Dn once
 // and walks the chunk's rows.  A row's 11 float64 terms meet by the rule of the header: butterfly inside the wave, the waves in order; the
@@ -204,6 +182,14 @@ __global__ __launch_bounds__(256) void depth_row_sums_kernel(const double* __res
             }
     }
     if (threadIdx.x < HB_DEPTH_NSUMS) sums[b * HB_DEPTH_NSUMS + threadIdx.x] = acc;
+}
+
+// the row pass for another unit's partials (hbird_depth_grid.hip: one slab per configuration and image)
+int hb_launch_depth_row_sums(const double* part, int64_t slabs, int h, int nb, double* sums, hipStream_t s) {
+    if (slabs < 1 || slabs > 0x7FFFFFFFLL) return hb_fail("hb_launch_depth_row_sums: bad slab count");
+    depth_row_sums_kernel<<<dim3((unsigned)slabs), dim3(256), 0, s>>>(part, h, nb, sums);
+    HB_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int hb_depth_upsample_metrics(const float* agg, int64_t B, int S, int r, int h, int w, const float* gt, float min_depth, float max_depth,

@@ -214,6 +214,16 @@ SIGNATURES_DEPTH = {
     "hb_depth_upsample_metrics": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
+# ... and include/hbird_hip_depth_grid.h (depth grids, csrc/hbird_depth_grid.hip: the depth metrics of a whole (k, beta) grid out of one call, the
+# resampling reduction of the paired bootstrap over float64 per-image sums); a header of its own, not included by hbird_hip.h
+DEPTH_GRID_MAX_CONFIGS = 16      # HB_DEPTH_GRID_MAX_CONFIGS
+SIGNATURES_DEPTH_GRID = {
+    "hb_depth_upsample_metrics_grid": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p,
+                                               c_void_p]),
+    "hb_bootstrap_weighted_sums": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+}
+
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -235,7 +245,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

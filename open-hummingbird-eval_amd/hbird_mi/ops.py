@@ -274,3 +274,39 @@ def depth_upsample_metrics(agg: torch.Tensor, S: int, target_grid: int, gt: torc
     _lib.check(_lib.lib().hb_depth_upsample_metrics(_p(agg), B, int(S), r, h, w, _p(gt), float(min_depth), float(max_depth), _p(sums), _p(pred),
                                                     _stream(agg)))
     return sums, pred
+
+
+# ---- depth grids (include/hbird_hip_depth_grid.h, csrc/hbird_depth_grid.hip) ------------------------------------------------------------------
+def depth_upsample_metrics_grid(agg: torch.Tensor, S: int, target_grid: int, gt: torch.Tensor, min_depth: float = 1e-3, max_depth: float = 10.0,
+                                want_map: bool = False):
+    """agg [n_cfg, B, S*S, 2 r^2] (what `search_aggregate_grid` returns on a depth bank, viewed per image) against gt [B,h,w] fp32 ->
+    (sums [n_cfg, B, DEPTH_NSUMS] float64, pred [n_cfg, B, h, w] fp32 -- or None unless `want_map`): slab c has the bits of
+    `depth_upsample_metrics(agg[c], ...)`.  More than DEPTH_GRID_MAX_CONFIGS configurations go through in chunks of that many.
+    Synchronises the current stream."""
+    _need_cuda(agg, gt)
+    r = int(target_grid)
+    if agg.dim() != 4 or agg.dtype != torch.float32 or agg.shape[0] < 1 or agg.shape[2] != S * S or agg.shape[3] != 2 * r * r:
+        raise ValueError(f"depth_upsample_metrics_grid: agg must be float32 [n_cfg >= 1, B, {S * S}, {2 * r * r}], got {agg.dtype} {tuple(agg.shape)}")
+    if gt.dim() != 3 or gt.dtype != torch.float32 or gt.shape[0] != agg.shape[1]:
+        raise ValueError(f"depth_upsample_metrics_grid: gt must be float32 [B,h,w] with B = {agg.shape[1]}, got {gt.dtype} {tuple(gt.shape)}")
+    agg, gt = agg.contiguous(), gt.contiguous()
+    n_cfg, (B, h, w) = agg.shape[0], gt.shape
+    sums = torch.empty((n_cfg, B, _lib.DEPTH_NSUMS), dtype=torch.float64, device=agg.device)
+    pred = torch.empty((n_cfg, B, h, w), dtype=torch.float32, device=agg.device) if want_map else None
+    for c0 in range(0, n_cfg, _lib.DEPTH_GRID_MAX_CONFIGS):
+        c1 = min(n_cfg, c0 + _lib.DEPTH_GRID_MAX_CONFIGS)
+        _lib.check(_lib.lib().hb_depth_upsample_metrics_grid(_p(agg[c0:c1]), c1 - c0, B, int(S), r, h, w, _p(gt), float(min_depth), float(max_depth),
+                                                             _p(sums[c0:c1]), _p(pred[c0:c1]) if want_map else None, _stream(agg)))
+    return sums, pred
+
+
+def bootstrap_weighted_sums(table: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
+    """table [n_img, cols] float64, W [R, n_img] int32 (rows of `bootstrap_multiplicities`) -> out [R, cols] float64 with
+    out[r][col] = the chain acc = 0.0; for i ascending: acc = acc + (double)W[r][i] * table[i][col] -- the same bits however R is cut."""
+    _need_cuda(table, W)
+    if table.dtype != torch.float64 or W.dtype != torch.int32 or table.dim() != 2 or W.dim() != 2 or W.shape[1] != table.shape[0]:
+        raise ValueError("bootstrap_weighted_sums: table [n_img, cols] must be float64 and W [R, n_img] int32 with matching n_img")
+    table, W = table.contiguous(), W.contiguous()
+    out = torch.empty((W.shape[0], table.shape[1]), dtype=torch.float64, device=table.device)
+    _lib.check(_lib.lib().hb_bootstrap_weighted_sums(_p(table), table.shape[0], table.shape[1], _p(W), W.shape[0], _p(out), _stream(table)))
+    return out
