@@ -92,6 +92,24 @@ def bootstrap_as_plain(mb, gridded: bool, sized: bool):
     return dict(mb.miou) if gridded else next(iter(mb.miou.values()))
 
 
+def _non_negative_int(v: str) -> int:
+    n = int(v)
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"{v!r} must be >= 0")
+    return n
+
+
+def _radius(v: str) -> int:
+    n = int(v)
+    if n < -1:
+        raise argparse.ArgumentTypeError(f"{v!r} must be a radius >= 0, or -1 for an unrestricted window")
+    return n
+
+
+class _DefaultInt(int):
+    """An integer default that can be told from the same value typed on the command line (--n-neighbours: 30, and 5 with --task video)."""
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Hummingbird retrieval evaluation on MI355X (hbird_mi.hbird_evaluation).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -108,7 +126,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num-workers", type=int, default=8)
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--amp", action="store_true", help="accepted for compatibility (unused, as in the reference)")
-    p.add_argument("--n-neighbours", type=_positive_int, default=30)
+    p.add_argument("--n-neighbours", type=_positive_int, default=_DefaultInt(30), help="(--task video: 5 unless given)")
     p.add_argument("--nn-method", choices=["hip", "faiss", "scann"], default="hip")
     p.add_argument("--nn-param", action="append", default=[], metavar="KEY=VALUE")
     p.add_argument("--memory-size", type=int, default=None)
@@ -144,8 +162,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--linear-probe-l2", type=float, default=1e-3, metavar="X", help="l2 weight of the fit (a definition, not tuned on real data)")
     p.add_argument("--linear-probe-gtol", type=float, default=1e-5, metavar="X", help="the fit stops once the gradient's largest entry is this small")
     p.add_argument("--linear-probe-iters", type=int, default=200, metavar="N", help="iteration limit of the fit")
-    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid"], default="segmentation",
-                   help="depth: monocular depth by retrieval (hbird_mi.depth; not in the reference's CLI) -- the bank stores each patch's local depth "
+    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid", "video"], default="segmentation",
+                   help="video: semi-supervised video object segmentation by label propagation (hbird_mi.video; not in the reference) -- "
+                        "--dataset-name synthetic-video | video-folder (the DAVIS layout under --data-dir); the result JSON carries J_mean, J_recall, "
+                        "F_mean, F_recall, J&F and per_sequence.  depth: monocular depth by retrieval (hbird_mi.depth; not in the reference's CLI) -- the bank stores each patch's local depth "
                         "values, the result JSON carries rmse, abs_rel, sq_rel, rmse_log, silog, log10, d1, d2, d3 (means of per-image metrics), "
                         "pooled, n_nopred and empty_images; --dataset-name synthetic-depth | depth-folder.  depth-grid: the same task over "
                         "--grid-k / --grid-beta / --memory-sizes from one pass, with --leave-one-out and --bootstrap (hbird_depth_grid_evaluation); "
@@ -157,6 +177,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-depth", type=_positive_float, default=1e-3, metavar="A", help="--task depth: smallest valid depth, metres")
     p.add_argument("--max-depth", type=_positive_float, default=10.0, metavar="B", help="--task depth: largest valid depth, metres")
     p.add_argument("--depth-scale", type=_positive_float, default=1000.0, metavar="X", help="--task depth: units per metre of 16-bit PNG depth files")
+    p.add_argument("--video-last-frames", type=_non_negative_int, default=7, metavar="N", help="--task video: predicted frames kept as context")
+    p.add_argument("--video-radius", type=_radius, default=12, metavar="R", help="--task video: window radius in cells around the query (-1: unrestricted)")
+    p.add_argument("--video-first-frame-radius", type=_radius, default=None, metavar="R",
+                   help="--task video: window radius on the first frame (default: --video-radius; -1: unrestricted)")
+    p.add_argument("--video-temperature", type=_positive_float, default=0.1, metavar="T", help="--task video: softmax temperature of the propagation")
+    p.add_argument("--no-channel-norm", action="store_true", help="--task video: argmax without the per-channel min-max normalisation of the label maps")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
     p.add_argument("--val-fs", dest="val_fs_path", type=str, default=None)
@@ -218,7 +244,7 @@ class _PatchPool(torch.nn.Module):
 
 
 def build_model(args) -> torch.nn.Module:
-    if args.dataset_name.split("*")[0] in ("synthetic", "synthetic-depth") and not (args.timm_model or args.dinov2):
+    if args.dataset_name.split("*")[0] in ("synthetic", "synthetic-depth", "synthetic-video") and not (args.timm_model or args.dinov2):
         return _PatchPool(args.patch_size)
     if args.dinov2:
         model = torch.hub.load("facebookresearch/dinov2", f"dinov2_{args.dinov2}")          # eval.py:213 (needs a hub cache)
@@ -335,11 +361,51 @@ def main_depth_grid(parser, args) -> None:
             json.dump(summary, f)
 
 
+VIDEO_EXCLUDES = DEPTH_EXCLUDES + ("memory_size", "leave_one_out_images", "leave_one_out_screen", "train_fs_path")
+VIDEO_ONLY = {"video_last_frames": 7, "video_radius": 12, "video_first_frame_radius": None, "video_temperature": 0.1, "no_channel_norm": False}
+
+
+def main_video(parser, args) -> None:
+    """--task video: hbird_mi.video.hbird_video_evaluation and its JSON."""
+    for name in VIDEO_EXCLUDES:
+        if getattr(args, name):
+            parser.error(f"--{name.replace('_', '-').replace('-path', '')} is not available with --task video")
+    if args.nn_method != "hip" or args.nn_param:
+        parser.error("--nn-method and --nn-param are not available with --task video (the propagation has one kernel)")
+    if args.augmentation_epoch != 1 or args.target_grid != 1:
+        parser.error("--augmentation-epoch and --target-grid are not available with --task video")
+    k = 5 if isinstance(args.n_neighbours, _DefaultInt) else int(args.n_neighbours)
+    logging.basicConfig(level=getattr(logging, args.log_level), force=True)
+    set_seed(args.seed)
+    from hbird_mi import video as hvideo
+    model = build_model(args)
+    t0 = time.time()
+    res = hvideo.hbird_video_evaluation(model, d_model=args.d_model, patch_size=args.patch_size, dataset_name=args.dataset_name,
+                                        data_dir=args.data_dir, input_size=args.input_size, frame_batch=args.batch_size, device=args.device,
+                                        n_neighbours=k, temperature=args.video_temperature, n_last_frames=args.video_last_frames,
+                                        radius=args.video_radius, first_frame_radius=args.video_first_frame_radius,
+                                        channel_norm=not args.no_channel_norm, ftr_extr_fn=default_ftr_extr_fn, val_fs_path=args.val_fs_path)
+    summary = {"task": "video", **{key: float(v) for key, v in res.items()}, "per_sequence": res.per_sequence,
+               "skipped": [list(s) for s in res.skipped], "n_objects": len(res.per_object), "n_neighbours": k,
+               "temperature": args.video_temperature, "last_frames": args.video_last_frames, "radius": args.video_radius,
+               "first_frame_radius": args.video_radius if args.video_first_frame_radius is None else args.video_first_frame_radius,
+               "channel_norm": not args.no_channel_norm, "seconds": round(time.time() - t0, 3), "dataset": args.dataset_name}
+    print(json.dumps(summary))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f)
+
+
 def main(argv: Optional[List[str]] = None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.bootstrap_seed is not None and not args.bootstrap:
         parser.error("--bootstrap-seed needs --bootstrap")
+    if args.task == "video":
+        return main_video(parser, args)
+    for name, default in VIDEO_ONLY.items():
+        if getattr(args, name) != default:
+            parser.error(f"--{name.replace('_', '-')} needs --task video")
     if args.task == "depth":
         return main_depth(parser, args)
     if args.task == "depth-grid":

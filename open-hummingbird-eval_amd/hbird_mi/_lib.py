@@ -223,6 +223,21 @@ SIGNATURES_DEPTH_GRID = {
     "hb_bootstrap_weighted_sums": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
+# ... and include/hbird_hip_propagate.h (video label propagation, csrc/hbird_propagate.hip and csrc/hbird_maskmetrics.hip: windowed retrieval over a
+# pool of context frames, the label map of a rectangular frame, the counts behind J and F); a header of its own, not included by hbird_hip.h
+PROPAGATE_MAX_K = 32             # HB_PROPAGATE_MAX_K
+PROPAGATE_MAX_CTX = 32           # HB_PROPAGATE_MAX_CTX
+PROPAGATE_MAX_C = 64             # HB_PROPAGATE_MAX_C
+PROPAGATE_MAX_D = 1024           # HB_PROPAGATE_MAX_D
+JF_MAX_BOUND = 32                # HB_JF_MAX_BOUND
+JF_COUNTS = ("inter", "union", "nfg", "ngt", "fg_match", "gt_match")      # HB_JF_*: the slots in order
+SIGNATURES_PROPAGATE = {
+    "hb_propagate_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hb_mask_upsample_argmax": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "hb_mask_jf_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+}
+
 
 
 class HbirdHipError(RuntimeError):
@@ -245,7 +260,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()) + list(SIGNATURES_PROPAGATE.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

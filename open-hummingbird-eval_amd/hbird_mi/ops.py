@@ -310,3 +310,71 @@ def bootstrap_weighted_sums(table: torch.Tensor, W: torch.Tensor) -> torch.Tenso
     out = torch.empty((W.shape[0], table.shape[1]), dtype=torch.float64, device=table.device)
     _lib.check(_lib.lib().hb_bootstrap_weighted_sums(_p(table), table.shape[0], table.shape[1], _p(W), W.shape[0], _p(out), _stream(table)))
     return out
+
+
+# ---- video label propagation (include/hbird_hip_propagate.h, csrc/hbird_propagate.hip, csrc/hbird_maskmetrics.hip) ----------------------------
+def propagate_labels(q: torch.Tensor, feat_pool: torch.Tensor, label_pool: torch.Tensor, slots, radii, grid, k: int = 5, temperature: float = 0.1,
+                     want_neighbours: bool = False):
+    """q [N, d] (the target frame's normalised tokens, N = gh * gw row-major) against the context frames `slots` of feat_pool [P, N, d] /
+    label_pool [P, N, c], context position f restricted to the square window of radius radii[f] around the query's cell (< 0: unrestricted)
+    -> labels [N, c] fp32: the softmax(score / temperature)-weighted sum of the k best candidates' label rows.  With `want_neighbours` also
+    (idx [N, k] int64 with id = f * N + cell and -1 past the candidates, score [N, k] fp32 with -inf there)."""
+    for name, t in (("q", q), ("feat_pool", feat_pool), ("label_pool", label_pool)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"propagate_labels: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    gh, gw = (int(g) for g in grid)
+    N = gh * gw
+    if q.dim() != 2 or q.shape[0] != N:
+        raise ValueError(f"propagate_labels: q must be [gh * gw, d] = [{N}, d], got {tuple(q.shape)}")
+    d = q.shape[1]
+    if feat_pool.dim() != 3 or tuple(feat_pool.shape[1:]) != (N, d):
+        raise ValueError(f"propagate_labels: feat_pool must be [slots, {N}, {d}], got {tuple(feat_pool.shape)}")
+    if label_pool.dim() != 3 or tuple(label_pool.shape[:2]) != (feat_pool.shape[0], N):
+        raise ValueError(f"propagate_labels: label_pool must be [{feat_pool.shape[0]}, {N}, c], got {tuple(label_pool.shape)}")
+    slots, radii = [int(s) for s in slots], [int(r) for r in radii]
+    if len(slots) != len(radii) or not slots:
+        raise ValueError(f"propagate_labels: slots and radii must be non-empty and of one length, got {len(slots)} and {len(radii)}")
+    if q.device != feat_pool.device or q.device != label_pool.device:
+        raise ValueError("propagate_labels: q, feat_pool and label_pool must be on one device")
+    _need_cuda(q, feat_pool, label_pool)
+    q, feat_pool, label_pool = q.contiguous(), feat_pool.contiguous(), label_pool.contiguous()
+    c, n_ctx = label_pool.shape[2], len(slots)
+    out = torch.empty((N, c), dtype=torch.float32, device=q.device)
+    idx = torch.empty((N, int(k)), dtype=torch.int64, device=q.device) if want_neighbours else None
+    score = torch.empty((N, int(k)), dtype=torch.float32, device=q.device) if want_neighbours else None
+    IntArr = ctypes.c_int * n_ctx
+    _lib.check(_lib.lib().hb_propagate_labels(_p(q), _p(feat_pool), _p(label_pool), feat_pool.shape[0], IntArr(*slots), IntArr(*radii), n_ctx, gh, gw,
+                                              d, c, int(k), float(temperature), _p(out), _p(idx), _p(score), _stream(q)))
+    return (out, idx, score) if want_neighbours else out
+
+
+def mask_upsample_argmax(labels: torch.Tensor, grid, h: int, w: int, channel_norm: bool = True) -> torch.Tensor:
+    """labels [B, gh * gw, c] fp32 -> the label map [B, h, w] int64: bilinear upsampling (align_corners=False, K6's four taps), with
+    `channel_norm` every (image, channel) rescaled to [0, 1] by its own extrema over the frame (DINO's norm_mask), argmax with the first
+    maximum winning.  The channel-norm form synchronises the current stream."""
+    gh, gw = (int(g) for g in grid)
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.float32 or labels.dim() != 3 or labels.shape[1] != gh * gw:
+        raise ValueError(f"mask_upsample_argmax: labels must be float32 [B, {gh * gw}, c], got {getattr(labels, 'dtype', type(labels))} "
+                         f"{tuple(getattr(labels, 'shape', ()))}")
+    _need_cuda(labels)
+    labels = labels.contiguous()
+    B, _, c = labels.shape
+    out = torch.empty((B, int(h), int(w)), dtype=torch.int64, device=labels.device)
+    _lib.check(_lib.lib().hb_mask_upsample_argmax(_p(labels), B, gh, gw, c, int(h), int(w), int(bool(channel_norm)), _p(out), _stream(labels)))
+    return out
+
+
+def mask_jf_counts(pred: torch.Tensor, gt: torch.Tensor, n_objects: int, bound_px: int) -> torch.Tensor:
+    """pred, gt [B, h, w] int64 -> counts [B, n_objects, 6] int64 in the order of _lib.JF_COUNTS, for the objects 1 .. n_objects: region
+    intersection and union, the sizes of both boundary maps, and each map's pixels within bound_px (a disk) of the other."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 3:
+            raise ValueError(f"mask_jf_counts: {name} must be an int64 [B,h,w] tensor, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if tuple(pred.shape) != tuple(gt.shape) or pred.device != gt.device:
+        raise ValueError(f"mask_jf_counts: pred and gt must have one shape and device, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    _need_cuda(pred, gt)
+    pred, gt = pred.contiguous(), gt.contiguous()
+    B, h, w = pred.shape
+    counts = torch.empty((B, int(n_objects), len(_lib.JF_COUNTS)), dtype=torch.int64, device=pred.device)
+    _lib.check(_lib.lib().hb_mask_jf_counts(_p(pred), _p(gt), B, h, w, int(n_objects), int(bound_px), _p(counts), _stream(pred)))
+    return counts
