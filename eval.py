@@ -7,6 +7,7 @@
   python eval.py --task depth --dataset-name synthetic-depth --data-dir "" --d-model 3 --patch-size 8 --input-size 64   # depth self-check
   python eval.py --task depth-grid --grid-k 1 5 30 --grid-beta 0.02 0.1 --bootstrap 1000 --dataset-name synthetic-depth --data-dir "" \\
       --d-model 3 --patch-size 8 --input-size 64                                                                      # ... over a (k, beta) grid
+  python eval.py --task knn-classify --dataset-name synthetic-classify --data-dir "" --d-model 3 --patch-size 8 --input-size 32   # image-level k-NN
 """
 from __future__ import annotations
 
@@ -162,8 +163,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--linear-probe-l2", type=float, default=1e-3, metavar="X", help="l2 weight of the fit (a definition, not tuned on real data)")
     p.add_argument("--linear-probe-gtol", type=float, default=1e-5, metavar="X", help="the fit stops once the gradient's largest entry is this small")
     p.add_argument("--linear-probe-iters", type=int, default=200, metavar="N", help="iteration limit of the fit")
-    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid", "video"], default="segmentation",
-                   help="video: semi-supervised video object segmentation by label propagation (hbird_mi.video; not in the reference) -- "
+    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid", "video", "knn-classify"], default="segmentation",
+                   help="knn-classify: the weighted k-NN classifier on image-level features (hbird_mi.classify; not in the reference) -- "
+                        "--dataset-name synthetic-classify | class-folder (train/<class>/*, val/<class>/* under --data-dir), --grid-k (default 10 20 "
+                        "100 200) x --grid-temperature (default 0.07) from one search per batch; the result JSON carries top1, top5 and "
+                        "mean_per_class keyed 'k=20,T=0.07', best, n and skipped.  video: semi-supervised video object segmentation by label propagation (hbird_mi.video; not in the reference) -- "
                         "--dataset-name synthetic-video | video-folder (the DAVIS layout under --data-dir); the result JSON carries J_mean, J_recall, "
                         "F_mean, F_recall, J&F and per_sequence.  depth: monocular depth by retrieval (hbird_mi.depth; not in the reference's CLI) -- the bank stores each patch's local depth "
                         "values, the result JSON carries rmse, abs_rel, sq_rel, rmse_log, silog, log10, d1, d2, d3 (means of per-image metrics), "
@@ -182,6 +186,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--video-first-frame-radius", type=_radius, default=None, metavar="R",
                    help="--task video: window radius on the first frame (default: --video-radius; -1: unrestricted)")
     p.add_argument("--video-temperature", type=_positive_float, default=0.1, metavar="T", help="--task video: softmax temperature of the propagation")
+    p.add_argument("--grid-temperature", type=_positive_float, nargs="+", default=None, metavar="T",
+                   help="--task knn-classify: the temperatures of the vote's weights exp(similarity / T) (default 0.07)")
+    p.add_argument("--top-n", type=_positive_int, default=None, metavar="N",
+                   help="--task knn-classify: predictions ranked per image, at most 8 (default 5: the JSON's top5 is the label among the first N)")
     p.add_argument("--no-channel-norm", action="store_true", help="--task video: argmax without the per-channel min-max normalisation of the label maps")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
@@ -244,7 +252,7 @@ class _PatchPool(torch.nn.Module):
 
 
 def build_model(args) -> torch.nn.Module:
-    if args.dataset_name.split("*")[0] in ("synthetic", "synthetic-depth", "synthetic-video") and not (args.timm_model or args.dinov2):
+    if args.dataset_name.split("*")[0] in ("synthetic", "synthetic-depth", "synthetic-video", "synthetic-classify") and not (args.timm_model or args.dinov2):
         return _PatchPool(args.patch_size)
     if args.dinov2:
         model = torch.hub.load("facebookresearch/dinov2", f"dinov2_{args.dinov2}")          # eval.py:213 (needs a hub cache)
@@ -396,11 +404,75 @@ def main_video(parser, args) -> None:
             json.dump(summary, f)
 
 
+KNN_EXCLUDES = ("frame_size", "window_stride", "memory_size", "grid_beta", "bootstrap", "overclustering", "linear_probe", "f_mem_p", "l_mem_p",
+                "leave_one_out_screen", "train_fs_path", "val_fs_path")
+KNN_ONLY = {"grid_temperature": None, "top_n": None}
+
+
+def classify_key(k: int, T: float) -> str:
+    """How a configuration of --task knn-classify is keyed in the result JSON."""
+    return f"k={int(k)},T={float(T)!r}"
+
+
+def main_knn_classify(parser, args) -> None:
+    """--task knn-classify: hbird_mi.classify.hbird_knn_classification and its JSON."""
+    if args.memory_sizes:
+        parser.error("--memory-sizes is not available with --task knn-classify: the bank holds one row per image (label subsets: "
+                     "HbirdKnnClassification.memory_view)")
+    for name in KNN_EXCLUDES:
+        if getattr(args, name):
+            parser.error(f"--{name.replace('_', '-').replace('-path', '')} is not available with --task knn-classify")
+    if not isinstance(args.n_neighbours, _DefaultInt):
+        parser.error("--n-neighbours is not available with --task knn-classify: give --grid-k")
+    if args.nn_method != "hip":
+        parser.error("--nn-method is not available with --task knn-classify (the vote reads the HIP index's lists)")
+    if args.target_grid != 1:
+        parser.error("--target-grid is not available with --task knn-classify")
+    if args.leave_one_out_images is not None and not args.leave_one_out:
+        parser.error("--leave-one-out-images needs --leave-one-out")
+    top_n = 5 if args.top_n is None else args.top_n
+    if top_n > 8:
+        parser.error("--top-n: at most 8 predictions are ranked per image")
+    ks = args.grid_k or [10, 20, 100, 200]
+    temps = args.grid_temperature or [0.07]
+    logging.basicConfig(level=getattr(logging, args.log_level), force=True)
+    set_seed(args.seed)
+    from hbird_mi import classify as hclassify
+    model = build_model(args)
+    t0 = time.time()
+    res = hclassify.hbird_knn_classification(model, d_model=args.d_model, patch_size=args.patch_size, dataset_name=args.dataset_name,
+                                             data_dir=args.data_dir, batch_size=args.batch_size, input_size=args.input_size,
+                                             augmentation_epoch=args.augmentation_epoch, device=args.device, n_neighbours=ks, temperatures=temps,
+                                             topn=top_n, nn_params=parse_nn_params(args.nn_param), ftr_extr_fn=default_ftr_extr_fn,
+                                             num_workers=args.num_workers, leave_one_out=args.leave_one_out,
+                                             leave_one_out_images=args.leave_one_out_images)
+    best, best_top1 = res.best() if res.n else (None, float("nan"))
+    summary = {"task": "knn-classify", "top1": {classify_key(*c): float(res.top1[c]) for c in res.configs},
+               f"top{top_n}": {classify_key(*c): float(res.topn[c]) for c in res.configs},
+               "mean_per_class": {classify_key(*c): float(res.mean_per_class[c]) for c in res.configs},
+               "best": None if best is None else {"key": classify_key(*best), "top1": float(best_top1)}, "n": res.n, "skipped": res.skipped,
+               "top_n": top_n, "seconds": round(time.time() - t0, 3), "dataset": args.dataset_name, **hclassify.last_run_info}
+    if args.leave_one_out:
+        summary["leave_one_out"] = True
+    print(json.dumps(summary))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f)
+
+
 def main(argv: Optional[List[str]] = None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.bootstrap_seed is not None and not args.bootstrap:
         parser.error("--bootstrap-seed needs --bootstrap")
+    if args.task == "knn-classify":
+        for name, default in VIDEO_ONLY.items():
+            if getattr(args, name) != default:
+                parser.error(f"--{name.replace('_', '-')} needs --task video")
+        return main_knn_classify(parser, args)
+    for name, default in KNN_ONLY.items():
+        if getattr(args, name) != default:
+            parser.error(f"--{name.replace('_', '-')} needs --task knn-classify")
     if args.task == "video":
         return main_video(parser, args)
     for name, default in VIDEO_ONLY.items():

@@ -238,6 +238,17 @@ SIGNATURES_PROPAGATE = {
     "hb_mask_jf_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# ... and include/hbird_hip_vote.h (image-level k-NN classification, csrc/hbird_vote.hip: the weighted vote of a (k, T) grid over one neighbour list
+# per query, the counts behind top-1 / top-n / mean-per-class accuracy); a header of its own, not included by hbird_hip.h
+VOTE_MAX_CONFIGS = 16            # HB_VOTE_MAX_CONFIGS
+VOTE_MAX_TOP = 8                 # HB_VOTE_MAX_TOP
+VOTE_MAX_K = 2048                # HB_VOTE_MAX_K
+VOTE_MAX_CLASSES = 2147483647    # HB_VOTE_MAX_CLASSES: no limit beyond int32 (a leader scan, no per-class bins)
+SIGNATURES_VOTE = {
+    "hb_knn_vote": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int, POINTER(c_int), c_int, POINTER(c_float), c_int,
+                            c_int, c_void_p, c_void_p, c_void_p]),
+    "hb_vote_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
 
 
 class HbirdHipError(RuntimeError):
@@ -260,7 +271,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()) + list(SIGNATURES_PROPAGATE.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()) + list(SIGNATURES_PROPAGATE.items()) + list(SIGNATURES_VOTE.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

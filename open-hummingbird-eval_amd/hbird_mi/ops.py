@@ -378,3 +378,70 @@ def mask_jf_counts(pred: torch.Tensor, gt: torch.Tensor, n_objects: int, bound_p
     counts = torch.empty((B, int(n_objects), len(_lib.JF_COUNTS)), dtype=torch.int64, device=pred.device)
     _lib.check(_lib.lib().hb_mask_jf_counts(_p(pred), _p(gt), B, h, w, int(n_objects), int(bound_px), _p(counts), _stream(pred)))
     return counts
+
+
+# ---- image-level k-NN classification (include/hbird_hip_vote.h, csrc/hbird_vote.hip) ---------------------------------------------------------
+def _vote_grid(who: str, ks, temps):
+    ks, temps = [int(k) for k in ks], [float(t) for t in temps]
+    if not ks or not temps:
+        raise ValueError(f"{who}: ks and temps must not be empty")
+    return ks, temps
+
+
+def knn_vote(idx: torch.Tensor, score: torch.Tensor, labels: torch.Tensor, C: int, ks, temps, topn: int = 5, id_base: int = 0,
+             want_votes: bool = False):
+    """The weighted vote of a (k, T) grid over one neighbour list per query: idx [nq, k_list] int64 / score [nq, k_list] fp32 as `search`
+    leaves them on an inner-product index (best first, -1 / -inf padding), labels [n_rows] int32 (one class in [0, C) per bank row, -1 =
+    unlabelled).  Configuration (k, T) votes over the first k list positions with weights exp(score / T); `ks` strictly ascending.
+    -> pred [len(ks) * len(temps), nq, topn] int32 (configuration ik * len(temps) + it; classes by descending vote, ties to the lower class,
+    -1 past the classes present) -- and with `want_votes` the votes [.., topn] fp32 beside it."""
+    for name, t, dt in (("idx", idx, torch.int64), ("score", score, torch.float32), ("labels", labels, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"knn_vote: {name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+    if idx.dim() != 2 or tuple(idx.shape) != tuple(score.shape) or labels.dim() != 1:
+        raise ValueError(f"knn_vote: idx and score must be [nq, k_list] alike and labels [n_rows], got {tuple(idx.shape)}, {tuple(score.shape)}, "
+                         f"{tuple(labels.shape)}")
+    if idx.device != score.device or idx.device != labels.device:
+        raise ValueError("knn_vote: idx, score and labels must be on one device")
+    ks, temps = _vote_grid("knn_vote", ks, temps)
+    _need_cuda(idx, score, labels)
+    idx, score, labels = idx.contiguous(), score.contiguous(), labels.contiguous()
+    nq, k_list = idx.shape
+    n_cfg = len(ks) * len(temps)
+    pred = torch.empty((n_cfg, nq, int(topn)), dtype=torch.int32, device=idx.device)
+    votes = torch.empty((n_cfg, nq, int(topn)), dtype=torch.float32, device=idx.device) if want_votes else None
+    if nq == 0:                                               # an empty call (an empty tensor has no address to hand over)
+        return (pred, votes) if want_votes else pred
+    _lib.check(_lib.lib().hb_knn_vote(_p(idx), _p(score), nq, k_list, int(id_base), _p(labels), labels.shape[0], int(C),
+                                      (ctypes.c_int * len(ks))(*ks), len(ks), (ctypes.c_float * len(temps))(*temps), len(temps), int(topn),
+                                      _p(pred), _p(votes), _stream(idx)))
+    return (pred, votes) if want_votes else pred
+
+
+def vote_counts(pred: torch.Tensor, qlabels: torch.Tensor, C: int, counts: torch.Tensor, n: torch.Tensor,
+                class_counts: Optional[torch.Tensor] = None) -> None:
+    """ADDS a batch to the count tables: pred [n_cfg, nq, topn] int32 (`knn_vote`), qlabels [nq] int32 (-1: counted nowhere) ->
+    counts [n_cfg, topn] int64 (slot t += 1 where the label is among pred[..., :t + 1]), n [1] int64 += the labelled queries, and where given
+    class_counts [n_cfg, C, 2] int64 ([c][0] += 1 per labelled query of class c, [c][1] += 1 where its first prediction is c).  A query label
+    outside [-1, C) raises ValueError before anything is counted (a flag read: the call synchronises the stream)."""
+    if not isinstance(pred, torch.Tensor) or pred.dtype != torch.int32 or pred.dim() != 3:
+        raise ValueError(f"vote_counts: pred must be an int32 [n_cfg, nq, topn] tensor, got {getattr(pred, 'dtype', type(pred))} {tuple(getattr(pred, 'shape', ()))}")
+    n_cfg, nq, topn = pred.shape
+    if not isinstance(qlabels, torch.Tensor) or qlabels.dtype != torch.int32 or tuple(qlabels.shape) != (nq,):
+        raise ValueError(f"vote_counts: qlabels must be an int32 [{nq}] tensor, got {getattr(qlabels, 'dtype', type(qlabels))} {tuple(getattr(qlabels, 'shape', ()))}")
+    for name, t, shape in (("counts", counts, (n_cfg, topn)), ("n", n, (1,)), ("class_counts", class_counts, (n_cfg, int(C), 2))):
+        if t is None and name == "class_counts":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"vote_counts: {name} must be a contiguous int64 {list(shape)} tensor, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+        if t.device != pred.device:
+            raise ValueError(f"vote_counts: {name} must be on the device of pred")
+    if qlabels.device != pred.device:
+        raise ValueError("vote_counts: qlabels must be on the device of pred")
+    _need_cuda(pred, qlabels, counts, n, class_counts)
+    pred, qlabels = pred.contiguous(), qlabels.contiguous()
+    if nq == 0:
+        return
+    _lib.check(_lib.lib().hb_vote_counts(_p(pred), _p(qlabels), nq, n_cfg, topn, int(C), _p(counts), _p(class_counts), _p(n), _stream(pred)),
+               ValueError)
