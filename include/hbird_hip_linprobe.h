@@ -26,6 +26,9 @@
  *   *used_host = n (HOST; skipped = ntotal - n), resid_opt [ntotal][C] fp32 = R or NULL.  The bank is read in row chunks of whole segments with
  *   a workspace of at most about HB_LINPROBE_WORKSPACE bytes; every buffer is a local of the call: hb_debug_live_allocations afterwards equals
  *   its value before.  Fails when every row is skipped.
+ * hb_linprobe_set_workspace(bytes): a test seam, process-wide like hb_set_layout_form: the workspace of later hb_linprobe_loss_grad calls;
+ *   0 restores HB_LINPROBE_WORKSPACE, a negative value is refused.  A chunk is at least one segment whatever the value, and no result depends
+ *   on it (the segment rule above).
  *
  * Wb, out, grad, resid_opt are DEVICE pointers on the index's device; work is enqueued on the index's stream, which the entries synchronise.
  * Every entry returns 0, or -1 with hb_last_error set -- before anything is launched for a NULL handle or pointer, C outside
@@ -39,4 +42,5 @@ int hb_linprobe_partition(int64_t ntotal, int64_t* seg_rows, int* nseg);
 int hb_linprobe_logits(hb_index_t* ix, const float* Wb, int C, float* out);
 int hb_linprobe_loss_grad(hb_index_t* bank, const float* Wb, int C, double l2, double* loss_host, double* grad, int64_t* used_host,
                           float* resid_opt);
+int hb_linprobe_set_workspace(int64_t bytes);
 #endif /* HBIRD_HIP_LINPROBE_H */

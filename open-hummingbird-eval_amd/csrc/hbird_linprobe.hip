@@ -353,6 +353,13 @@ extern "C" int hb_linprobe_partition(int64_t ntotal, int64_t* seg_rows, int* nse
     return 0;
 }
 
+static int64_t g_linprobe_workspace = 0;      // 0 = HB_LINPROBE_WORKSPACE (tests: a small one makes the chunk loop run on small banks)
+extern "C" int hb_linprobe_set_workspace(int64_t bytes) {
+    if (bytes < 0) return hb_fail("hb_linprobe_set_workspace: bytes must be 0 (HB_LINPROBE_WORKSPACE) or positive, got " + std::to_string(bytes));
+    g_linprobe_workspace = bytes;
+    return 0;
+}
+
 extern "C" int hb_linprobe_logits(hb_index_t* ix, const float* Wb, int C, float* out) {
     if (!ix) return hb_fail("hb_linprobe_logits: NULL index handle");
     if (!Wb || !out) return hb_fail("hb_linprobe_logits: NULL pointer");
@@ -395,7 +402,8 @@ extern "C" int hb_linprobe_loss_grad(hb_index_t* bank, const float* Wb, int C, d
     const int cp = par.ct * 32;
     // the bank in row chunks of whole segments: residuals [rows][cp], staged rows [rows][xs], segment partials [segments][cp][xs]
     const int64_t seg_bytes = seg_rows * (int64_t)(cp + xs) * 4;
-    const int chunk_segs = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, (int64_t)HB_LINPROBE_WORKSPACE / seg_bytes));
+    const int64_t workspace = g_linprobe_workspace > 0 ? g_linprobe_workspace : (int64_t)HB_LINPROBE_WORKSPACE;
+    const int chunk_segs = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, workspace / seg_bytes));
     const int64_t chunk_rows = (int64_t)chunk_segs * seg_rows, npad = (n + LP_ROWS - 1) / LP_ROWS * LP_ROWS;
     const int64_t chunk_pad = std::min(chunk_rows, npad);
     hb_dev<float> resid, X, partial, rowloss; hb_dev<unsigned char> skip; hb_dev<double> tree, scal;

@@ -201,6 +201,7 @@ SIGNATURES_LINPROBE = {
     "hb_linprobe_partition": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int)]),
     "hb_linprobe_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "hb_linprobe_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_double, POINTER(c_double), c_void_p, POINTER(c_int64), c_void_p]),
+    "hb_linprobe_set_workspace": (c_int, [c_int64]),
 }
 
 # ... and include/hbird_hip_depth.h (depth estimation by retrieval, csrc/hbird_depth.hip: depth maps to patch label rows, aggregated rows to a

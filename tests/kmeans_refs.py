@@ -13,6 +13,8 @@ Every world generator asserts its own condition: at every iteration of the model
 distances differ by more than 1e-3 of the best (and, stricter than asked, by more than 1e-4 outright), so that fp32 arithmetic cannot flip an
 assignment and the model alone decides what the engine must return.  The tie worlds are the exception: their ties are exactly equal centroids.
 """
+import functools
+
 import numpy as np
 
 TWO30 = float(2 ** 30)
@@ -114,14 +116,18 @@ def _unit(v):
     return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
 
 
-def blob_world(K, D, rows, seed, sigma=0.05, max_iter=10):
-    """K planted blobs of unit-norm rows around random unit centres, rows dealt to the blobs in random order; init: the first row of every blob.
-    -> (x float32 [rows, D], init float32 [K, D], init_rows int64 [K], model)."""
+def _draw_blobs(K, D, rows, seed, sigma):
     g = np.random.default_rng(seed)
     centres = _unit(g.standard_normal((K, D)))
     blob = np.concatenate([np.arange(K), g.integers(0, K, rows - K)])
     g.shuffle(blob)
-    x = _unit(centres[blob].astype(np.float64) + sigma * g.standard_normal((rows, D)))
+    return _unit(centres[blob].astype(np.float64) + sigma * g.standard_normal((rows, D))), blob
+
+
+def blob_world(K, D, rows, seed, sigma=0.05, max_iter=10):
+    """K planted blobs of unit-norm rows around random unit centres, rows dealt to the blobs in random order; init: the first row of every blob.
+    -> (x float32 [rows, D], init float32 [K, D], init_rows int64 [K], model)."""
+    x, blob = _draw_blobs(K, D, rows, seed, sigma)
     init_rows = np.array([int(np.flatnonzero(blob == c)[0]) for c in range(K)], dtype=np.int64)
     model = fit(x, x[init_rows], max_iter)
     assert_margins(model)
@@ -131,6 +137,67 @@ def blob_world(K, D, rows, seed, sigma=0.05, max_iter=10):
 
 # (K, D, rows, seed): the committed seeds pass the margin condition (checked by tests/test_kmeans_cpu.py on every run)
 BLOB_WORLDS = [(3, 16, 600, 11), (33, 16, 4000, 12), (3, 72, 4000, 13), (33, 72, 600, 14)]
+
+# The bank-size seams (the arithmetic is spelled out in tests/linprobe_refs.py at BIG_ROWS, and asserted by tests/test_kmeans_cpu.py):
+# 4,100 row tiles in 128 segments of 33 -- all four slots of a wave, a second trip, a segment of 8 tiles and three empty ones --, 33 workgroups
+# of kmeans_counts_kernel and kmeans_changed_kernel, rows with j = 1 and 2 in the inertia tree, two default staging chunks (131,072 + 123).
+BIG_ROWS = 131195
+BIG_HOLE = 100003                                  # the one non-finite row: past row 65,536
+BIG_BLOB_WORLD = (5, 16, BIG_ROWS, 15)
+SEG_TILES_MIN, MAX_SEGS, WAVES, UNROLL = 16, 128, 8, 4      # KM_SEG_TILES, KM_MAX_SEGS, KM_WAVES, KM_UNROLL of csrc/hbird_kmeans.hip
+
+
+def km_segments(row0, n):
+    """km_accumulate's launch arithmetic -> (rt_begin, rt_end, segs, seg_tiles): the row tiles [rt_begin, rt_end) of rows row0 .. row0 + n - 1,
+    segs = min(128, ceil(tiles / 16)) workgroups per column group, each of seg_tiles = ceil(tiles / segs) tiles."""
+    rt_begin, rt_end = row0 >> 5, (row0 + n + 31) >> 5
+    nt = rt_end - rt_begin
+    segs = max(1, min(MAX_SEGS, -(-nt // SEG_TILES_MIN)))
+    return rt_begin, rt_end, segs, -(-nt // segs)
+
+
+def walked_tiles(row0, n, trips=None, slots=UNROLL):
+    """[(tile, segment, wave, slot, trip)] of every row tile kmeans_accumulate_kernel reads: in segment s, wave w and slot u of trip p take
+    tile t0 + w + 8 u + 32 p while it is below the segment's end.  `trips` and `slots` cut the walk short: WRONG variants for
+    tests/test_bank_task_seams_cpu.py."""
+    rt_begin, rt_end, segs, seg_tiles = km_segments(row0, n)
+    out = []
+    for s in range(segs):
+        t0 = rt_begin + s * seg_tiles
+        t1 = min(rt_end, t0 + seg_tiles)
+        for w in range(WAVES):
+            p = 0
+            while t0 + w + WAVES * UNROLL * p < t1 and (trips is None or p < trips):
+                for u in range(slots):
+                    t = t0 + w + WAVES * u + WAVES * UNROLL * p
+                    if t < t1:
+                        out.append((t, s, w, u, p))
+                p += 1
+    return out
+
+
+def walked_sums(x, a, K, row0=0, n=None, trips=None, slots=UNROLL):
+    """integer_sums over the rows of the tiles that walked_tiles visits (the whole range when the walk is the kernel's)."""
+    n = x.shape[0] - row0 if n is None else n
+    keep = np.zeros(x.shape[0], dtype=bool)
+    for t, *_ in walked_tiles(row0, n, trips, slots):
+        keep[max(row0, t * 32):min(row0 + n, (t + 1) * 32)] = True
+    return integer_sums(x, np.where(keep, np.asarray(a), -1), K)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def big_blob_world(max_iter=10):
+    """BIG_BLOB_WORLD: blob_world's draw with row BIG_HOLE made non-finite (it stays unassigned); the margins are asserted.
+    -> (x, init, init_rows, model)."""
+    K, D, rows, seed = BIG_BLOB_WORLD
+    x, blob = _draw_blobs(K, D, rows, seed, 0.05)
+    init_rows = np.array([int(np.flatnonzero(blob == c)[0]) for c in range(K)], dtype=np.int64)
+    assert BIG_HOLE not in set(init_rows.tolist())
+    x[BIG_HOLE, 2] = np.nan
+    model = fit(x, x[init_rows], max_iter)
+    assert_margins(model)
+    assert model["converged"] and model["history"][0]["changed"] == rows - 1 and all(h["unassigned"] == 1 for h in model["history"])
+    return x, x[init_rows].copy(), init_rows, model
 
 
 def drift_world(K, D, rows, seed, sigma=0.12, max_iter=20):

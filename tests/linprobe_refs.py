@@ -6,6 +6,8 @@
   objective(z, x, y, Wb, l2, skipped)  float64 from GIVEN logits: loss, gradient, residuals R, probabilities p, row losses l
   segment_gradient(R, x, skipped, Wb, l2)  the engine's gradient order given residuals: per segment an fp32 fmaf chain over ascending rows from
                                 0, the partials added in float64 in ascending segment order, / n, + l2 Wb
+  chunks(ntotal, workspace_segs), chunked_sums(...)  the host loop over workspace chunks, and the float64 sums as that loop walks them (with
+                                two wrong variants for tests/test_bank_task_seams_cpu.py)
   lbfgs(fun, x0, gtol, max_iter)  the fit's loop restated; fit_fp32_forward: that loop on an fp32 forward; optimum64: the float64 optimum
 
 The pieces reach each other through the module's names (row_mass, used_rows, regulariser, add_segments, chain_logits), so a test can swap one for
@@ -110,7 +112,7 @@ def _fma32(a, b, c):
     return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
 
 
-def segment_partials(R, x, skipped):
+def segment_partials_by_rows(R, x, skipped):
     """[nseg] arrays float32 [C, D + 1]: per segment the fmaf chain over ascending rows of R[r][c] * [1, x[r]][j], started at 0."""
     R, x = np.asarray(R, dtype=np.float32), np.asarray(x, dtype=np.float32)
     aug = np.concatenate([np.ones((x.shape[0], 1), dtype=np.float32), x], axis=1)
@@ -125,8 +127,53 @@ def segment_partials(R, x, skipped):
     return out
 
 
+def segment_partials(R, x, skipped):
+    """segment_partials_by_rows with all segments advancing together: step i takes row j * seg_rows + i of every segment j (the same fma on
+    the same operands in the same order per segment; rows past the end are the exact zeros that the engine's padding rows are).
+    tests/test_linprobe_cpu.py holds the two forms to each other on bits."""
+    R, x = np.asarray(R, dtype=np.float32), np.asarray(x, dtype=np.float32)
+    aug = np.concatenate([np.ones((x.shape[0], 1), dtype=np.float32), x], axis=1)
+    aug[skipped] = 0.0
+    seg_rows, nseg = partition(x.shape[0])
+    pad = nseg * seg_rows - x.shape[0]
+    Rp = np.concatenate([R, np.zeros((pad, R.shape[1]), dtype=np.float32)]).reshape(nseg, seg_rows, R.shape[1])
+    Ap = np.concatenate([aug, np.zeros((pad, aug.shape[1]), dtype=np.float32)]).reshape(nseg, seg_rows, aug.shape[1])
+    acc = np.zeros((nseg, R.shape[1], aug.shape[1]), dtype=np.float32)
+    for i in range(seg_rows):
+        acc = _fma32(Rp[:, i, :, None], Ap[:, i, None, :], acc)
+    return list(acc)
+
+
 def segment_gradient(R, x, skipped, Wb, l2):
     return add_segments(segment_partials(R, x, skipped)) / used_rows(skipped) + regulariser(Wb, l2)[1]
+
+
+def chunks(ntotal, workspace_segs):
+    """The host loop of hb_linprobe_loss_grad: [(row0, rows, segments)] of every workspace chunk when the workspace holds `workspace_segs`
+    segments (None: all of them); a chunk is at least one segment."""
+    seg_rows, nseg = partition(ntotal)
+    per = nseg if workspace_segs is None else min(nseg, max(1, workspace_segs))
+    out = []
+    for seg0 in range(0, nseg, per):
+        segs, row0 = min(per, nseg - seg0), seg0 * seg_rows
+        out.append((row0, min(ntotal, row0 + segs * seg_rows) - row0, segs))
+    return out
+
+
+def chunked_sums(R, x, skipped, workspace_segs=None, staged_from_row_0=False, segment_cut=None):
+    """sum_r R[r][c] [1, x[r]][j] in float64 as the host loop walks it: chunk by chunk, segment by segment, residuals and staged rows by their
+    chunk-local index.  The two switches are WRONG variants for tests/test_bank_task_seams_cpu.py: a chunk whose staged rows restart at bank
+    row 0, and a segment whose row loop ends after `segment_cut` rows."""
+    R64, x64 = np.asarray(R).astype(np.float64), np.asarray(x, dtype=np.float32).astype(np.float64)
+    aug = np.concatenate([np.ones((x64.shape[0], 1)), np.where(skipped[:, None], 0.0, x64)], axis=1)
+    seg_rows = partition(x64.shape[0])[0]
+    total = np.zeros((R64.shape[1], aug.shape[1]))
+    for row0, rows, segs in chunks(x64.shape[0], workspace_segs):
+        x0 = 0 if staged_from_row_0 else row0
+        for j in range(segs):
+            a, b = j * seg_rows, min(rows, j * seg_rows + (seg_rows if segment_cut is None else min(seg_rows, segment_cut)))
+            total += R64[row0 + a:row0 + b].T @ aug[x0 + a:x0 + b]
+    return total
 
 
 def gradient_bound(R, x, skipped):
@@ -256,10 +303,41 @@ WORLDS = [(3, 16, 600, 1024, 21, 0.3), (33, 16, 4000, 1024, 22, 0.2), (3, 72, 40
 WIDE_WORLD = (151, 16, 600, 64, 25, 0.2)          # P = 196: count rows of stride 152
 SEGMENT_WORLD = (3, 16, 513, 64, 26, 0.3)         # three segments, the last one of one row: the smallest row count with three
 
+# The bank-size seams.  BIG_ROWS = 131,195 = 4,099 row tiles of 32 and 27 rows = 512 blocks of 256 and 123 rows:
+#   linear probe (partition): t = ceil(131,195 / 256) = 513 > MAX_SEGS, so seg_rows = 256 * ceil(513 / 512) = 512 and nseg = ceil(131,195 / 512) = 257,
+#     the last segment of 131,195 - 256 * 512 = 123 rows; the loss tree has rows with j = 1 (r >= 65,536) and, for r >= 131,072, j = 2
+#   k-means (km_segments of tests/kmeans_refs.py): nt = 4,100 row tiles, segs = min(128, ceil(4,100 / 16)) = 128, seg_tiles = ceil(4,100 / 128) = 33:
+#     124 full segments (4,092 tiles), one of 8 tiles and three empty ones; 33 tiles are two trips of 32 with all four slots live
+# (tests/test_linprobe_cpu.py and tests/test_kmeans_cpu.py assert this arithmetic.)
+BIG_ROWS = 131195
+BIG_HOLE = 100003                                  # the one non-finite row of a big world: past row 65,536 (tree index j = 1)
+BIG_WORLD = (3, 16, BIG_ROWS, 64, 27, 0.3)
+
+# Class tiles: CT = ceil(C / 32) from 1 to 8 at both ends of every tile (C = 32 CT: the `t * 32 + i < C` masks stop masking; C = 32 CT + 1:
+# one live class in the last tile), on 300 rows (nine row tiles and 12 rows, two forward workgroups, two segments); (256, 72): width padded to
+# 80, g8 = 10, two LDS staging rounds of the largest Wb; (225, 384): a wide bank.  Count rows (P = 16) have their stride padded to 8.
+TILE_ROWS = 300
+TILE_WORLDS = [(C, 16, TILE_ROWS, 8, 40 + i, 0.2) for i, C in enumerate((32, 64, 65, 96, 97, 128, 160, 161, 192, 193, 224, 225, 256, 129))] + [
+    (256, 72, TILE_ROWS, 8, 60, 0.15), (225, 384, TILE_ROWS, 8, 61, 0.1)]      # (C = 33, the low end of two tiles, is in WORLDS)
+
+# Residuals and loss on TILE_WORLDS and BIG_WORLD (C up to 256), measured as MEASURED_P_REL and MEASURED_L_REL were (profiles/r34/README.md):
+MEASURED_P_REL_WIDE = 2.98e-6   # (224, 16, 300) at parameters of scale 4
+MEASURED_L_REL_WIDE = 1.98e-8   # (225, 384, 300) at parameters of scale 1
+BOUND_P_REL_WIDE, BOUND_L_REL_WIDE = 4 * MEASURED_P_REL_WIDE, 4 * MEASURED_L_REL_WIDE
+
 
 @functools.lru_cache(maxsize=None)
 def world(spec, P=16):
     return draw_world(*spec, P=P)
+
+
+@functools.lru_cache(maxsize=None)
+def big_world():
+    """BIG_WORLD with its one non-finite row, BIG_HOLE."""
+    w = dict(world(BIG_WORLD))
+    w["x"] = w["x"].copy()
+    w["x"][BIG_HOLE, 5] = np.nan
+    return w
 
 
 @functools.lru_cache(maxsize=None)

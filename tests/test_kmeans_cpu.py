@@ -134,6 +134,26 @@ def test_committed_worlds_hold_their_margins_and_their_histories():
         R.assert_margins(R.fit(x, c, 3))
 
 
+def test_the_big_blob_world_crosses_the_row_count_seams_and_holds_its_margins():
+    n = R.BIG_ROWS
+    rt_begin, rt_end, segs, seg_tiles = R.km_segments(0, n)
+    assert (rt_begin, rt_end, segs, seg_tiles) == (0, 4100, 128, 33)
+    full, rest = divmod(4100, 33)
+    assert (full, rest) == (124, 8) and segs - full - 1 == 3            # 124 full segments, one of 8 tiles, three empty ones
+    walk = R.walked_tiles(0, n)
+    assert sorted(t for t, *_ in walk) == list(range(4100))             # every tile once
+    assert {u for _, _, _, u, _ in walk} == {0, 1, 2, 3} and {p for *_, p in walk} == {0, 1}
+    assert {s for _, s, *_ in walk} == set(range(125))
+    assert R.km_segments(0, 4000) == (0, 125, 8, 16) and R.km_segments(5, 70) == (0, 3, 1, 3) and R.km_segments(65541, 10) == (2048, 2049, 1, 1)
+    assert n > 2 * 65536 and n > 131072 == 131072                       # the inertia tree at j = 1 and 2; the default staging chunk splits the bank
+    x, init, init_rows, model = R.big_blob_world()                      # (asserts the margins at every iteration)
+    assert x.shape == (n, 16) and init.shape == (5, 16) and model["converged"] and model["n_iter"] <= 10
+    assert np.flatnonzero(~np.isfinite(x).all(axis=1)).tolist() == [R.BIG_HOLE] and 65536 < R.BIG_HOLE and model["assign"][R.BIG_HOLE] == -1
+    a = model["assign"]
+    S, cnt = R.integer_sums(x, a, 5)
+    assert np.array_equal(R.walked_sums(x, a, 5), S) and cnt.sum() == n - 1
+
+
 # ---- named checks of the model, and the wrong variants that must fail them -----------------------------------------------------------------------
 def check_half_even():
     q = R.quantise(np.array([2.0 ** -31, 3 * 2.0 ** -31, -3 * 2.0 ** -31], dtype=np.float32)).tolist()

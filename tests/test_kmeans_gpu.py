@@ -1,7 +1,10 @@
 """k-means over the resident bank on the GPU (include/hbird_hip_kmeans.h, hbird_mi/kmeans.py) against the numpy model of tests/kmeans_refs.py:
 the assignment step against the public k = 1 search and, on worlds whose fp32 arithmetic is exact, against the float64 argmin; the integer
 update on bits; the loop on assignments, centroid bits and the integers of its history.  Shapes are the smallest at which a path can go wrong:
-one row, rows around a tile (31, 33), several tiles and segments (257, 1000, 4000), a padded width (72 -> 80), K = 1 and K = 2048."""
+one row, rows around a tile (31, 33), several tiles and segments (257, 1000, 4000), a padded width (72 -> 80), K = 1 and K = 2048; and
+R.BIG_ROWS = 131,195 rows, the smallest bank that crosses every row-count seam at once (tests/linprobe_refs.py spells out the arithmetic,
+tests/test_bank_task_seams_cpu.py holds the lists below to it): all four slots of an accumulating wave, a second trip, empty trailing segments,
+33 workgroups of the counting kernels, j = 1 and 2 in the inertia tree, a default staging chunk that splits the bank."""
 import ctypes
 import math
 
@@ -172,6 +175,69 @@ def test_accumulate_over_split_row_ranges_equals_one_call(cuda_device):
     with pytest.raises(ValueError, match="outside the bank"):
         KM.accumulate(bank, at, K, row0=1)
     bank.close()
+
+
+# ---- past the first bank-size seams (R.BIG_ROWS; the lists are held to the launch arithmetic by tests/test_bank_task_seams_cpu.py) -----------------
+BIG_D = 16
+BIG_UPDATE_K = (5, 2048)
+# (row0, n) of the calls that together cover the bank: cuts off the tile edges, the last range ending inside the last tile
+BIG_SPLITS = [(0, 65541), (65541, R.BIG_ROWS - 10 - 65541), (R.BIG_ROWS - 10, 10)]
+BIG_ASSIGN_CHUNKS = (0, 64 * 1024)              # the default staging chunk (131,072 rows: two chunks) against chunks of 65,536 (three)
+BIG_SAMPLE = (R.BIG_ROWS - 4096, 4096)          # rows of the sample held to the public search: both sides of the default chunk's edge, 131,072
+
+
+def _big_uniform(seed):
+    g = np.random.default_rng(seed)
+    return g.uniform(-1, 1, (R.BIG_ROWS, BIG_D)).astype(np.float32), g
+
+
+@pytest.mark.parametrize("K", BIG_UPDATE_K)
+def test_accumulate_on_the_big_bank_every_slot_a_second_trip_and_empty_segments(cuda_device, K):
+    x, g = _big_uniform(20 + K)
+    a = np.where(g.random(R.BIG_ROWS) < 0.1, -1, g.integers(0, K, R.BIG_ROWS)).astype(np.int32)
+    a[R.BIG_ROWS - 1] = K - 1
+    _check_update(x, a, K, seed=K)
+
+
+def test_accumulate_over_split_row_ranges_of_the_big_bank_equals_one_call(cuda_device):
+    K = 9
+    x, g = _big_uniform(30)
+    a = np.where(g.random(R.BIG_ROWS) < 0.1, -1, g.integers(0, K, R.BIG_ROWS)).astype(np.int32)
+    assert BIG_SPLITS[0][0] == 0 and all(p[0] + p[1] == q[0] for p, q in zip(BIG_SPLITS, BIG_SPLITS[1:])) and sum(BIG_SPLITS[-1]) == R.BIG_ROWS
+    bank, at = _bank(x), torch.from_numpy(a).cuda()
+    whole = KM.accumulate(bank, at, K)
+    sums = counts = None
+    for row0, n in BIG_SPLITS:
+        sums, counts = KM.accumulate(bank, at[row0:row0 + n], K, row0=row0, sums=sums, counts=counts)
+    assert torch.equal(sums, whole[0]) and torch.equal(counts, whole[1])
+    S, cnt = R.integer_sums(x, a, K)
+    assert np.array_equal(sums.cpu().numpy(), S) and np.array_equal(counts.cpu().numpy(), cnt)
+    # a range that ends inside the last tile, on its own, against the model
+    row0, n = BIG_SPLITS[1][0], R.BIG_ROWS - 10 - BIG_SPLITS[1][0]
+    part = KM.accumulate(bank, at[row0:row0 + n], K, row0=row0)
+    masked = np.full(R.BIG_ROWS, -1, dtype=np.int32); masked[row0:row0 + n] = a[row0:row0 + n]
+    S, cnt = R.integer_sums(x, masked, K)
+    assert np.array_equal(part[0].cpu().numpy(), S) and np.array_equal(part[1].cpu().numpy(), cnt)
+    bank.close()
+
+
+def test_assign_on_the_big_bank_the_default_staging_chunk_splits_it(cuda_device):
+    x, init, init_rows, model = R.big_blob_world()
+    bank, cent, theirs = _bank(x), _cent(model["centroids"]), _cent(model["centroids"])
+    got = {c: KM.assign_rows(bank, cent, chunk_rows=c) for c in BIG_ASSIGN_CHUNKS}
+    a, d = got[0]
+    assert torch.equal(got[64 * 1024][0], a) and np.array_equal(_bits(got[64 * 1024][1]), _bits(d))
+    assert np.array_equal(a.cpu().numpy(), model["assign"]) and a[R.BIG_HOLE].item() == -1      # (the margins hold: the model decides)
+    row0, n = BIG_SAMPLE
+    idx, dist = theirs.search(torch.from_numpy(x[row0:row0 + n]).cuda(), 1)
+    assert torch.equal(a[row0:row0 + n].long(), idx.view(-1)) and np.array_equal(_bits(d[row0:row0 + n]), _bits(dist.view(-1)))
+    bank.close(); cent.close(); theirs.close()
+
+
+def test_fit_on_the_big_blob_world_equals_the_model(cuda_device):
+    x, init, init_rows, model = R.big_blob_world()
+    res = _check_fit(x, init, model, max_iter=10)
+    assert res.converged and res.n_iter == model["n_iter"] and all(h["unassigned"] == 1 for h in res.history)
 
 
 def test_accumulate_refuses_rows_outside_the_quantisers_range(cuda_device):

@@ -12,7 +12,7 @@ import linprobe_refs as R
 from hbird_mi import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"hb_linprobe_partition", "hb_linprobe_logits", "hb_linprobe_loss_grad"}
+NAMES = {"hb_linprobe_partition", "hb_linprobe_logits", "hb_linprobe_loss_grad", "hb_linprobe_set_workspace"}
 C_TYPES = {"hb_index_t*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float*": ctypes.c_void_p,
            "const float*": ctypes.c_void_p, "double*": ctypes.c_void_p}
 HOST_OUT = {("hb_linprobe_partition", "seg_rows"): ctypes.POINTER(ctypes.c_int64), ("hb_linprobe_partition", "nseg"): ctypes.POINTER(ctypes.c_int),
@@ -53,6 +53,7 @@ def test_linprobe_entries_are_declared_exported_bound_and_documented():
     assert [a for _, a in decl["hb_linprobe_partition"][1]] == ["ntotal", "seg_rows", "nseg"]
     assert [a for _, a in decl["hb_linprobe_logits"][1]] == ["ix", "Wb", "C", "out"]
     assert [a for _, a in decl["hb_linprobe_loss_grad"][1]] == ["bank", "Wb", "C", "l2", "loss_host", "grad", "used_host", "resid_opt"]
+    assert decl["hb_linprobe_set_workspace"][1] == [("int64_t", "bytes")]
     assert int(re.search(r"#define HB_LINPROBE_MAX_C (\d+)", header).group(1)) == _lib.LINPROBE_MAX_C == 256
     assert int(re.search(r"#define HB_LINPROBE_MAX_SEGS (\d+)", header).group(1)) == _lib.LINPROBE_MAX_SEGS == R.MAX_SEGS
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
@@ -89,6 +90,8 @@ def test_linprobe_entries_refuse_bad_arguments_before_any_launch():
     rows, n = ctypes.c_int64(0), ctypes.c_int(0)
     assert L.hb_linprobe_partition(100, None, ctypes.byref(n)) != 0 and "NULL pointer" in _lib.last_error()
     assert L.hb_linprobe_partition(0, ctypes.byref(rows), ctypes.byref(n)) != 0 and "positive" in _lib.last_error()
+    assert L.hb_linprobe_set_workspace(-1) != 0 and "hb_linprobe_set_workspace" in _lib.last_error()
+    assert L.hb_linprobe_set_workspace(65536) == 0 and L.hb_linprobe_set_workspace(0) == 0
 
 
 def test_partition_is_the_written_rule_and_the_model_restates_it():
@@ -253,3 +256,37 @@ def test_the_wide_and_the_segment_world_are_what_they_are_for():
     w = R.world(R.WIDE_WORLD, 196)
     assert w["C"] == 151 and (w["counts"].sum(axis=1) == 196).all() and (151 + 7) // 8 * 8 == 152
     assert R.partition(R.world(R.SEGMENT_WORLD)["x"].shape[0]) == (256, 3)
+
+
+def test_the_big_world_and_the_tile_worlds_are_what_they_are_for():
+    n = R.BIG_ROWS
+    assert R.BIG_WORLD[:3] == (3, 16, n) and -(-n // 256) == 513 and R.partition(n) == (512, 257) and n - 256 * 512 == 123
+    assert n > 2 * 65536 and 65536 < R.BIG_HOLE < n            # the loss tree: rows at j = 1 and 2; the non-finite row past 65,536
+    w = R.big_world()
+    assert np.flatnonzero(R.skipped_rows(w["x"])).tolist() == [R.BIG_HOLE] and np.isfinite(R.world(R.BIG_WORLD)["x"]).all()
+    assert R.chunks(n, None) == [(0, n, 257)]
+    three = R.chunks(n, 3)
+    assert len(three) == 86 and three[-1] == (255 * 512, n - 255 * 512, 2) and all(c == (i * 1536, 1536, 3) for i, c in enumerate(three[:-1]))
+    assert R.chunks(513, 1) == [(0, 256, 1), (256, 256, 1), (512, 1, 1)] and R.chunks(513, 2) == [(0, 512, 2), (512, 1, 1)] and R.chunks(513, 0) == R.chunks(513, 1)
+    tiles = {}
+    for C, D, rows, n_val, seed, sigma in R.TILE_WORLDS:
+        assert rows == R.TILE_ROWS == 9 * 32 + 12 and R.partition(rows) == (256, 2)
+        tiles.setdefault(-(-C // 32), set()).add(C)
+        w = R.world((C, D, rows, n_val, seed, sigma))
+        assert w["counts"].shape == (rows, C) and (w["counts"].sum(axis=1) == 16).all()
+    assert sorted(tiles) == [1, 2, 3, 4, 5, 6, 7, 8] and all(32 * ct in cs for ct, cs in tiles.items())          # every tile count with its tile full ...
+    assert all(32 * (ct - 1) + 1 in cs for ct, cs in tiles.items() if ct > 2)                                     # ... and with one class in its last tile
+    assert (256, 72) in {w[:2] for w in R.TILE_WORLDS} and (225, 384) in {w[:2] for w in R.TILE_WORLDS}
+    assert len(set(w[4] for w in R.TILE_WORLDS)) == len(R.TILE_WORLDS)
+
+
+def test_segment_partials_in_step_equal_the_row_by_row_form_on_bits():
+    for spec, hole in ((R.WORLDS[0], 37), (R.SEGMENT_WORLD, 512), (R.TILE_WORLDS[2], 299)):
+        w = R.world(spec)
+        x = w["x"].copy(); x[hole, 3] = np.nan
+        Wb = (np.random.default_rng(7).standard_normal((w["C"], w["D"] + 1)) * 0.5).astype(np.float32)
+        z, skip = R.chain_logits(x, Wb)
+        R32 = R.objective(z, x, w["y"], Wb, 1e-2, skip)["R"].astype(np.float32)
+        fast, slow = R.segment_partials(R32, x, skip), R.segment_partials_by_rows(R32, x, skip)
+        assert len(fast) == len(slow) == R.partition(x.shape[0])[1]
+        assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(fast, slow))
