@@ -307,7 +307,8 @@ int hb_rerank_copy_replay(int setting, uint64_t bank_bytes, uint64_t need_bytes,
  * 6 workgroups, 7 kernel family (1 = fp16), 8 balance (uneven XCD shares apply), 9 / 10 cluster shape, 11 auto_cluster (the fp32 kernel's
  * automatic shape), 12 panel, 13 phased, 14 xs (XCD-level query sharing), 15 lag, 16 the kernel -- 0 fp16 candidate kernel; LDS-staged fp32
  * kernels: 1 lists, 2 lists cold (small searches), 3 pools, 4 lists clustered, 5 pools clustered, 6 CEIL; register-resident fp32 kernels: 8 + 4
- * wide + 2 clustered + 1 small --, 17 the work list's workgroups, 18 small.  Negative: bad arguments. */
+ * wide + 2 clustered + 1 small --, 17 the work list's workgroups, 18 small; with n_out >= 20: 19 filled (the filled clustered list is asked
+ * for).  Negative: bad arguments. */
 int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int n_out);
 /* hb_certificate_bound_replay: the bounds of the fp16 screen's certificate without a GPU (tests), evaluated in float by the code the re-rank
  * kernels compile (csrc/hbird_certificate.h).  in[0..7] (n_in >= 8): 0 D, 1 metric, 2 ||q||, 3 bmax = max ||b||, and of the mean-centred
@@ -416,6 +417,10 @@ int hb_index_rerank_copy_bytes(const hb_index_t* ix, int64_t* bytes);
 /* Work-list statistics of the last search: out[0]=workgroups, [1]=segments, [2]=slots, [3]=panel tiles,
  * [4]=max slots per query tile, [5]=query tiles, [6]=bank tiles, [7]=cluster shape (query ways * 16 + bank ways). */
 int hb_index_schedule_info(const hb_index_t* ix, int64_t out[8]);
+/* ... and how its clusters were dealt: out[0] = 1 when the leftover query tiles of a ragged last group were dealt as rows of other shapes
+ * (the filled list, hb_index_set_cluster_sharing), [1] = cluster ticks in which a member had no pair, [2] = all member ticks (0 without
+ * clusters), [3] = 1 when a filled list was asked for and refused because a query tile would have got more slots than the search takes. */
+int hb_last_schedule_fill(const hb_index_t* ix, int64_t out[4]);
 /* L2-sharing clusters of the kNN work list (speed only; results never depend on it): cluster_q x cluster_b workgroups
  * of one XCD walk (cluster_q query tiles) x (cluster_b interleaved bank tiles) in lockstep, so that one L2 fill serves
  * several workgroups.  0 x 0 = automatic (the fp16 candidate kernel of big searches: 8 x 1, or 4 x 2 / 2 x 2 when that
@@ -427,7 +432,10 @@ int hb_index_set_cluster(hb_index_t* ix, int cluster_q, int cluster_b, int sync_
 /* How a clustered work list is dealt (speed only): 2 = every run of one query group is split over ALL clusters of an XCD, so that
  * the XCD's workgroups keep re-reading the same cluster_q query tiles -- they stay in its L2 instead of being streamed through the
  * fabric once per pair (the clusters of an XCD need no sync among themselves for that); 1 = each cluster takes its own range of
- * the q-major unit list; 0 = automatic. */
+ * the q-major unit list; 0 = automatic; 3 = as 2, and the fp16 candidate pass's lists FILLED: the r = query tiles mod cluster_q tiles
+ * that a ragged last group leaves over are dealt as rows of other shapes with the same member count (r as a sum of powers of two; 2^i
+ * tiles x cluster_q cluster_b / 2^i consecutive bank tiles), so that no member idles for a whole row.  Automatic: the fp16 candidate
+ * pass shares and fills, the fp32 kernels do neither. */
 int hb_index_set_cluster_sharing(hb_index_t* ix, int mode);
 /* Soft-sync statistics of the last clustered search (synchronises the stream): out[0] = progress checks, [1] = waits
  * (re-polls while a member was behind), [2] = members that gave up waiting (bounded spin); zeros without clusters. */
@@ -450,6 +458,12 @@ int hb_schedule_plan_phased(int nqt, int nbt, int workgroups, int panel_tiles, i
 /* hb_schedule_plan / _phased for the work list of hb_index_set_cluster_sharing(ix, 2). */
 int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int panel_tiles, int d, int cluster_q, int cluster_b, int phased,
                             int* segs_out, int64_t max_segs, int64_t stats[8]);
+/* ... and for the FILLED list (mode 3): xcd_share as modes 2 / 1, xcd_w8 the eight XCD shares (NULL: equal), slot_limit the most slots
+ * a query tile may get (0: any number; beyond it the list of old is returned), the cuts as hb_schedule_plan_phased returns them (phased
+ * != 0; all three pointers may be NULL).  stats[0..7] as above, [8] = filled, [9] = idle member ticks, [10] = member ticks, [11] = refused. */
+int hb_schedule_plan_filled(int nqt, int nbt, int workgroups, int panel_tiles, int d, int cluster_q, int cluster_b, int phased, int xcd_share,
+                            const double* xcd_w8, int slot_limit, int* segs_out, int64_t max_segs, int64_t stats[12], int* clocks_out,
+                            int max_cuts, int* n_cuts, int* bounds_out);
 
 #include "hbird_hip_centre.h"
 #include "hbird_hip_select.h"

@@ -266,10 +266,22 @@ void hb_knn_plan_clusters(const hb_knn_plan_in& in, hb_knn_plan& p) {
     // clusters: 302.7 -> 291.5 ms and 0.97 -> 0.52 TB of L2-miss traffic per search (L2 hit rate 0.60 -> 0.78); the fp32 kernel's 2 x 4
     // clusters lose 1.6 % with it (2298 -> 2334 ms: 1600 slots instead of 592, and its 768 KiB query tiles do not stay in L2 beside
     // sixteen bank streams anyway: 1.95 -> 1.62 TB) -> off there (profiles/r04/xs_*.txt)
-    p.xs = cq * cb > 1 && (in.xcd_share == 2 || (in.xcd_share == 0 && f16));
+    p.xs = cq * cb > 1 && (in.xcd_share >= 2 || (in.xcd_share == 0 && f16));
+    // The filled dealing (hb_build_clustered): the leftover tiles of a ragged last query group as rows of other shapes, so that no member idles
+    // for a whole row -- the fp16 candidate kernel's lists only (automatic wherever its clusters are on and a tile is left over; mode 3 asks
+    // for it by name, modes 1 and 2 keep the lists of old).  The launcher adds the slot limit (hb_fill_slot_limit).
+    p.filled = f16 && cq * cb > 1 && nqt > cq && nqt % cq != 0 && (in.xcd_share == 3 || in.xcd_share == 0);
     // soft-sync lag in stages: the members stay inside the L2's reach (4 MiB per XCD: tens of fp32 k8 stages); 0 disables
     // the sync (the members then share only while they happen to run together: 36 % instead of 53 % L2 hits)
     p.lag = cq * cb > 1 ? (in.sync_lag >= 0 ? in.sync_lag : 16) : 0;
+}
+
+int hb_fill_slot_limit(int klw, int kc, bool phased) {
+    const long long lds = 48 * 1024 / 8;                                           // entries of a merge block's LDS
+    const long long w = std::max(1, klw), k = std::max(1, kc);
+    long long lim = lds / w >= 2 ? std::max<long long>(lds / w, (lds / w) * (lds / k)) : 2 * (lds / k);   // one level, or groups of lds / w slots x lds / k groups
+    if (phased) lim = std::min<long long>(lim, 144 * 1024 / 16 / w);               // one wave's share of the floor kernel's LDS, in pool entries
+    return (int)std::max<long long>(1, std::min<long long>(lim, 1 << 20));
 }
 
 void hb_knn_plan_kernel(const hb_knn_plan_in& in, int sched_G, hb_knn_plan& p) {
@@ -375,6 +387,7 @@ extern "C" int hb_knn_plan_replay(const int64_t* in, int n_in, int64_t* out, int
     out[0] = p.kc; out[1] = p.wide; out[2] = p.klw; out[3] = p.small_pools; out[4] = p.nqt; out[5] = p.nbt; out[6] = p.G; out[7] = p.fam; out[8] = p.balance;
     out[9] = p.cq; out[10] = p.cb; out[11] = p.auto_cluster; out[12] = p.panel; out[13] = p.phased; out[14] = p.xs; out[15] = p.lag; out[16] = p.kernel;
     out[17] = sched_G; out[18] = p.small;
+    if (n_out > 19) out[19] = p.filled;
     return 0;
 }
 // the fp16 screen's bounds as the re-rank kernels compile them (hbird_certificate.h), in float (include/hbird_hip.h: the slots)

@@ -133,6 +133,7 @@ struct hb_knn_plan {
     // hb_knn_plan_clusters
     int cq = 1, cb = 1; bool auto_cluster = false; int panel = 0;
     bool phased = false, xs = false; int lag = 0;
+    bool filled = false;          // the ragged last query group's tiles as rows of other shapes (hb_build_clustered)
     // hb_knn_plan_kernel
     bool small = false; int kernel = HB_KERNEL_LISTS;
 };
@@ -148,6 +149,10 @@ inline int hb_knn_workgroups(int force_G, int num_cu) { return force_G > 0 ? for
 void hb_knn_plan_shape(const hb_knn_plan_in& in, hb_knn_plan& p);
 void hb_knn_plan_clusters(const hb_knn_plan_in& in, hb_knn_plan& p);
 void hb_knn_plan_kernel(const hb_knn_plan_in& in, int sched_G, hb_knn_plan& p);
+// Most slots per query tile a filled list may have for a pool search of width klw that delivers kc entries: what pool_floor_kernel gathers
+// in its 144 KiB of LDS between two phases (beyond it the floors go through the merge, ten times the cost: knn_seed_floors), and what
+// launch_merge reaches in two levels of 48 KiB.
+int hb_fill_slot_limit(int klw, int kc, bool phased);
 
 // ---- the rungs of an excluding search (hb_index_search_excluding, hbird_exclude.hip) -----------------------------------------------------
 // The best k rows outside a group of at most gmax rows are the first k non-excluded entries of the best need = k + gmax rows.  Few queries

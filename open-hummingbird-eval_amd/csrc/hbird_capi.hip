@@ -211,7 +211,7 @@ extern "C" int hb_index_last_fp16_fallbacks(const hb_index_t* ix, int64_t* n) {
 
 extern "C" int hb_index_set_cluster_sharing(hb_index_t* ix, int mode) {
     if (!ix) return hb_fail("hb_index_set_cluster_sharing: NULL index handle");
-    if (mode < 0 || mode > 2) return hb_fail("hb_index_set_cluster_sharing: mode must be 0 (automatic), 1 (off) or 2 (on)");
+    if (mode < 0 || mode > 3) return hb_fail("hb_index_set_cluster_sharing: mode must be 0 (automatic), 1 (off), 2 (on) or 3 (on, filled)");
     ix->xcd_share = mode; ix->sched = hb_schedule(); ix->fp32_pinned = 1;
     return 0;
 }
@@ -347,6 +347,12 @@ extern "C" int hb_index_schedule_info(const hb_index_t* ix, int64_t out[8]) {
     const hb_schedule& s = ix->sched;
     out[0] = s.G; out[1] = (int64_t)s.segs.size(); out[2] = s.n_slots; out[3] = s.panel; out[4] = s.max_slots_per_qt;
     out[5] = s.nqt; out[6] = s.nbt; out[7] = s.cq * 16 + s.cb;
+    return 0;
+}
+extern "C" int hb_last_schedule_fill(const hb_index_t* ix, int64_t out[4]) {
+    if (!ix || !out) return hb_fail("hb_last_schedule_fill: NULL argument");
+    const hb_schedule& s = ix->sched;
+    out[0] = s.filled; out[1] = s.idle_member_ticks; out[2] = s.member_ticks; out[3] = s.fill_refused;
     return 0;
 }
 

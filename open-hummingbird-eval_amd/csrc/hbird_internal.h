@@ -57,7 +57,7 @@ struct hb_index {
     int force_G = 0, force_panel = 0;                    // test/tuning overrides
     int force_cq = 0, force_cb = 0;                      // cluster shape override (0 = automatic)
     int sync_lag = -1;                                   // soft-sync lag in stages (-1 = automatic, 0 = no sync)
-    int xcd_share = 0;                                   // clustered work lists: 0 = automatic, 1 = off, 2 = on (hb_index_set_cluster_sharing)
+    int xcd_share = 0;                                   // clustered work lists: 0 = automatic, 1 = off, 2 = on, 3 = on and filled (hb_index_set_cluster_sharing)
     // work shares per XCD group (blocks equal mod 8): hb_index_set_xcd_weights / calibrated from the workgroups' own time stamps.
     // Two families with shares of their own: [0] the fp32 kernels, [1] the fp16 candidate kernel (power-limited: its XCDs differ by other amounts)
     struct xcd_cal : hb_xcd_state {                      // (the decisions' state: hbird_calibrate.h; here the HIP side)

@@ -799,10 +799,12 @@ static int knn_get_work_list(hb_index* ix, int esc, const hb_knn_plan& p, hipStr
     hb_schedule& sc = esc == 0 ? ix->sched : ix->sched_esc;      // (the nested searches of uncertified queries keep a list of their own: the caller's stays cached)
     hb_dev<char>& sched_dev = esc == 0 ? ix->sched_dev : ix->sched_esc_dev;
     const int nqt = p.nqt, nbt = p.nbt, G = p.G;
+    // (a filled list's leftover query tiles get more slots: only as many as the floors between the phases and the merge take, hb_fill_slot_limit)
+    const int fill_limit = p.filled ? hb_fill_slot_limit(p.klw, p.kc, p.phased) : 0;
     const bool rebuilt = !(sc.nqt == nqt && sc.nbt == nbt && sc.panel == p.panel && sc.cq == p.cq && sc.cb == p.cb && sc.phased == p.phased &&
-                           sc.xcd_share == p.xs && (sc.G == G || (long long)nqt * nbt < G) &&
+                           sc.xcd_share == p.xs && sc.fill_asked == p.filled && sc.fill_slot_limit == fill_limit && (sc.G == G || (long long)nqt * nbt < G) &&
                            (sc.xcd_w.empty() ? std::equal(shares, shares + 8, equal_shares) : std::equal(shares, shares + 8, sc.xcd_w.begin())));
-    if (rebuilt) { hb_build_schedule(nqt, nbt, G, p.panel, sc, p.cq, p.cb, p.phased, p.xs, shares); ++ix->sched_builds; }
+    if (rebuilt) { hb_build_schedule(nqt, nbt, G, p.panel, sc, p.cq, p.cb, p.phased, p.xs, shares, p.filled, fill_limit); ++ix->sched_builds; }
     const struct { const void* data; size_t bytes; } part[6] = {{sc.segs.data(), sc.segs.size() * sizeof(hb_seg)}, {sc.wg_off.data(), sc.wg_off.size() * 4},
         {sc.qt_off.data(), sc.qt_off.size() * 4}, {sc.qt_slots.data(), sc.qt_slots.size() * 4}, {sc.wg_member.data(), sc.wg_member.size() * 4},
         {sc.phase_bounds.data(), sc.phase_bounds.size() * 4}};

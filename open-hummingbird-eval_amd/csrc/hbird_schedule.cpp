@@ -163,22 +163,45 @@ static long long hb_share_bound(long long W, const std::vector<double>& cum, int
     return std::min<long long>(W, std::max<long long>(0, (long long)std::floor((double)W * cum[i] + phi)));
 }
 
-static void hb_build_clustered(int nqt, int nbt, int G, int panel, int cq, int cb, hb_schedule& out, bool xcd_share) {
-    const int CS = cq * cb, NC = G / CS, NQG = (nqt + cq - 1) / cq;
+// Filled dealing (`filled`).  A ragged last query group (r = nqt mod cq tiles) leaves cq - r of a cluster's query ways without a pair
+// for all of its units, and their clock advances all the same: 2 of 88 member slots at 86 query tiles as 8 x 1 -- under XCD-level
+// sharing all of them on the last XCD, which then runs a quarter of its workgroups idle for most of every panel.  The filled list deals
+// the leftover tiles as rows of OTHER shapes with the same member count CS = cq cb: r is written as a sum of powers of two, and a part of
+// 2^i tiles becomes units of (2^i query tiles) x (CS / 2^i consecutive bank tiles) -- member m takes query way m / (CS / 2^i) and bank
+// way m mod (CS / 2^i), its segments stride CS / 2^i (8 x 1 and r = 6: a 4 x 2 row and a 2 x 4 row).  Every such row is a run of its own
+// in the q-major unit list, ceil(panel tiles / bank ways) units long, so only its partial last unit leaves members idle.  XCD ranges,
+// shares and the split of a run over an XCD's clusters are cut in units (ticks) as before: every XCD is dealt the same time.  The
+// leftover tiles get more slots (a tile of a 2 x 4 row: four per cluster); cq must be a power of two.
+struct hb_unit_row { int q0, qw, bw; };   // query tiles q0 .. q0 + qw - 1, bw bank ways (qw bw = CS)
+
+static void hb_build_clustered(int nqt, int nbt, int G, int panel, int cq, int cb, hb_schedule& out, bool xcd_share, bool filled) {
+    const int CS = cq * cb, NC = G / CS;
     out.cq = cq; out.cb = cb; out.n_clusters = NC; out.xcd_share = xcd_share;
+    std::vector<hb_unit_row> rows;                // the panel's unit list, q-major: full query groups, then the leftover tiles
+    for (int q = 0; q + cq <= nqt; q += cq) rows.push_back({q, cq, cb});
+    const int q_left = nqt / cq * cq, r = nqt - q_left;
+    filled = filled && r > 0 && nqt >= cq && (cq & (cq - 1)) == 0;      // (fewer tiles than query ways: the shape was the caller's to choose)
+    out.filled = filled;
+    if (r > 0 && !filled) rows.push_back({q_left, cq, cb});       // (its query ways beyond the last tile idle)
+    if (filled)
+        for (int part = cq >> 1, q = q_left; part >= 1; part >>= 1)
+            if (r & part) { rows.push_back({q, part, CS / part}); q += part; }
+    const int NR = (int)rows.size();
     std::vector<std::vector<hb_seg>> per_wg(G);   // logical workgroup = cluster * CS + member
     std::vector<int> slot_of((size_t)G * nqt, -1);   // (logical wg, q_tile) -> slot
     std::vector<std::vector<int>> slots_of_qt(nqt);
     std::vector<int> clock(NC, 0);                // cluster clock: tiles each member has been dealt (idle ones included)
-    // units [qg][j0, j0 + cnt) of the panel at bank tile b0 (pp tiles) -> the members of cluster c
-    auto deal = [&](int c, int b0, int pp, int qg, int j0, int cnt) {
+    // units [j0, j0 + cnt) of row rw of the panel at bank tile b0 (pp tiles) -> the members of cluster c
+    auto deal = [&](int c, int b0, int pp, const hb_unit_row& rw, int j0, int cnt) {
         for (int m = 0; m < CS; ++m) {
-            const int ia = m / cb, ib = m % cb, q = qg * cq + ia, w = c * CS + m;
+            const int ia = m / rw.bw, ib = m % rw.bw, q = rw.q0 + ia, w = c * CS + m;
             int n = cnt;
-            if ((j0 + cnt - 1) * cb + ib >= pp) --n;      // the partial last group has no tile for this member
-            if (q >= nqt || n <= 0) continue;             // idle for these units (its clock still advances)
+            if ((j0 + cnt - 1) * rw.bw + ib >= pp) --n;   // the partial last group has no tile for this member
+            out.member_ticks += cnt;
+            if (q >= nqt || n <= 0) { out.idle_member_ticks += cnt; continue; }   // idle for these units (its clock still advances)
+            out.idle_member_ticks += cnt - n;
             hb_seg sg;
-            sg.q_tile = q; sg.b_tile0 = b0 + j0 * cb + ib; sg.n_tiles = n; sg.stride = cb; sg.tile0 = clock[c]; sg.next_tile0 = 0;
+            sg.q_tile = q; sg.b_tile0 = b0 + j0 * rw.bw + ib; sg.n_tiles = n; sg.stride = rw.bw; sg.tile0 = clock[c]; sg.next_tile0 = 0;
             int& known = slot_of[(size_t)w * nqt + q];
             if (known < 0) {
                 sg.slot = out.n_slots++; sg.first = 1;
@@ -194,10 +217,18 @@ static void hb_build_clustered(int nqt, int nbt, int G, int panel, int cq, int c
     // uneven shares: per cluster (plain clustered list) or per XCD range (XCD-level query sharing)
     const std::vector<double> cum = (!out.xcd_w.empty() && !xcd_share && NC % 8 == 0) ? hb_cum_shares(NC, NC / 8, out.xcd_w) : std::vector<double>();
     const std::vector<double> cumx = (!out.xcd_w.empty() && xcd_share) ? hb_cum_shares(8, 1, out.xcd_w) : std::vector<double>();
+    std::vector<long long> first(NR + 1, 0);      // first[i]: the panel's units ahead of row i (a row's bank groups: the last one may be partial)
     for (int b0 = 0; b0 < nbt; b0 += panel) {
         const int pp = std::min(panel, nbt - b0);
-        const int UB = (pp + cb - 1) / cb;        // bank groups of the panel (the last one may be partial)
-        const long long U = (long long)NQG * UB;
+        for (int i = 0; i < NR; ++i) first[i + 1] = first[i] + (pp + rows[i].bw - 1) / rows[i].bw;
+        const long long U = first[NR];
+        // the run of one row that starts at unit e of the panel and ends before e1: its row, first unit and length
+        auto run_at = [&](long long e, long long e1, int* j0, int* len) {
+            const int i = (int)(std::upper_bound(first.begin(), first.end(), e) - first.begin()) - 1;
+            *j0 = (int)(e - first[i]);
+            *len = (int)std::min<long long>(first[i + 1] - e, e1 - e);
+            return i;
+        };
         if (xcd_share) {
             // XCD-level sharing of the QUERY tiles: the q-major unit list is cut into eight ranges, one per XCD, and every run of
             // one query group inside a range is split over ALL clusters of that XCD (contiguous bank sub-ranges), so that at any
@@ -209,11 +240,11 @@ static void hb_build_clustered(int nqt, int nbt, int G, int panel, int cq, int c
                 long long e1 = (U * (x + 1)) / 8;
                 if (!cumx.empty()) { e = hb_share_bound(U, cumx, x, 8, b0 / panel); e1 = hb_share_bound(U, cumx, x + 1, 8, b0 / panel); }
                 while (e < e1) {
-                    const int qg = (int)(e / UB), j0 = (int)(e % UB);
-                    const int L = (int)std::min<long long>(UB - j0, e1 - e);
-                    for (int i = 0; i < per_xcd_c; ++i) {
-                        const int a0 = (int)((long long)L * i / per_xcd_c), a1 = (int)((long long)L * (i + 1) / per_xcd_c);
-                        if (a1 > a0) deal(x * per_xcd_c + (i + rot) % per_xcd_c, b0, pp, qg, j0 + a0, a1 - a0);
+                    int j0, L;
+                    const int i = run_at(e, e1, &j0, &L);
+                    for (int ci = 0; ci < per_xcd_c; ++ci) {
+                        const int a0 = (int)((long long)L * ci / per_xcd_c), a1 = (int)((long long)L * (ci + 1) / per_xcd_c);
+                        if (a1 > a0) deal(x * per_xcd_c + (ci + rot) % per_xcd_c, b0, pp, rows[i], j0 + a0, a1 - a0);
                     }
                     ++rot;
                     e += L;
@@ -225,9 +256,9 @@ static void hb_build_clustered(int nqt, int nbt, int G, int panel, int cq, int c
             long long e0 = (U * c) / NC, e1 = (U * (c + 1)) / NC;
             if (!cum.empty()) { e0 = hb_share_bound(U, cum, c, NC, b0 / panel); e1 = hb_share_bound(U, cum, c + 1, NC, b0 / panel); }
             while (e0 < e1) {
-                const int qg = (int)(e0 / UB), j0 = (int)(e0 % UB);
-                const int cnt = (int)std::min<long long>(UB - j0, e1 - e0);
-                deal(c, b0, pp, qg, j0, cnt);
+                int j0, cnt;
+                const int i = run_at(e0, e1, &j0, &cnt);
+                deal(c, b0, pp, rows[i], j0, cnt);
                 e0 += cnt;
             }
         }
@@ -245,7 +276,22 @@ static void hb_build_clustered(int nqt, int nbt, int G, int panel, int cq, int c
     hb_finish_schedule(out, per_wg, logical_of_block, slots_of_qt);
 }
 
-void hb_build_schedule(int nqt, int nbt, int G, int panel, hb_schedule& out, int cq, int cb, bool phased, bool xcd_share, const double* xcd_w) {
+static void hb_build_schedule_as(int nqt, int nbt, int G, int panel, hb_schedule& out, int cq, int cb, bool phased, bool xcd_share, const double* xcd_w,
+                                 bool filled);
+
+// filled: the leftover query tiles of a clustered list's ragged last group as rows of other shapes (hb_build_clustered).  Their tiles get
+// more slots than the others; where a query tile would get more than fill_slot_limit (> 0) of them -- what the floors between two phases
+// gather in LDS, the merge's reach: the launcher knows -- the list of old is built instead (out.fill_refused).
+void hb_build_schedule(int nqt, int nbt, int G, int panel, hb_schedule& out, int cq, int cb, bool phased, bool xcd_share, const double* xcd_w, bool filled,
+                       int fill_slot_limit) {
+    hb_build_schedule_as(nqt, nbt, G, panel, out, cq, cb, phased, xcd_share, xcd_w, filled);
+    const bool refused = out.filled && fill_slot_limit > 0 && out.max_slots_per_qt > fill_slot_limit;
+    if (refused) hb_build_schedule_as(nqt, nbt, G, panel, out, cq, cb, phased, xcd_share, xcd_w, false);
+    out.fill_asked = filled; out.fill_slot_limit = fill_slot_limit; out.fill_refused = refused;
+}
+
+static void hb_build_schedule_as(int nqt, int nbt, int G, int panel, hb_schedule& out, int cq, int cb, bool phased, bool xcd_share, const double* xcd_w,
+                                 bool filled) {
     out = hb_schedule();
     out.nqt = nqt; out.nbt = nbt; out.panel = panel; out.phased = phased;
     if (xcd_w) {
@@ -275,7 +321,7 @@ void hb_build_schedule(int nqt, int nbt, int G, int panel, hb_schedule& out, int
         }
     }
     if (cq < 1 || cb < 1 || cq * cb > HB_CLUSTER_MAX || G % (8 * cq * cb) != 0) { cq = 1; cb = 1; }
-    if (cq * cb > 1) { hb_build_clustered(nqt, nbt, G, panel, cq, cb, out, xcd_share); return; }
+    if (cq * cb > 1) { hb_build_clustered(nqt, nbt, G, panel, cq, cb, out, xcd_share, filled); return; }
     std::vector<std::vector<hb_seg>> per_wg(G);
     std::vector<int> slot_of((size_t)G * nqt, -1);   // (wg, q_tile) -> slot
     std::vector<std::vector<int>> slots_of_qt(nqt);
@@ -329,7 +375,8 @@ void hb_build_schedule(int nqt, int nbt, int G, int panel, hb_schedule& out, int
 // Host-only: build the kNN work list for a (query tiles x bank tiles) grid without touching a GPU, for inspection
 // and tests.  segs_out receives up to max_segs rows of {block, q_tile, b_tile0, n_tiles, slot, first}.
 static int schedule_plan(int nqt, int nbt, int workgroups, int panel_tiles, int d, int cluster_q, int cluster_b, bool phased,
-                         int* segs_out, int64_t max_segs, int64_t stats[8], hb_schedule& sc, bool xcd_share = false, const double* xcd_w = nullptr) {
+                         int* segs_out, int64_t max_segs, int64_t stats[8], hb_schedule& sc, bool xcd_share = false, const double* xcd_w = nullptr,
+                         bool filled = false, int fill_slot_limit = 0) {
     if (!stats) return hb_fail("hb_schedule_plan: stats is NULL");
     if (nqt <= 0 || nbt <= 0 || workgroups <= 0 || d <= 0) return hb_fail("hb_schedule_plan: bad arguments");
     const int dp = (d + HB_KC - 1) / HB_KC * HB_KC;
@@ -338,7 +385,7 @@ static int schedule_plan(int nqt, int nbt, int workgroups, int panel_tiles, int 
     if (cq < 0 || cb < 0) hb_default_cluster(nqt, nbt, G, cq == -2, &cq, &cb);  // negative: the automatic shape (-1 fp16, -2 fp32 kernel)
     if (cq < 1 || cb < 1 || (long long)nqt * nbt < workgroups || cq * cb > HB_CLUSTER_MAX || G % (8 * cq * cb) != 0) { cq = 1; cb = 1; }
     const int panel = panel_tiles > 0 ? panel_tiles : hb_default_panel(nqt, G, (size_t)HB_BT * dp * 4, cq, cb);
-    hb_build_schedule(nqt, nbt, workgroups, panel, sc, cq, cb, phased, xcd_share && cq * cb > 1, xcd_w);
+    hb_build_schedule(nqt, nbt, workgroups, panel, sc, cq, cb, phased, xcd_share && cq * cb > 1, xcd_w, filled && cq * cb > 1, fill_slot_limit);
     stats[0] = sc.G; stats[1] = (int64_t)sc.segs.size(); stats[2] = sc.n_slots; stats[3] = sc.panel;
     stats[4] = sc.max_slots_per_qt; stats[5] = sc.nqt; stats[6] = sc.nbt; stats[7] = sc.cq * 16 + sc.cb;
     if (segs_out) {
@@ -389,5 +436,25 @@ extern "C" int hb_schedule_plan_shared(int nqt, int nbt, int workgroups, int pan
                                        int* segs_out, int64_t max_segs, int64_t stats[8]) {
     hb_schedule sc;
     return schedule_plan(nqt, nbt, workgroups, panel_tiles, d, cluster_q, cluster_b, phased != 0, segs_out, max_segs, stats, sc, true);
+}
+
+// The FILLED clustered list (hb_index_set_cluster_sharing(ix, 3), and the fp16 candidate pass's automatic choice): the arguments of
+// hb_schedule_plan_shared, whether the XCDs share their query tiles, shares (NULL: equal) and the slot limit (0: none) as the launcher passes
+// them, and the phase cuts as hb_schedule_plan_phased returns them.  stats[8..11]: filled, idle member ticks, member ticks, refused.
+extern "C" int hb_schedule_plan_filled(int nqt, int nbt, int workgroups, int panel_tiles, int d, int cluster_q, int cluster_b, int phased, int xcd_share,
+                                       const double* xcd_w8, int slot_limit, int* segs_out, int64_t max_segs, int64_t stats[12], int* clocks_out,
+                                       int max_cuts, int* n_cuts, int* bounds_out) {
+    if (slot_limit < 0) return hb_fail("hb_schedule_plan_filled: bad slot limit");
+    hb_schedule sc;
+    if (schedule_plan(nqt, nbt, workgroups, panel_tiles, d, cluster_q, cluster_b, phased != 0, segs_out, max_segs, stats, sc, xcd_share != 0, xcd_w8, true,
+                      slot_limit)) return -1;
+    stats[8] = sc.filled; stats[9] = sc.idle_member_ticks; stats[10] = sc.member_ticks; stats[11] = sc.fill_refused;
+    if (n_cuts) *n_cuts = (int)sc.phase_clock.size();
+    for (int p = 0; p < (int)sc.phase_clock.size() && p < max_cuts; ++p) {
+        if (clocks_out) clocks_out[p] = sc.phase_clock[p];
+        if (bounds_out)
+            for (int b = 0; b < sc.G; ++b) bounds_out[(size_t)p * sc.G + b] = sc.phase_bounds[(size_t)p * sc.G + b] - sc.wg_off[b];
+    }
+    return 0;
 }
 

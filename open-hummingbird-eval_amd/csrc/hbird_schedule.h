@@ -44,10 +44,17 @@ struct hb_schedule {
     int n_slots = 0;
     int max_slots_per_qt = 0;
     int n_clusters = 0;
+    // clustered lists: the leftover query tiles of a ragged last group dealt as rows of other shapes (hb_build_clustered)
+    bool fill_asked = false;         // what the caller asked for (the key of a cached list) ...
+    int fill_slot_limit = 0;         // ... with at most this many slots per query tile (0: any number)
+    bool filled = false;             // ... and what it got: false where no tile was left over, or the filled list broke the limit
+    bool fill_refused = false;       // (the latter)
+    long long member_ticks = 0;      // cluster ticks x members, and those of them without a pair (a query way beyond the last tile, a bank
+    long long idle_member_ticks = 0; // way beyond the panel's end)
 };
 
 void hb_build_schedule(int nqt, int nbt, int G, int panel_tiles, hb_schedule& out, int cq = 1, int cb = 1, bool phased = false,
-                       bool xcd_share = false, const double* xcd_w = nullptr);
+                       bool xcd_share = false, const double* xcd_w = nullptr, bool filled = false, int fill_slot_limit = 0);
 int hb_default_panel(int nqt, int G, size_t tile_bytes, int cq = 1, int cb = 1);
 // automatic cluster shape for a search (1 x 1 when clusters do not apply)
 void hb_default_cluster(int nqt, int nbt, int G, bool fp32_kernel, int* cq, int* cb);

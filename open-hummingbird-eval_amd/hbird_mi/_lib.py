@@ -86,6 +86,9 @@ SIGNATURES = {
     "hb_schedule_plan_phased": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, POINTER(c_int64),
                                         c_void_p, c_int, POINTER(c_int), c_void_p]),
     "hb_schedule_plan_shared": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, POINTER(c_int64)]),
+    "hb_schedule_plan_filled": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                        POINTER(c_int64), c_void_p, c_int, POINTER(c_int), c_void_p]),
+    "hb_last_schedule_fill": (c_int, [c_void_p, POINTER(c_int64)]),
     "hb_index_set_cluster": (c_int, [c_void_p, c_int, c_int, c_int]),
     "hb_index_set_cluster_sharing": (c_int, [c_void_p, c_int]),
     "hb_index_set_label_denominator": (c_int, [c_void_p, c_int]),

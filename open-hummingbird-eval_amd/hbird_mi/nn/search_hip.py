@@ -779,7 +779,8 @@ class HipFlatIndex:
         _lib.check(_lib.lib().hb_index_set_cluster(self._h, int(cluster_q), int(cluster_b), int(sync_lag)))
 
     def set_cluster_sharing(self, mode: int = 0):
-        """How a clustered work list is dealt (speed only): 0 automatic, 1 per-cluster ranges, 2 XCD-level query-tile sharing."""
+        """How a clustered work list is dealt (speed only): 0 automatic, 1 per-cluster ranges, 2 XCD-level query-tile sharing, 3 the same with
+        the leftover query tiles of a ragged last group dealt as rows of other shapes (the filled list; fp16 candidate pass)."""
         _lib.check(_lib.lib().hb_index_set_cluster_sharing(self._h, int(mode)))
 
     def cluster_stats(self) -> dict:
@@ -793,6 +794,11 @@ class HipFlatIndex:
         keys = ["workgroups", "segments", "slots", "panel_tiles", "max_slots_per_qtile", "query_tiles", "bank_tiles"]
         d = dict(zip(keys, list(out)[:7]))
         d["cluster"] = [int(out[7]) // 16, int(out[7]) % 16]
+        fill = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.lib().hb_last_schedule_fill(self._h, fill))
+        d["filled"] = int(fill[0]); d["idle_member_ticks"] = int(fill[1]); d["member_ticks"] = int(fill[2])
+        if fill[3]:
+            d["fill_refused"] = 1      # (a filled list was asked for and would have broken the slot limit: the list of old ran)
         return d
 
 
