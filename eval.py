@@ -8,6 +8,8 @@
   python eval.py --task depth-grid --grid-k 1 5 30 --grid-beta 0.02 0.1 --bootstrap 1000 --dataset-name synthetic-depth --data-dir "" \\
       --d-model 3 --patch-size 8 --input-size 64                                                                      # ... over a (k, beta) grid
   python eval.py --task knn-classify --dataset-name synthetic-classify --data-dir "" --d-model 3 --patch-size 8 --input-size 32   # image-level k-NN
+  python eval.py --task linear-classify --probe-l2 1e-2 1e-3 --dataset-name synthetic-classify --data-dir "" --d-model 3 --patch-size 8 \\
+      --input-size 32                                                                                                 # ... and the linear probe
 """
 from __future__ import annotations
 
@@ -38,6 +40,13 @@ def _positive_float(v: str) -> float:
     f = float(v)
     if not (f > 0 and f != float("inf")):
         raise argparse.ArgumentTypeError("must be a finite positive number")
+    return f
+
+
+def _non_negative_float(v: str) -> float:
+    f = float(v)
+    if not (f >= 0 and f != float("inf")):
+        raise argparse.ArgumentTypeError("must be a finite non-negative number")
     return f
 
 
@@ -163,7 +172,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--linear-probe-l2", type=float, default=1e-3, metavar="X", help="l2 weight of the fit (a definition, not tuned on real data)")
     p.add_argument("--linear-probe-gtol", type=float, default=1e-5, metavar="X", help="the fit stops once the gradient's largest entry is this small")
     p.add_argument("--linear-probe-iters", type=int, default=200, metavar="N", help="iteration limit of the fit")
-    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid", "video", "knn-classify"], default="segmentation",
+    p.add_argument("--task", choices=["segmentation", "depth", "depth-grid", "video", "knn-classify", "linear-classify"], default="segmentation",
                    help="knn-classify: the weighted k-NN classifier on image-level features (hbird_mi.classify; not in the reference) -- "
                         "--dataset-name synthetic-classify | class-folder (train/<class>/*, val/<class>/* under --data-dir), --grid-k (default 10 20 "
                         "100 200) x --grid-temperature (default 0.07) from one search per batch; the result JSON carries top1, top5 and "
@@ -190,6 +199,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--task knn-classify: the temperatures of the vote's weights exp(similarity / T) (default 0.07)")
     p.add_argument("--top-n", type=_positive_int, default=None, metavar="N",
                    help="--task knn-classify: predictions ranked per image, at most 8 (default 5: the JSON's top5 is the label among the first N)")
+    p.add_argument("--probe-l2", type=_non_negative_float, nargs="+", default=None, metavar="L",
+                   help="--task linear-classify: the l2 weights of the softmax head, one fit each, at most 16 (default 1e-3: a definition, not tuned)")
     p.add_argument("--no-channel-norm", action="store_true", help="--task video: argmax without the per-channel min-max normalisation of the label maps")
     p.add_argument("--ignore-index", type=int, default=255)
     p.add_argument("--train-fs", dest="train_fs_path", type=str, default=None)
@@ -460,6 +471,55 @@ def main_knn_classify(parser, args) -> None:
             json.dump(summary, f)
 
 
+def probe_key(l2: float) -> str:
+    """How a configuration of --task linear-classify is keyed in the result JSON."""
+    return f"l2={float(l2)!r}"
+
+
+def main_linear_classify(parser, args) -> None:
+    """--task linear-classify: hbird_mi.classify.hbird_linear_classification and its JSON."""
+    if args.memory_sizes:
+        parser.error("--memory-sizes is not available with --task linear-classify: the bank holds one row per image (label subsets: "
+                     "HbirdKnnClassification.memory_view)")
+    for name in KNN_EXCLUDES + ("grid_k", "leave_one_out", "leave_one_out_images"):
+        if getattr(args, name):
+            parser.error(f"--{name.replace('_', '-').replace('-path', '')} is not available with --task linear-classify")
+    if not isinstance(args.n_neighbours, _DefaultInt):
+        parser.error("--n-neighbours is not available with --task linear-classify")
+    if args.nn_method != "hip":
+        parser.error("--nn-method is not available with --task linear-classify (the head is fitted on the HIP index)")
+    if args.target_grid != 1:
+        parser.error("--target-grid is not available with --task linear-classify")
+    top_n = 5 if args.top_n is None else args.top_n
+    if top_n > 8:
+        parser.error("--top-n: at most 8 predictions are ranked per image")
+    l2s = args.probe_l2 or [1e-3]
+    if len(l2s) > 16 or len(set(l2s)) != len(l2s):
+        parser.error("--probe-l2: 1 to 16 different values")
+    logging.basicConfig(level=getattr(logging, args.log_level), force=True)
+    set_seed(args.seed)
+    from hbird_mi import classify as hclassify
+    model = build_model(args)
+    t0 = time.time()
+    res = hclassify.hbird_linear_classification(model, d_model=args.d_model, patch_size=args.patch_size, dataset_name=args.dataset_name,
+                                                data_dir=args.data_dir, batch_size=args.batch_size, input_size=args.input_size,
+                                                augmentation_epoch=args.augmentation_epoch, device=args.device, l2s=l2s,
+                                                gtol=args.linear_probe_gtol, max_iter=args.linear_probe_iters, topn=top_n,
+                                                nn_params=parse_nn_params(args.nn_param), ftr_extr_fn=default_ftr_extr_fn,
+                                                num_workers=args.num_workers)
+    best, best_top1 = res.best() if res.n else (None, float("nan"))
+    summary = {"task": "linear-classify", "top1": {probe_key(v): float(res.top1[v]) for v in res.l2s},
+               f"top{top_n}": {probe_key(v): float(res.topn[v]) for v in res.l2s},
+               "mean_per_class": {probe_key(v): float(res.mean_per_class[v]) for v in res.l2s},
+               "fits": {probe_key(v): res.fits[v] for v in res.l2s},
+               "best": None if best is None else {"key": probe_key(best), "top1": float(best_top1)}, "n": res.n, "skipped": res.skipped,
+               "top_n": top_n, "seconds": round(time.time() - t0, 3), "dataset": args.dataset_name, **hclassify.last_run_info}
+    print(json.dumps(summary))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f)
+
+
 def main(argv: Optional[List[str]] = None) -> None:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -469,7 +529,18 @@ def main(argv: Optional[List[str]] = None) -> None:
         for name, default in VIDEO_ONLY.items():
             if getattr(args, name) != default:
                 parser.error(f"--{name.replace('_', '-')} needs --task video")
+        if args.probe_l2 is not None:
+            parser.error("--probe-l2 needs --task linear-classify")
         return main_knn_classify(parser, args)
+    if args.task == "linear-classify":
+        for name, default in VIDEO_ONLY.items():
+            if getattr(args, name) != default:
+                parser.error(f"--{name.replace('_', '-')} needs --task video")
+        if args.grid_temperature is not None:
+            parser.error("--grid-temperature needs --task knn-classify")
+        return main_linear_classify(parser, args)
+    if args.probe_l2 is not None:
+        parser.error("--probe-l2 needs --task linear-classify")
     for name, default in KNN_ONLY.items():
         if getattr(args, name) != default:
             parser.error(f"--{name.replace('_', '-')} needs --task knn-classify")

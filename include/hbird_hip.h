@@ -474,6 +474,7 @@ int hb_schedule_plan_filled(int nqt, int nbt, int workgroups, int panel_tiles, i
 #include "hbird_hip_kmeans.h"
 #include "hbird_hip_linprobe.h"
 #include "hbird_hip_depth.h"
+#include "hbird_hip_linprobe_class.h"
 
 #ifdef __cplusplus
 }

@@ -10,20 +10,20 @@
 // linprobe_stage_rows_kernel copies a chunk's rows to row-major [1, x] (skipped and padding rows as zeros) and linprobe_backward_kernel
 // contracts residuals and staged rows over the ROW index with the same MFMA: one wave = (segment) x (a 32-column tile of [1, x]) x (two class
 // tiles), one fmaf chain over the segment's ascending rows per output, partials to HBM; linprobe_reduce_kernel adds them in float64 in segment order.
-// No floating-point atomic appears in this unit.
+// Beyond eight class tiles (the image-level probe, hbird_linprobe_class.hip) linprobe_backward_wide_kernel takes four class tiles x two
+// column tiles per wave: the same chains, fewer loads per MFMA.  The kernels that take any class-tile count are reached by both units
+// through the host launchers of hbird_linprobe_dev.h.  No floating-point atomic appears in this unit.
 #include "../../include/hbird_hip.h"
 #include "hbird_internal.h"
 #include "hbird_k5_dev.h"
+#include "hbird_linprobe_dev.h"
 #include <algorithm>
 
-#define LP_THREADS 512
-#define LP_ROWS 256                  // rows of a forward workgroup (eight waves x one 32-row tile)
-#define LP_GC 8                      // column groups of Wb staged in LDS at a time (CT KiB each)
 #define LP_BWD_CTW 2                 // class tiles of a backward wave
 #define LP_BWD_STAGE 16              // row pairs of one stage of its loads (two stages in flight)
-#define LP_TREE_BLOCKS 256
-
-typedef float lp_f32x16 __attribute__((ext_vector_type(16)));
+#define LP_BWD_WIDE_CTW 4            // the wide form beyond eight class tiles (cp > 256): class tiles x column tiles of a wave,
+#define LP_BWD_WIDE_DTW 2            //   eight accumulators fed by six loads per row pair
+#define LP_BWD_WIDE_STAGE 8
 
 struct lp_fwd_args {
     const float* tiles; int g8; int64_t ntotal;
@@ -246,6 +246,64 @@ __global__ __launch_bounds__(64) void linprobe_backward_kernel(const float* __re
     }
 }
 
+// The same chains with a wave tile of CTW class tiles x DTW column tiles: every output is still its own fmaf chain over the segment's ascending
+// rows, so the bits are those of linprobe_backward_kernel; CTW + DTW loads feed CTW * DTW MFMAs per row pair.
+template <int CTW, int DTW>
+__global__ __launch_bounds__(64) void linprobe_backward_wide_kernel(const float* __restrict__ resid, int cp, const float* __restrict__ X, int xs,
+                                                                    int64_t seg_rows, int64_t rows_pad, float* __restrict__ partial) {
+    const int lane = threadIdx.x, h = lane >> 5, i = lane & 31;
+    const int d0 = blockIdx.x * DTW, nd = min(DTW, xs / 32 - d0), t0 = blockIdx.z * CTW, nt = min(CTW, cp / 32 - t0);
+    const int64_t seg = blockIdx.y, r0 = seg * seg_rows, r1 = std::min<int64_t>(rows_pad, r0 + seg_rows);      // (both multiples of 256)
+    lp_f32x16 acc[CTW][DTW];
+#pragma unroll
+    for (int t = 0; t < CTW; ++t)
+#pragma unroll
+        for (int u = 0; u < DTW; ++u)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[t][u][v] = 0.0f;
+    const float* xp = X + d0 * 32 + i;
+    const float* rp = resid + t0 * 32 + i;
+    float ra[2][LP_BWD_WIDE_STAGE][CTW], xb[2][LP_BWD_WIDE_STAGE][DTW];
+    auto load = [&](int b, int64_t r) {
+#pragma unroll
+        for (int p = 0; p < LP_BWD_WIDE_STAGE; ++p) {
+            const int64_t row = r + 2 * p + h;
+#pragma unroll
+            for (int u = 0; u < DTW; ++u) xb[b][p][u] = u < nd ? xp[row * (int64_t)xs + u * 32] : 0.0f;
+#pragma unroll
+            for (int t = 0; t < CTW; ++t) ra[b][p][t] = t < nt ? rp[row * (int64_t)cp + t * 32] : 0.0f;
+        }
+    };
+    auto compute = [&](int b) {
+#pragma unroll
+        for (int p = 0; p < LP_BWD_WIDE_STAGE; ++p)
+#pragma unroll
+            for (int t = 0; t < CTW; ++t)
+#pragma unroll
+                for (int u = 0; u < DTW; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[b][p][t], xb[b][p][u], acc[t][u], 0, 0, 0);
+    };
+    load(0, r0);
+    for (int64_t r = r0; r < r1; r += 4 * LP_BWD_WIDE_STAGE) {      // (256 rows are a whole number of double stages)
+        load(1, r + 2 * LP_BWD_WIDE_STAGE);
+        compute(0);
+        if (r + 4 * LP_BWD_WIDE_STAGE < r1) load(0, r + 4 * LP_BWD_WIDE_STAGE);
+        compute(1);
+    }
+#pragma unroll
+    for (int t = 0; t < CTW; ++t) {
+        if (t >= nt) break;
+#pragma unroll
+        for (int u = 0; u < DTW; ++u) {
+            if (u >= nd) break;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int c = (t0 + t) * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+                partial[(seg * cp + c) * (int64_t)xs + (d0 + u) * 32 + i] = acc[t][u][v];
+            }
+        }
+    }
+}
+
 // acc[c][j] += the chunk's segment partials in float64, ascending segments
 __global__ __launch_bounds__(256) void linprobe_reduce_kernel(const float* __restrict__ partial, int nseg, int cp, int xs, int C, int d1,
                                                               double* __restrict__ acc) {
@@ -319,8 +377,14 @@ int lp_forward(const lp_fwd_args& a, int ct, int64_t rows_pad, hipStream_t s) {
     return 0;
 }
 
-int lp_backward(int ct, const float* resid, const float* X, int xs, int64_t seg_rows, int64_t rows_pad, int nseg, float* partial, hipStream_t s) {
-    if (ct == 1)
+}  // namespace
+
+int hb_lp_backward(int ct, const float* resid, const float* X, int xs, int64_t seg_rows, int64_t rows_pad, int nseg, float* partial, hipStream_t s) {
+    if (ct > 8)      // (measured against linprobe_backward_kernel<2> at C = 1000: profiles/r36/README.md)
+        linprobe_backward_wide_kernel<LP_BWD_WIDE_CTW, LP_BWD_WIDE_DTW><<<dim3((unsigned)((xs / 32 + LP_BWD_WIDE_DTW - 1) / LP_BWD_WIDE_DTW), (unsigned)nseg,
+                                                                              (unsigned)((ct + LP_BWD_WIDE_CTW - 1) / LP_BWD_WIDE_CTW)), dim3(64), 0, s>>>(
+            resid, ct * 32, X, xs, seg_rows, rows_pad, partial);
+    else if (ct == 1)
         linprobe_backward_kernel<1><<<dim3((unsigned)(xs / 32), (unsigned)nseg, 1), dim3(64), 0, s>>>(resid, 32, X, xs, seg_rows, rows_pad, partial);
     else
         linprobe_backward_kernel<LP_BWD_CTW><<<dim3((unsigned)(xs / 32), (unsigned)nseg, (unsigned)((ct + LP_BWD_CTW - 1) / LP_BWD_CTW)), dim3(64), 0, s>>>(
@@ -329,20 +393,36 @@ int lp_backward(int ct, const float* resid, const float* X, int xs, int64_t seg_
     return 0;
 }
 
-// the parameters in the kernels' form
-struct lp_params {
-    hb_dev<float> wt, bias;
-    int ct = 0;
-    int make(const hb_index* ix, const float* Wb, int C, hipStream_t s) {
-        ct = (C + 31) / 32;
-        const int64_t total = (int64_t)ct * ix->g8 * HB_BLK;
-        if (wt.ensure((size_t)total * 4, HB_GROW_EXACT) || bias.ensure((size_t)ct * 32 * 4, HB_GROW_EXACT)) return -1;
-        linprobe_retile_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(Wb, C, ix->d, ix->g8, ct, wt, bias);
-        HB_HIP(hipGetLastError());
-        return 0;
-    }
-};
-}  // namespace
+int lp_params::make(const hb_index* ix, const float* Wb, int C, hipStream_t s) {
+    ct = (C + 31) / 32;
+    const int64_t total = (int64_t)ct * ix->g8 * HB_BLK;
+    if (wt.ensure((size_t)total * 4, HB_GROW_EXACT) || bias.ensure((size_t)ct * 32 * 4, HB_GROW_EXACT)) return -1;
+    linprobe_retile_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(Wb, C, ix->d, ix->g8, ct, wt, bias);
+    HB_HIP(hipGetLastError());
+    return 0;
+}
+
+int hb_lp_stage_rows(const hb_index* ix, int64_t row0, int64_t rows_pad, const unsigned char* skip, float* X, int xs, hipStream_t s) {
+    linprobe_stage_rows_kernel<<<dim3((unsigned)(rows_pad / 32)), dim3(256), 0, s>>>(ix->tiles, ix->g8, ix->d, row0, skip, X, xs);
+    if (hipGetLastError() != hipSuccess) return hb_fail("linprobe: linprobe_stage_rows_kernel did not launch");
+    return 0;
+}
+int hb_lp_reduce(const float* partial, int nseg, int cp, int xs, int C, int d1, double* grad, hipStream_t s) {
+    linprobe_reduce_kernel<<<dim3((unsigned)(((int64_t)C * d1 + 255) / 256)), dim3(256), 0, s>>>(partial, nseg, cp, xs, C, d1, grad);
+    if (hipGetLastError() != hipSuccess) return hb_fail("linprobe: linprobe_reduce_kernel did not launch");
+    return 0;
+}
+int hb_lp_loss_tree(const float* rowloss, const unsigned char* skip, int64_t n, double* tree, const float* Wb, int64_t total, double* scal, hipStream_t s) {
+    linprobe_loss_partial_kernel<<<dim3(LP_TREE_BLOCKS), dim3(256), 0, s>>>(rowloss, skip, n, tree);
+    linprobe_loss_final_kernel<<<dim3(1), dim3(256), 0, s>>>(tree, Wb, total, scal);
+    if (hipGetLastError() != hipSuccess) return hb_fail("linprobe: the loss kernels did not launch");
+    return 0;
+}
+int hb_lp_finish(double* grad, const float* Wb, int64_t total, double n, double l2, hipStream_t s) {
+    linprobe_finish_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(grad, Wb, total, n, l2);
+    HB_HIP(hipGetLastError());
+    return 0;
+}
 
 extern "C" int hb_linprobe_partition(int64_t ntotal, int64_t* seg_rows, int* nseg) {
     if (!seg_rows || !nseg) return hb_fail("hb_linprobe_partition: NULL pointer");
@@ -359,6 +439,7 @@ extern "C" int hb_linprobe_set_workspace(int64_t bytes) {
     g_linprobe_workspace = bytes;
     return 0;
 }
+int64_t hb_lp_workspace() { return g_linprobe_workspace > 0 ? g_linprobe_workspace : (int64_t)HB_LINPROBE_WORKSPACE; }
 
 extern "C" int hb_linprobe_logits(hb_index_t* ix, const float* Wb, int C, float* out) {
     if (!ix) return hb_fail("hb_linprobe_logits: NULL index handle");
@@ -402,7 +483,7 @@ extern "C" int hb_linprobe_loss_grad(hb_index_t* bank, const float* Wb, int C, d
     const int cp = par.ct * 32;
     // the bank in row chunks of whole segments: residuals [rows][cp], staged rows [rows][xs], segment partials [segments][cp][xs]
     const int64_t seg_bytes = seg_rows * (int64_t)(cp + xs) * 4;
-    const int64_t workspace = g_linprobe_workspace > 0 ? g_linprobe_workspace : (int64_t)HB_LINPROBE_WORKSPACE;
+    const int64_t workspace = hb_lp_workspace();
     const int chunk_segs = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, workspace / seg_bytes));
     const int64_t chunk_rows = (int64_t)chunk_segs * seg_rows, npad = (n + LP_ROWS - 1) / LP_ROWS * LP_ROWS;
     const int64_t chunk_pad = std::min(chunk_rows, npad);
@@ -424,26 +505,20 @@ extern "C" int hb_linprobe_loss_grad(hb_index_t* bank, const float* Wb, int C, d
         a.row0 = (int64_t)seg0 * seg_rows;
         const int64_t rows = std::min(n, a.row0 + (int64_t)segs * seg_rows) - a.row0, rows_pad = (rows + LP_ROWS - 1) / LP_ROWS * LP_ROWS;
         if (lp_forward(a, par.ct, rows_pad, s)) { rc = -1; break; }
-        linprobe_stage_rows_kernel<<<dim3((unsigned)(rows_pad / 32)), dim3(256), 0, s>>>(bank->tiles, bank->g8, d, a.row0, skip, X, xs);
-        if (hipGetLastError() != hipSuccess) { rc = hb_fail("hb_linprobe_loss_grad: linprobe_stage_rows_kernel did not launch"); break; }
-        if (lp_backward(par.ct, resid, X, xs, seg_rows, rows_pad, segs, partial, s)) { rc = -1; break; }
-        linprobe_reduce_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(partial, segs, cp, xs, C, d1, grad);
-        if (hipGetLastError() != hipSuccess) { rc = hb_fail("hb_linprobe_loss_grad: linprobe_reduce_kernel did not launch"); break; }
+        if (hb_lp_stage_rows(bank, a.row0, rows_pad, skip, X, xs, s) || hb_lp_backward(par.ct, resid, X, xs, seg_rows, rows_pad, segs, partial, s)
+            || hb_lp_reduce(partial, segs, cp, xs, C, d1, grad, s)) { rc = -1; break; }
     }
     double h[3] = {0.0, 0.0, 0.0};
     if (!rc) {
-        linprobe_loss_partial_kernel<<<dim3(LP_TREE_BLOCKS), dim3(256), 0, s>>>(rowloss, skip, n, tree);
-        linprobe_loss_final_kernel<<<dim3(1), dim3(256), 0, s>>>(tree, Wb, total, scal);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess)
-            rc = hb_fail("hb_linprobe_loss_grad: the loss kernels did not launch");
+        if (hb_lp_loss_tree(rowloss, skip, n, tree, Wb, total, scal, s)) rc = -1;
+        else if (hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) rc = hb_fail("hb_linprobe_loss_grad: the loss did not come back");
     }
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = hb_fail("hb_linprobe_loss_grad: the stream failed");
     if (rc) return rc;
     *used_host = (int64_t)h[1];
     if (h[1] < 1.0) return hb_fail("hb_linprobe_loss_grad: every row of the bank holds a non-finite component");
     *loss_host = h[0] / h[1] + 0.5 * l2 * h[2];
-    linprobe_finish_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(grad, Wb, total, h[1], l2);
-    HB_HIP(hipGetLastError());
+    if (hb_lp_finish(grad, Wb, total, h[1], l2, s)) return -1;
     HB_HIP(hipStreamSynchronize(s));      // (the workspace goes with the call)
     return 0;
 }

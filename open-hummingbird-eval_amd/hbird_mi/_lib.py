@@ -254,6 +254,15 @@ SIGNATURES_VOTE = {
     "hb_vote_counts": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# ... and include/hbird_hip_linprobe_class.h (the image-level linear probe, csrc/hbird_linprobe_class.hip: a softmax head's logits, loss and gradient
+# on one class id per bank row for 1000 classes and more, the top-n of a logit table), which hbird_hip.h includes
+LINPROBE_CLASS_MAX_C = 16384     # HB_LINPROBE_CLASS_MAX_C: the largest C accepted; nothing is sized by it
+SIGNATURES_LINPROBE_CLASS = {
+    "hb_linprobe_class_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "hb_linprobe_class_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, POINTER(c_double), c_void_p, POINTER(c_int64), c_void_p]),
+    "hb_logits_topn": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+}
+
 
 class HbirdHipError(RuntimeError):
     pass
@@ -275,7 +284,7 @@ def lib() -> ctypes.CDLL:
         # HBIRD_PLAN_ONLY=1 (tests/test_sanitizers_cpu.py): LIB_PATH names the host-only sanitizer build of the work-list planner,
         # which exports the hb_schedule_plan* / hb_calibration_* entry points and hb_last_error only
         plan_only = os.environ.get("HBIRD_PLAN_ONLY") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()) + list(SIGNATURES_PROPAGATE.items()) + list(SIGNATURES_VOTE.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CENTRE.items()) + list(SIGNATURES_SELECT.items()) + list(SIGNATURES_GRID.items()) + list(SIGNATURES_EXCLUDE.items()) + list(SIGNATURES_SCREEN.items()) + list(SIGNATURES_EXCLUDE_SCREEN.items()) + list(SIGNATURES_BOOTSTRAP.items()) + list(SIGNATURES_KMEANS.items()) + list(SIGNATURES_LINPROBE.items()) + list(SIGNATURES_DEPTH.items()) + list(SIGNATURES_DEPTH_GRID.items()) + list(SIGNATURES_PROPAGATE.items()) + list(SIGNATURES_VOTE.items()) + list(SIGNATURES_LINPROBE_CLASS.items()):
             if plan_only and not (name.startswith("hb_schedule_plan") or name.startswith("hb_calibration_") or name in ("hb_f16_adapt_replay", "hb_exact_screen_replay", "hb_rerank_copy_replay", "hb_knn_plan_replay", "hb_certificate_bound_replay", "hb_exclude_plan_replay") or name == "hb_last_error"):
                 continue
             fn = getattr(L, name)  # AttributeError here = header and library disagree

@@ -7,6 +7,10 @@ tensor (one integer per bank row, no dense label rows).  Per validation batch: t
 `index.search` at the largest k, then `ops.knn_vote` + `ops.vote_counts` once per launch of `grid_plan(ks, temperatures)` -- a query's best k
 are the first k of its best k_max and T only enters after the search, so one search serves the whole (k, T) table.  Only the count tables
 reach the host.  One process, one device.
+
+The linear-probe column stands beside it (`fit_linear_probe`, `evaluate_linear_probe`, `hbird_linear_classification`): a softmax head on the
+same bank rows and class ids, include/hbird_hip_linprobe_class.h -- again this engine's own definition (L2-penalised, full-batch L-BFGS, not
+DINO's SGD recipe with batch norm), with no accuracy held to a published one.
 """
 from __future__ import annotations
 
@@ -48,6 +52,28 @@ class KnnClassMetrics:
         if not self.n:
             raise ValueError("best: no labelled query was scored")
         key = max(self.configs, key=lambda c: (self.top1[c], -self.configs.index(c)))
+        return key, self.top1[key]
+
+
+class LinearClassMetrics:
+    """The accuracies of the image-level linear probe, one configuration per l2: `top1`, `topn` and `mean_per_class` are dicts keyed by l2
+    (`KnnClassMetrics`' definitions on the same count tables); `n` labelled queries were scored, `skipped` unlabelled ones (class id -1) were
+    not -- they are counted, never dropped silently; `fits[l2]` = dict(state, n_iter, rows_used, rows_skipped) of that l2's fit.  `best()` ->
+    (l2, top1) of the best top-1, the first such l2 in the order given on a tie.  With n == 0 every figure is NaN."""
+
+    def __init__(self, l2s, counts, class_counts, n: int, skipped: int, fits):
+        table = KnnClassMetrics([(i, 1.0) for i in range(len(l2s))], counts, class_counts, n, skipped)
+        self.l2s = [float(v) for v in l2s]
+        self.counts, self.class_counts, self.n, self.skipped, self.n_top = table.counts, table.class_counts, table.n, table.skipped, table.n_top
+        self.top1 = {v: table.top1[(i, 1.0)] for i, v in enumerate(self.l2s)}
+        self.topn = {v: table.topn[(i, 1.0)] for i, v in enumerate(self.l2s)}
+        self.mean_per_class = {v: table.mean_per_class[(i, 1.0)] for i, v in enumerate(self.l2s)}
+        self.fits = {float(k): dict(v) for k, v in fits.items()}
+
+    def best(self) -> Tuple[float, float]:
+        if not self.n:
+            raise ValueError("best: no labelled query was scored")
+        key = max(self.l2s, key=lambda v: (self.top1[v], -self.l2s.index(v)))
         return key, self.top1[key]
 
 
@@ -295,6 +321,56 @@ class HbirdKnnClassification:
         limit = self.n_images if max_images is None else min(self.n_images, int(max_images))
         return self._pass("evaluate_leave_one_out", train_loader, limit=limit, cut=max_images is not None)
 
+    # ---- the linear probe (include/hbird_hip_linprobe_class.h) ------------------------------------------------------------------------------
+    def fit_linear_probe(self, l2: float = 1e-3, gtol: float = 1e-5, max_iter: int = 200, Wb0=None):
+        """`linear_probe.linear_probe_fit_classes` on the bank's rows and `self.labels`: a softmax head with an L2 penalty on the normalised
+        features, by full-batch L-BFGS (this engine's own definition -- not DINO's SGD recipe with batch norm; no accuracy has been held to
+        a published one).  Rows of label -1 take no part.  -> `LinearProbe`; the caller closes it."""
+        from hbird_mi.linear_probe import linear_probe_fit_classes
+        if self.index is None or self.index.ntotal == 0:
+            raise ValueError("fit_linear_probe: the bank is empty")
+        with torch.cuda.device(self.gpu_device):
+            return linear_probe_fit_classes(self.index, self.labels, self.num_classes, l2=l2, gtol=gtol, max_iter=max_iter, Wb0=Wb0)
+
+    def evaluate_linear_probe(self, val_loader, l2s=(1e-3,), gtol: float = 1e-5, max_iter: int = 200) -> LinearClassMetrics:
+        """The linear-probe column beside `evaluate`'s k-NN column.  One head per l2 (at most 16, duplicates refused) is fitted on the bank,
+        in DESCENDING l2 order, each warm-started from the one before; then ONE pass over the loader scores them all: per batch
+        each probe's `logits(features)` (`ops.normalize_rows`, then the logits entry) -> `ops.logits_topn` -> `ops.vote_counts`.  Only the count tables reach the host.
+        A `memory_view(...)` is an ordinary instance, so label-subset probes need no code; choosing l2 on a held-out part of the training
+        split is `memory_view(images=kept).evaluate_linear_probe(loader_of_the_other_images, l2s=...)`."""
+        who = "evaluate_linear_probe"
+        l2s = [float(v) for v in (l2s if isinstance(l2s, (list, tuple)) else [l2s])]
+        if not l2s or len(l2s) > _lib.VOTE_MAX_CONFIGS or len(set(l2s)) != len(l2s) or not all(np.isfinite(v) and v >= 0 for v in l2s):
+            raise ValueError(f"{who}: l2s must be 1 to {_lib.VOTE_MAX_CONFIGS} different non-negative numbers, got {l2s}")
+        if self.index is None or self.index.ntotal == 0:
+            raise ValueError(f"{who}: the bank is empty")
+        C, topn = self.num_classes, self.n_top
+        probes, fits, warm = {}, {}, None
+        try:
+            for v in sorted(l2s, reverse=True):
+                probes[v] = self.fit_linear_probe(l2=v, gtol=gtol, max_iter=max_iter, Wb0=warm)
+                warm = probes[v].Wb
+                fits[v] = dict(state=probes[v].state, n_iter=probes[v].n_iter, rows_used=probes[v].rows_used, rows_skipped=probes[v].rows_skipped)
+            counts = torch.zeros((len(l2s), topn), dtype=torch.int64, device=self.gpu_device)
+            per_class = torch.zeros((len(l2s), C, 2), dtype=torch.int64, device=self.gpu_device)
+            n = torch.zeros(1, dtype=torch.int64, device=self.gpu_device)
+            seen = 0
+            with torch.no_grad(), torch.cuda.device(self.gpu_device):
+                for x, y in val_loader:
+                    qlab = self._class_ids(y, who).to(self.gpu_device)
+                    q = self._features(x)                    # (`LinearProbe.logits` normalises the rows: `ops.normalize_rows`, once)
+                    if qlab.numel() != q.shape[0]:
+                        raise ValueError(f"{who}: {qlab.numel()} class ids for {q.shape[0]} images")
+                    seen += q.shape[0]
+                    pred = torch.stack([ops.logits_topn(probes[v].logits(q), topn) for v in l2s])      # [n_cfg, nq, topn]: one configuration per l2
+                    ops.vote_counts(pred, qlab, C, counts, n, per_class)
+            if not seen:
+                raise ValueError(f"{who}: the loader is empty")
+            return LinearClassMetrics(l2s, counts.cpu().numpy(), per_class.cpu().numpy(), int(n.item()), seen - int(n.item()), fits)
+        finally:
+            for probe in probes.values():
+                probe.close()
+
     def close(self) -> None:
         if self.index is not None:
             self.index.close()
@@ -330,5 +406,30 @@ def hbird_knn_classification(model, d_model: int, patch_size: int, dataset_name:
         if leave_one_out:
             return ev.evaluate_leave_one_out(dataset.train_dataloader(), max_images=leave_one_out_images)
         return ev.evaluate(dataset.val_dataloader())
+    finally:
+        ev.close()
+
+
+def hbird_linear_classification(model, d_model: int, patch_size: int, dataset_name: str, data_dir: str, batch_size: int = 64, input_size: int = 224,
+                                augmentation_epoch: int = 1, device: str | torch.device = "cuda", l2s=(1e-3,), gtol: float = 1e-5,
+                                max_iter: int = 200, topn: int = 5, nn_params: Optional[Dict[str, Any]] = None, ftr_extr_fn=None,
+                                feature_fn=None, num_workers: int = 8) -> LinearClassMetrics:
+    """The function form of `HbirdKnnClassification.evaluate_linear_probe`: datasets and features as `hbird_knn_classification` takes them; one
+    softmax head per l2, fitted on the bank of training images and scored on the validation split."""
+    from hbird_mi.data.classify import get_classify_dataset
+    from hbird_mi.models import FeatureExtractor, FeatureExtractorSimple
+    dataset = get_classify_dataset(dataset_name, data_dir, batch_size, num_workers, input_size)
+    if feature_fn is None:
+        S = max(1, int(input_size) // int(patch_size))
+        if ftr_extr_fn is None:
+            feature_fn = FeatureExtractor(model, eval_spatial_resolution=S, d_model=d_model)
+        else:
+            feature_fn = FeatureExtractorSimple(model, ftr_extr_fn=ftr_extr_fn, eval_spatial_resolution=S, d_model=d_model)
+    ev = HbirdKnnClassification(feature_fn, dataset.get_num_classes(), n_neighbours=(1,), topn=topn, nn_params=nn_params, device=device)
+    try:
+        ev.build(dataset.train_dataloader(), augmentation_epoch=augmentation_epoch)
+        last_run_info.clear()
+        last_run_info.update(bank_rows=int(ev.index.ntotal), num_classes=int(ev.num_classes))
+        return ev.evaluate_linear_probe(dataset.val_dataloader(), l2s=l2s, gtol=gtol, max_iter=max_iter)
     finally:
         ev.close()

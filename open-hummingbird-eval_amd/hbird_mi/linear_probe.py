@@ -12,6 +12,10 @@ The fit: L-BFGS with memory 10 from Wb = 0; the first step length is 1 / ||g||_2
 at most 30 halvings); a pair (s, y) is kept when y . s > 1e-10 ||y|| ||s||; every evaluation rounds Wb to fp32.  It ends `converged` when
 ||g||_inf <= gtol, `stalled` when the line search is exhausted (fp32 noise in the Armijo test; a reported state, not an error), `max_iter`
 otherwise.  The defaults l2 = 1e-3, gtol = 1e-5, max_iter = 200 are definitions, not values tuned on real data.
+
+The image-level probe (include/hbird_hip_linprobe_class.h, csrc/hbird_linprobe_class.hip) is the same head on ONE class id per row instead of a
+label row, for up to 16384 classes: `class_logits_of`, `class_loss_grad`, `linear_probe_fit_classes`.  A row of label -1 is skipped like a
+non-finite row; for C <= 256 the bits are those of `loss_grad` on the one-hot label table.
 """
 from __future__ import annotations
 
@@ -92,6 +96,61 @@ def loss_grad(index, Wb, l2: float, return_residuals: bool = False) -> LossGrad:
     return LossGrad(float(loss.value), grad.cpu().numpy(), int(used.value), n - int(used.value), resid)
 
 
+# ---- the image-level probe: one class id per row, any class count up to HB_LINPROBE_CLASS_MAX_C (include/hbird_hip_linprobe_class.h) ----------
+def _class_params(Wb, d: int, dev: torch.device, who: str) -> torch.Tensor:
+    t = Wb if isinstance(Wb, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(Wb), dtype=np.float32))
+    if t.dim() != 2 or t.shape[1] != d + 1 or not t.dtype.is_floating_point:
+        raise ValueError(f"{who}: Wb must be a float [C, {d + 1}] array (bias, then the {d} weights), got {tuple(t.shape)}")
+    if t.shape[0] < 1 or t.shape[0] > _lib.LINPROBE_CLASS_MAX_C:
+        raise ValueError(f"{who}: C must be in [1, {_lib.LINPROBE_CLASS_MAX_C}], got {t.shape[0]}")
+    return t.detach().to(dev, torch.float32).contiguous()
+
+
+def _class_labels(labels, ntotal: int, dev: torch.device, who: str) -> torch.Tensor:
+    t = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
+    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"{who}: labels must be a 1-d integer array (one class id per bank row, -1 = unlabelled), got {t.dtype} {tuple(t.shape)}")
+    if t.shape[0] != ntotal:
+        raise ValueError(f"{who}: {t.shape[0]} labels for a bank of {ntotal} rows")
+    if t.dtype != torch.int32:                           # (an id beyond int32 must not wrap into the valid range)
+        if t.numel() and (int(t.min()) < -(2 ** 31) or int(t.max()) >= 2 ** 31):
+            raise ValueError(f"{who}: a label does not fit int32")
+    return t.detach().to(dev, torch.int32).contiguous()
+
+
+def class_logits_of(index, Wb) -> torch.Tensor:
+    """hb_linprobe_class_logits: z float32 [ntotal, C] (CUDA) of every stored row of `index`, C up to 16384: `logits_of`'s bits."""
+    index = _single_index(index, "class_logits_of")
+    dev = torch.device("cuda", index.device)
+    w = _class_params(Wb, index.d, dev, "class_logits_of")
+    with torch.cuda.device(dev):
+        index.use_current_stream()
+        out = torch.empty((index.ntotal, w.shape[0]), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().hb_linprobe_class_logits(index._h, _p(w), int(w.shape[0]), _p(out)), ValueError)
+    return out
+
+
+def class_loss_grad(index, labels, Wb, l2: float, return_residuals: bool = False) -> LossGrad:
+    """hb_linprobe_class_loss_grad: one evaluation over the whole bank against `labels` ([ntotal] integers in [0, C), -1 = the row is skipped)
+    -> LossGrad as `loss_grad` returns it.  The bank needs no label table."""
+    index = _single_index(index, "class_loss_grad")
+    dev = torch.device("cuda", index.device)
+    w = _class_params(Wb, index.d, dev, "class_loss_grad")
+    y = _class_labels(labels, index.ntotal, dev, "class_loss_grad")
+    if not np.isfinite(float(l2)) or float(l2) < 0:
+        raise ValueError(f"class_loss_grad: l2 must be a non-negative number, got {l2!r}")
+    C = int(w.shape[0])
+    with torch.cuda.device(dev):
+        index.use_current_stream()
+        n = index.ntotal
+        grad = torch.empty((C, index.d + 1), dtype=torch.float64, device=dev)
+        resid = torch.empty((n, C), dtype=torch.float32, device=dev) if return_residuals else None
+        loss, used = ctypes.c_double(0.0), ctypes.c_int64(0)
+        _lib.check(_lib.lib().hb_linprobe_class_loss_grad(index._h, _p(y), _p(w), C, float(l2), ctypes.byref(loss), _p(grad), ctypes.byref(used),
+                                                          _p(resid)), ValueError)
+    return LossGrad(float(loss.value), grad.cpu().numpy(), int(used.value), n - int(used.value), resid)
+
+
 def lbfgs(fun, x0: np.ndarray, gtol: float, max_iter: int):
     """The fit's loop on `fun(x) -> (loss, grad)` (float64 arrays of x0's shape) -> (x, history [(loss, ||g||_inf)], n_iter, state)."""
     x = np.array(x0, dtype=np.float64)
@@ -159,7 +218,8 @@ class LinearProbe:
 
     def logits(self, x: torch.Tensor) -> torch.Tensor:
         """z float32 [..., C] of the tokens x [..., D] (a CUDA tensor on the probe's GPU): the rows are normalised with `ops.normalize_rows`,
-        appended to a cached scratch index (`reset()`, `add` at `set_fp16(0)`) and handed to hb_linprobe_logits -- the bank's own arithmetic."""
+        appended to a cached scratch index (`reset()`, `add` at `set_fp16(0)`) and handed to hb_linprobe_logits -- the bank's own arithmetic
+        (hb_linprobe_class_logits, the same bits, for a probe of more than 256 classes)."""
         D = int(self.weights.shape[1])
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() < 2 or x.shape[-1] != D:
             raise ValueError(f"LinearProbe.logits: expected a CUDA tensor [..., {D}]")
@@ -176,7 +236,7 @@ class LinearProbe:
             ix.use_current_stream()
             ix.reset()
             ix.add(rows, normalize=False)
-            z = logits_of(ix, self.Wb)
+            z = logits_of(ix, self.Wb) if self.num_classes <= _lib.LINPROBE_MAX_C else class_logits_of(ix, self.Wb)
         return z.view(tuple(x.shape[:-1]) + (self.num_classes,))
 
     def close(self) -> None:
@@ -210,6 +270,41 @@ def linear_probe_fit(index, l2: float = 1e-3, gtol: float = 1e-5, max_iter: int 
 
     x, history, n_iter, state = lbfgs(fun, np.zeros((C, D + 1), dtype=np.float64), float(gtol), int(max_iter))
     dev = torch.device("cuda", index.device)
+    wb = torch.from_numpy(x.astype(np.float32)).to(dev)
+    return LinearProbe(wb[:, 1:].contiguous(), wb[:, 0].contiguous(), [dict(loss=f, gmax=g) for f, g in history], n_iter, state, used[0], used[1],
+                       float(l2))
+
+
+def linear_probe_fit_classes(index, labels, num_classes: int, l2: float = 1e-3, gtol: float = 1e-5, max_iter: int = 200, Wb0=None) -> LinearProbe:
+    """Fit the softmax head on the rows of `index` against one class id per row (`labels`: [ntotal] integers in [0, num_classes), -1 = the row
+    takes no part): the image-level linear probe, for up to 16384 classes.  The same L-BFGS and the same `LinearProbe` as `linear_probe_fit`;
+    `Wb0` ([num_classes, D + 1], bias first) is a warm start, None starts at 0.  The defaults are definitions, not values tuned on real data.
+    The definition is this engine's own -- an L2-penalised softmax head on normalised features by full-batch L-BFGS, not DINO's SGD recipe with
+    batch norm; no accuracy has been held to a published one.  ValueError for a HipMultiIndex and under torch.distributed."""
+    index = _single_index(index, "linear_probe_fit_classes")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        raise ValueError(f"linear_probe_fit_classes: max_iter must be a non-negative integer, got {max_iter!r}")
+    if not (np.isfinite(float(l2)) and float(l2) >= 0 and np.isfinite(float(gtol)) and float(gtol) >= 0):
+        raise ValueError("linear_probe_fit_classes: l2 and gtol must be non-negative numbers")
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= int(num_classes) <= _lib.LINPROBE_CLASS_MAX_C:
+        raise ValueError(f"linear_probe_fit_classes: C must be in [1, {_lib.LINPROBE_CLASS_MAX_C}], got {num_classes!r}")
+    C, D = int(num_classes), index.d
+    dev = torch.device("cuda", index.device)
+    y = _class_labels(labels, index.ntotal, dev, "linear_probe_fit_classes")
+    if Wb0 is None:
+        x0 = np.zeros((C, D + 1), dtype=np.float64)
+    else:
+        x0 = _class_params(Wb0, D, dev, "linear_probe_fit_classes").cpu().numpy().astype(np.float64)
+        if x0.shape[0] != C:
+            raise ValueError(f"linear_probe_fit_classes: Wb0 has {x0.shape[0]} classes, num_classes is {C}")
+    used = [0, 0]
+
+    def fun(x):
+        r = class_loss_grad(index, y, x.astype(np.float32), l2)
+        used[:] = [r.used, r.skipped]
+        return r.loss, r.grad
+
+    x, history, n_iter, state = lbfgs(fun, x0, float(gtol), int(max_iter))
     wb = torch.from_numpy(x.astype(np.float32)).to(dev)
     return LinearProbe(wb[:, 1:].contiguous(), wb[:, 0].contiguous(), [dict(loss=f, gmax=g) for f, g in history], n_iter, state, used[0], used[1],
                        float(l2))

@@ -445,3 +445,24 @@ def vote_counts(pred: torch.Tensor, qlabels: torch.Tensor, C: int, counts: torch
         return
     _lib.check(_lib.lib().hb_vote_counts(_p(pred), _p(qlabels), nq, n_cfg, topn, int(C), _p(counts), _p(class_counts), _p(n), _stream(pred)),
                ValueError)
+
+
+def logits_topn(logits: torch.Tensor, topn: int = 5) -> torch.Tensor:
+    """hb_logits_topn: logits [nq, C] fp32 -> pred [nq, topn] int32 -- the classes by descending logit, ties to the lower class id; a NaN
+    logit ranks below every number and is never written; the tail holds -1 where C < topn or fewer than topn logits are numbers.  The form
+    `vote_counts` takes is pred[None]."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError(f"logits_topn: logits must be a float32 [nq, C] tensor, got {getattr(logits, 'dtype', type(logits))} "
+                         f"{tuple(getattr(logits, 'shape', ()))}")
+    if isinstance(topn, bool) or not isinstance(topn, int) or not 1 <= topn <= _lib.VOTE_MAX_TOP:
+        raise ValueError(f"logits_topn: topn={topn!r} must be an integer in [1, {_lib.VOTE_MAX_TOP}]")
+    nq, C = logits.shape
+    if not 1 <= C <= _lib.LINPROBE_CLASS_MAX_C:
+        raise ValueError(f"logits_topn: C must be in [1, {_lib.LINPROBE_CLASS_MAX_C}], got {C}")
+    _need_cuda(logits)
+    logits = logits.contiguous()
+    pred = torch.empty((nq, topn), dtype=torch.int32, device=logits.device)
+    if nq == 0:                                               # an empty call (an empty tensor has no address to hand over)
+        return pred
+    _lib.check(_lib.lib().hb_logits_topn(_p(logits), nq, C, topn, _p(pred), _stream(logits)), ValueError)
+    return pred
